@@ -9,10 +9,18 @@ of `synth.config("target")`, the same seeded SplitMix64 generator the parity tes
 golden digests use (one generator is the single source of truth).
 
     python bench.py                                   # N=1: settle, 50 warm-up steps, 1 000 timed steps
-    python bench.py --gpus 1 --steps 20 --warmup 5    # what the driver runs
+    python bench.py --gpus 1 --steps 20 --warmup 5    # the headline alone: set up, warm up, time the steps, print the line
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full            # ... and every other leg (see below)
+    python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs D  # ... and the last step's results as D/<name>.npy
     python bench.py --phase sort                      # the radix-sort phase of the large path, one 33.5 M-partition topic
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W [--scaling strong --workload cfg4]
+
+A plain run prints the headline (`metric`, `value`, `unit`, `ms_per_step` = the wall time of the K timed steps over K, the
+kernels' HIP-event time and the HBM roofline reading derived from it) and nothing that takes work of its own.  `--full` adds,
+after the timed region: the cold call, the oracle parity check and `cpu_baseline`, `host_boundary`, the other BASELINE
+configs and `small_call`, the latest / all-none / same-buffer / wire-out forms of the batch, the PMC traffic of live
+rocprofv3 passes, the radix-sort phase and `lag_ratio` (the `--no-*` options switch single legs off again).
 
 Timing.  The target batch runs the package at its power cap and the power controller needs
 ~50 ms of back-to-back launches to settle, so before the W counted
@@ -114,7 +122,20 @@ def parse_args():
                          "at the target (1 = the round 1-4 form: every step on the same buffers)")
     ap.add_argument("--no-live-traffic", action="store_true",
                     help="roofline.traffic from the committed PMC summary instead of two rocprofv3 child passes in this run")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beyond the headline: cold call, oracle parity, cpu_baseline, host_boundary, the other "
+                         "BASELINE configs, small calls, the latest / all-none / same-buffer forms, live PMC traffic, the sort "
+                         "phase, lag_ratio (the --no-* options above switch single legs off again).  Without it a run sets up, "
+                         "warms up, times the steps, writes --dump-outputs and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float64): the partition "
+                         "order, member ranks and per-consumer totals; an output larger than its share of 64 MB is replaced by a "
+                         "fixed, seeded sample of its positions")
+    args = ap.parse_args()
+    if not args.full:
+        # a plain run measures the headline only: every leg beyond the timed steps is behind --full
+        args.no_cpu_baseline = args.no_configs = args.no_sort_phase = args.no_live_traffic = True
+    return args
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -364,6 +385,33 @@ def kernel_name(max_p, max_c):
 
 FROZEN_FULL = os.path.join(ROOT, "tests", "golden", "oracle_frozen_full.json")   # tests/golden/make_golden.py --full
 
+DUMP_BYTES = 60 << 20           # what --dump-outputs writes at most (float64 elements; under the 64 MB it may write)
+DUMP_SEED = 20240611
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every array of `arrays` (name -> 1-D device tensor or host array) as dirname/<name>.npy in float64 (exact for
+    the ids, ranks and totals here: all below 2^53).  Each array gets an equal share of DUMP_BYTES; a longer one is replaced by
+    the elements at a fixed, seeded sample of its positions in increasing order (the same positions for arrays of one length,
+    so that a partition's id and member rank stay paired).  The inputs are seeded too: two builds run with the same arguments
+    write files that compare element for element."""
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_BYTES // 8 // max(1, len(arrays))
+    for name, a in arrays.items():
+        n = int(a.shape[0])
+        if n > share:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=share, replace=False))
+            if isinstance(a, np.ndarray):
+                a = a[idx]
+            else:
+                import torch
+                a = a.index_select(0, torch.from_numpy(idx).to(a.device))
+        if not isinstance(a, np.ndarray):
+            a = a.cpu().numpy()
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+        print("dump-outputs: %s.npy, %d of %d elements%s" % (name, min(n, share), n, " (seeded sample)" if n > share else ""),
+              file=sys.stderr)
+
 
 CACHE_PROOF_BYTES = 3 * 256 * (1 << 20)         # three Infinity Caches' worth between two touches of the same bytes
 MAX_ROTATION = 24
@@ -588,14 +636,15 @@ def run_small_calls(N, ctx):
                     "launch, PCIe round trips and completion"}
 
 
-def run_sort_phase(torch, N, ctx, dev, n, reps, stream, form="single", live=False, ids=None):
+def run_sort_phase(torch, N, ctx, dev, n, reps, stream, form="single", live=False, ids=None, warmup=1, dump_dir=None):
     """The radix-sort phase of the large path on one topic of n partitions (no consumers: keys, sort, ids).  Times come
     from HIP events the library records around its phases (LA_FLAG_PROFILE / la_last_phase_times)."""
     w = sort_phase_workload(n, torch, dev, ids)
     torch.cuda.empty_cache()
     sh = DeviceShard(torch, N, dev, w, 0, 1, False, "auto",
                      flags=N.LA_FLAG_PROFILE | (N.LA_FLAG_SORT_MULTIKERNEL if form == "multi" else 0))
-    ctx.assign_batch_device(sh.batch, stream)                      # scratch allocation, first touch
+    for _ in range(max(1, warmup)):
+        ctx.assign_batch_device(sh.batch, stream)                  # scratch allocation, first touch
     ctx.sync(stream)
     sort_ms, keys_ms, ids_ms = [], [], []
     t0 = time.perf_counter()
@@ -605,6 +654,8 @@ def run_sort_phase(torch, N, ctx, dev, n, reps, stream, form="single", live=Fals
         t = ctx.last_phase_times()
         sort_ms.append(t.sort_ms); keys_ms.append(t.keys_ms); ids_ms.append(t.greedy_ms)
     call_ms = (time.perf_counter() - t0) / reps * 1e3
+    if dump_dir:
+        dump_outputs(dump_dir, {"partition_id": sh.out_pid[:n]})
     ms = float(np.mean(sort_ms))
     bytes_id, bytes_key = SORT_BYTES[form]
     keys_first = bool(getattr(t, "keys_first", 0))
@@ -691,12 +742,13 @@ def main():
     # ---- --phase sort: its own line -------------------------------------------------------------------------
     if args.phase == "sort":
         n = args.partitions or SORT_PHASE_PARTITIONS
-        reps = max(1, min(args.steps, 20))
-        sp = run_sort_phase(torch, N, ctx, dev, n, reps, stream, args.sort_form, live=not args.no_live_traffic)
+        reps = max(1, args.steps)
+        sp = run_sort_phase(torch, N, ctx, dev, n, reps, stream, args.sort_form, live=not args.no_live_traffic,
+                            warmup=args.warmup, dump_dir=args.dump_outputs if rank == 0 else None)
         if rank == 0:
             print(json.dumps({
                 "metric": "radix-sort phase of the large path, partitions sorted/sec", "value": round(n / (sp["kernel_ms"] * 1e-3), 1),
-                "unit": "partitions/sec", "n_gpus": 1, "steps": reps, "warmup": 1, "ms_per_step": sp["kernel_ms"],
+                "unit": "partitions/sec", "n_gpus": 1, "steps": reps, "warmup": max(1, args.warmup), "ms_per_step": sp["kernel_ms"],
                 "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "int64", "data": "synthetic",
                 "config": {"workload": "1 topic x %d partitions x 0 consumers, uniform [0, 2^40) lags, randomly permuted ids" % n,
                            "phase": "sort"},
@@ -881,20 +933,21 @@ def main():
 
     # strong scaling: the gathered buffer, stripped of its padding, is the global assignment -- checked below
     gathered_host = None
-    if strong and rank == 0:
+    if strong and rank == 0 and (args.full or args.dump_outputs):
         if do_gather and packed and not unpack:
             # the map was left in the wire format: expand it here, after the timed region, with the library's own decoder
-            # (and time the expansion: what a consumer that wants the two int32 arrays pays on top of a step)
+            # (and, with --full, time the expansion: what a consumer that wants the two int32 arrays pays on top of a step)
             tmp = torch.empty(2 * world * cap, device=dev, dtype=torch.int32)
             ctx.unpack_results(world * cap, wire_recv.data_ptr(), fmt, tmp.data_ptr(), tmp.data_ptr() + 4 * world * cap, stream)
             ctx.sync(stream)
-            u0, u1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            u0.record()
-            for _ in range(10):
-                ctx.unpack_results(world * cap, wire_recv.data_ptr(), fmt, tmp.data_ptr(), tmp.data_ptr() + 4 * world * cap, stream)
-            u1.record()
-            ctx.sync(stream)
-            unpack_ms_max = float(u0.elapsed_time(u1)) / 10
+            if args.full:
+                u0, u1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                u0.record()
+                for _ in range(10):
+                    ctx.unpack_results(world * cap, wire_recv.data_ptr(), fmt, tmp.data_ptr(), tmp.data_ptr() + 4 * world * cap, stream)
+                u1.record()
+                ctx.sync(stream)
+                unpack_ms_max = float(u0.elapsed_time(u1)) / 10
             g = tmp.cpu().numpy().reshape(2, world * cap)
             gathered_host = (sharding.strip_padding(g[0], counts, cap), sharding.strip_padding(g[1], counts, cap))
         elif do_gather and packed:
@@ -907,6 +960,16 @@ def main():
         else:
             gathered_host = (sh.out_pid[:n_part].cpu().numpy(), sh.out_rank[:n_part].cpu().numpy())
 
+    # ---- --dump-outputs: what the last timed step computed, before any leg of --full touches the buffers ----
+    if args.dump_outputs and rank == 0:
+        if strong:                             # the global assignment every rank holds after the step's all-gather
+            dump_outputs(args.dump_outputs, {"partition_id": gathered_host[0], "member_rank": gathered_host[1]})
+        else:
+            # the copy the last step worked on (the fused wire form wrote no int32 arrays: sets[0] was rerun above)
+            last = sets[0] if fused else sets[(step_no[0] - 1) % rot]
+            dump_outputs(args.dump_outputs, {"partition_id": last.out_pid[:n_part], "member_rank": last.out_rank[:n_part],
+                                             "total_lag": last.out_total[: last.k]})
+
     if rank != 0:
         if use_dist:
             dist.barrier()                     # rank 0 is still measuring its extras and checking the oracle: leave together
@@ -914,20 +977,22 @@ def main():
         return
 
     # ---- what one rebalance sees: the first call after a second of idle (rank 0; the other ranks wait at the barrier) ----
-    torch.cuda.synchronize()
-    time.sleep(1.0)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    c0 = time.perf_counter()
-    e0.record()
-    ctx.assign_batch_device(b, stream)
-    e1.record()
-    ctx.sync(stream)
-    cold_wall = (time.perf_counter() - c0) * 1e3
-    cold_ms = float(e0.elapsed_time(e1))
-    cold = {"ms": round(cold_ms, 4), "wall_ms": round(cold_wall, 4), "value": round(n_part / (cold_ms * 1e-3), 1),
-            "what": "ONE la_assign_batch_device call (HIP events around it; wall = enqueue + la_sync) after the GPU "
-                    "idled for 1 s: clocks and power state as a rebalance finds them%s"
-                    % (" (rank 0's shard, no gather)" if world > 1 else "")}
+    cold = None
+    if args.full:
+        torch.cuda.synchronize()
+        time.sleep(1.0)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        c0 = time.perf_counter()
+        e0.record()
+        ctx.assign_batch_device(b, stream)
+        e1.record()
+        ctx.sync(stream)
+        cold_wall = (time.perf_counter() - c0) * 1e3
+        cold_ms = float(e0.elapsed_time(e1))
+        cold = {"ms": round(cold_ms, 4), "wall_ms": round(cold_wall, 4), "value": round(n_part / (cold_ms * 1e-3), 1),
+                "what": "ONE la_assign_batch_device call (HIP events around it; wall = enqueue + la_sync) after the GPU "
+                        "idled for 1 s: clocks and power state as a rebalance finds them%s"
+                        % (" (rank 0's shard, no gather)" if world > 1 else "")}
 
     ms_per_step = elapsed / args.steps * 1e3
     value = n_total * args.steps / elapsed
@@ -955,7 +1020,7 @@ def main():
                 "algorithmic_bytes_per_partition": bpp,
                 "algorithmic_bytes_per_launch": bpp * n_part,
                 # the same bytes over the time of ONE call after a second of idle: the regime a real rebalance lives in
-                "frac_cold": round(bpp * n_part / (cold_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)}
+                "frac_cold": round(bpp * n_part / (cold_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if cold else None}
     roofline["frac_rotating"] = roofline["frac"] if rot > 1 else None
     roofline["rotation"] = {"sets": rot, "bytes_resident": int(rot * (bpp * n_part + 8 * sh.k)),
                             "what": "the timed steps rotate over %d distinct resident copies of the batch (inputs and result buffers): "
@@ -1041,7 +1106,7 @@ def main():
 
     # ---- quality metric of BASELINE.json: max/min per-consumer total lag per topic (min clamped to 1) ----
     lag_ratio = None
-    if uniform and C > 0:
+    if args.full and uniform and C > 0:
         tot = sh.out_total[: b.n_topics * C].reshape(b.n_topics, C).to(torch.float64)
         ratio = tot.max(dim=1).values / tot.min(dim=1).values.clamp(min=1.0)
         lag_ratio = {"mean": round(float(ratio.mean()), 4), "p99": round(float(torch.quantile(ratio[:1000000], 0.99)), 4),
@@ -1394,9 +1459,11 @@ def main():
                              "elem_bytes": int(fmt.elem_bytes) if packed else 8, "id_bits": int(fmt.id_bits) if packed else None,
                              "gather_bytes_per_rank": int(gather_bytes_per_rank), "unpacked_in_step": bool(unpack),
                              "pack_ms": round(pack_ms_max, 4), "gather_ms": round(gather_ms_max, 4), "unpack_ms": round(unpack_ms_max, 4),
-                             "unpack_ms_source": ("inside the step" if unpack else "rank 0, 10 back-to-back expansions after the timed region") if packed else None,
+                             "unpack_ms_source": ("inside the step" if unpack else
+                                                  "rank 0, 10 back-to-back expansions after the timed region" if args.full else
+                                                  "not measured: the expansion after the timed region is timed with --full") if packed else None,
                              "value_if_unpacked_in_step": (round(n_total / ((elapsed / args.steps) + unpack_ms_max * 1e-3), 1)
-                                                           if (packed and not unpack) else None),
+                                                           if (packed and not unpack and args.full) else None),
                              "kernels_ms": round(kern_ms_max, 4)} if do_gather else None),
                    "backend": ("rccl" if backend == "nccl" else "gloo, ranks sharing devices (test hook: not a performance number)") if use_dist else None,
                    "bounds_hint": ({"max_end_offset": sh.bounds[0], "max_partition_id": sh.bounds[1],
@@ -1412,7 +1479,7 @@ def main():
                                "gloo and with RCCL at one rank); roofline.wire_out is what one GPU can say about the N > 1 step's kernels"
                                if world == 1 else
                                "strong scaling: ONE batch split over the ranks by la_plan_shards, one all-gather per step inside the timed region")},
-        "cold_call_ms": cold["ms"],
+        "cold_call_ms": cold["ms"] if cold else None,
         "cold_call": cold,
         "sort_phase": sort_phase,
         "lag_ratio": lag_ratio,

@@ -23,7 +23,7 @@ def _run(n, extra, env_extra):
     port = 29600 + os.getpid() % 300 + n
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n), "--master-addr",
            "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "5",
-           "--warmup", "2", "--settle-ms", "5", "--no-sort-phase"] + extra
+           "--warmup", "2", "--settle-ms", "5", "--full", "--no-sort-phase"] + extra
     out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]

@@ -235,13 +235,14 @@ def test_key32_greedy_model_equals_the_literal_oracle(P, C, kind, seed):
         assert redone == 0                                                      # drop == 0: the key is exact, ties included
 
 
-def test_generated_sort_networks_sort_in_the_lane_level_simulator_and_are_current():
+def test_generated_sort_networks_sort_in_the_lane_level_simulator_and_are_current(tmp_path):
     """la_sort32_net.h is generated (tools/gen_sort32_net.py): the committed header is what the generator emits today, and the
     instruction streams -- DPP moves, v_permlane*_swap, v_med3_u32 with data-driven direction -- sort 64 / 128 / 256 keys in a
     lane-level simulator of exactly those instructions (random keys, heavy duplicates, all-ones sentinels, reversed input)."""
     import importlib.util
     import os
     import random
+    import shutil
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -249,9 +250,14 @@ def test_generated_sort_networks_sort_in_the_lane_level_simulator_and_are_curren
     g = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(g)
     header = os.path.join(root, "kafka_lag_based_assignor_amd", "csrc", "la_sort32_net.h")
-    before = open(header).read()
-    subprocess.check_call([sys.executable, os.path.join(root, "tools", "gen_sort32_net.py")], stdout=subprocess.DEVNULL)
-    assert open(header).read() == before, "la_sort32_net.h is stale: run tools/gen_sort32_net.py"
+    # the generator writes the header beside itself: run a copy in a scratch tree, so that the checkout (and the header's mtime,
+    # which the build compares with its objects) is left alone
+    os.makedirs(tmp_path / "tools")
+    os.makedirs(tmp_path / "kafka_lag_based_assignor_amd" / "csrc")
+    shutil.copy(os.path.join(root, "tools", "gen_sort32_net.py"), tmp_path / "tools")
+    subprocess.check_call([sys.executable, str(tmp_path / "tools" / "gen_sort32_net.py")], stdout=subprocess.DEVNULL)
+    emitted = (tmp_path / "kafka_lag_based_assignor_amd" / "csrc" / "la_sort32_net.h").read_text()
+    assert open(header).read() == emitted, "la_sort32_net.h is stale: run tools/gen_sort32_net.py"
     random.seed(7)
     for E in (1, 2, 4):
         ins = g.gen(E)

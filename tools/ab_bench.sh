@@ -16,9 +16,9 @@ for rep in 1 2 3; do
   for lib in "$@"; do
     [ "$lib" = default ] && unset LA_LIB_PATH || export LA_LIB_PATH=$R/$lib
     if [ "$WHAT" = sort ]; then
-      timeout 200 python bench.py --phase sort --steps 10 --no-live-traffic $ARGS > $O/b.json 2> $O/b.err
+      timeout 200 python bench.py --phase sort --steps 10 --full --no-live-traffic $ARGS > $O/b.json 2> $O/b.err
     else
-      timeout 120 python bench.py --steps 1000 --no-cpu-baseline --no-sort-phase --no-live-traffic $ARGS > $O/b.json 2> $O/b.err
+      timeout 120 python bench.py --steps 1000 --full --no-cpu-baseline --no-sort-phase --no-live-traffic $ARGS > $O/b.json 2> $O/b.err
     fi
     python3 - <<PY | tee -a $O/summary.txt
 import json

@@ -8,14 +8,14 @@
 #   build      __graft_entry__.build() + smoke()
 #   tests      pytest -m gpu (TESTS_K='-k expr' narrows it; TESTS_FILES='tests/a.py tests/b.py')
 #   stress     tools/stress_gpu.py (STRESS_ARGS, STRESS_SEED0)
-#   bench      bench.py --gpus 1 --steps 20 --warmup 5  (the driver's command)  -> bench_driver.json + a digest
-#   benchlong  bench.py (default 1000 steps)
-#   stats      rocprofv3 --kernel-trace --stats of the driver's bench command (no oracle legs)
+#   bench      bench.py --gpus 1 --steps 20 --warmup 5 --full  (the headline command + every other leg)  -> bench_driver.json + a digest
+#   benchlong  bench.py --full (default 1000 steps)
+#   stats      rocprofv3 --kernel-trace --stats of the plain bench command (no oracle legs)
 #   pmc        FETCH_SIZE / WRITE_SIZE / SQ / LDS counter passes over tools/pmc_probe.py (PROBE_ARGS) -> pmc_summary.json
 #   cfg5       tools/cfg5_probe.py + rocprofv3 stats of the cfg5 call (large_probe) ; CFG5_ARGS for other sizes
 #   block      tools/block_probe.py + rocprofv3 stats of cfg2b and two block batches
 #   blockpmc   LDS / VALU counter passes over the cfg2b call
-#   sort       bench.py --phase sort + rocprofv3 stats / timeline of the 33.5 M-partition sort
+#   sort       bench.py --phase sort --full + rocprofv3 stats / timeline of the 33.5 M-partition sort
 #   latency    tools/latency_probe.py + tools/latency_c.c at the C ABI
 #   lab:CMD    any command (quoted), output to lab_N.txt  -- for one-off A/B runs, e.g. "lab:LA_X=1 python tools/cfg5_probe.py"
 set -u
@@ -39,10 +39,10 @@ for STEP in "$@"; do
     stress)
       STRESS_SEED0=${STRESS_SEED0:-61000} timeout 900 python tools/stress_gpu.py ${STRESS_ARGS:-100 40 60 40 10 10 300} 2>&1 | grep -v amdgpu.ids | tail -4 | tee $O/stress.txt ;;
     bench)
-      timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver.json 2> $O/bench.err; tail -2 $O/bench.err
+      timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_driver.json 2> $O/bench.err; tail -2 $O/bench.err
       python tools/bench_digest.py $O/bench_driver.json | tee $O/bench_digest.txt ;;
     benchlong)
-      timeout 600 python bench.py > $O/bench.json 2>> $O/bench.err; python tools/bench_digest.py $O/bench.json ;;
+      timeout 600 python bench.py --full > $O/bench.json 2>> $O/bench.err; python tools/bench_digest.py $O/bench.json ;;
     stats)
       prof --kernel-trace --stats --output-format csv -d $O/stats -- python $R/bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-sort-phase > $O/stats.log 2>&1
       find $O/stats -name "*kernel_stats.csv" | head -1 | xargs head -6 | cut -c1-200 ;;
@@ -66,7 +66,7 @@ for STEP in "$@"; do
       LAG_BITS=40 prof --pmc SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY --kernel-trace --output-format csv -d $O/pmc_block -- python $R/tools/block_probe.py 1,10000,128 > $O/pmc_block.log 2>&1
       python tools/pmc_parse.py $O/pmc_block > $O/pmc_block_summary.json 2> $O/pmc_block_parse.err; head -c 1500 $O/pmc_block_summary.json; echo ;;
     sort)
-      timeout 300 python bench.py --phase sort > $O/bench_sort.json 2>> $O/bench.err; cut -c1-900 $O/bench_sort.json
+      timeout 300 python bench.py --phase sort --full > $O/bench_sort.json 2>> $O/bench.err; cut -c1-900 $O/bench_sort.json
       prof --kernel-trace --stats --output-format csv -d $O/stats_sort -- python $R/tools/large_probe.py --partitions 33554432 --consumers 0 --launches 8 > $O/stats_sort.log 2>&1
       python3 tools/trace_timeline.py $O/stats_sort > $O/sort_timeline.txt 2>&1; tail -30 $O/sort_timeline.txt ;;
     latency)
