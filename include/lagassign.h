@@ -49,6 +49,14 @@
  *   out_total_lag[k]    final consumerTotalLags of consumer k of that topic
  *                       (Main.java:265, the value the debug summary prints, :283-291)
  *
+ * Buffers (every entry point, host and device arrays alike; tests/test_buffer_contract_gpu.py holds the library to it):
+ *   - an array needs only its element's alignment: a view that starts at any element of a larger buffer (one shard's
+ *     slice, t[1:]) is as good as a fresh allocation;
+ *   - results are written only inside [0, N) / [0, K) (member_off: [0, M]) of the arrays given for them -- the wide
+ *     stores of the kernels never reach past the last element or before the first;
+ *   - inputs (the const arrays, h_part_off / h_cons_off included, and the caller's own arrays of the in-place
+ *     pipelines) are never written, not even as scratch.
+ *
  * Arithmetic is Java's: 64-bit two's-complement wrap on subtract/add, signed compares.
  * Results are bit-identical to the reference for every input, including negative lags
  * and overflowing totals.
@@ -337,8 +345,12 @@ typedef struct la_device_batch {
     int32_t flags;                   /* LA_FLAG_*; 0 in normal use                       */
     int64_t n_partitions;            /* N                                                */
     int64_t n_consumers;             /* K                                                */
-    /* Shape hint: upper bounds over the batch.  A topic that exceeds them is reported
-     * as LA_ESHAPE by la_sync(); nothing is written for it. */
+    /* Shape hint: upper bounds over the batch.  With a hint within one wave tile (1024
+     * partitions x 64 consumers) and no LA_FLAG_RAGGED, a topic that exceeds it is reported
+     * as LA_ESHAPE by la_sync(); nothing is written for it -- neither its partitions' results
+     * nor its consumers' totals -- and the other topics of the batch are assigned as usual.
+     * With a larger hint, or LA_FLAG_RAGGED, the library routes every topic by its real
+     * shape (h_part_off / h_cons_off, below): a topic over the hint is assigned like any other. */
     int64_t max_partitions_per_topic;
     int64_t max_consumers_per_topic;
     /* device pointers */

@@ -255,6 +255,21 @@ def _check_out3(out, n: int, k: int):
     return out_p, out_m, out_t
 
 
+def _check_out_grouped(out, m: int, n: int, k: int):
+    """Caller-owned grouped result buffers (member_off int64[M+1], grouped_topic int32[N] or None, grouped_partition int32[N],
+    totals int64[K] or None): contiguous, of the right type and size, as for _check_out3."""
+    off, g_t, g_p, out_t = out
+
+    def ok(a, dtype, size, optional=False):
+        if a is None:
+            return optional
+        return isinstance(a, np.ndarray) and a.dtype == dtype and a.size == size and a.flags.c_contiguous
+
+    if not (ok(off, np.int64, m + 1) and ok(g_t, np.int32, n, True) and ok(g_p, np.int32, n) and ok(out_t, np.int64, k, True)):
+        raise ValueError("out buffers must be contiguous int64[M+1], int32[N] or None, int32[N], int64[K] or None")
+    return off, g_t, g_p, out_t
+
+
 def plan_shards(part_off, n_shards: int) -> np.ndarray:
     """la_plan_shards: the library's own planner (pure host code, no device needed).  Returns int32
     bounds[n_shards + 1]: shard r owns topics [bounds[r], bounds[r+1])."""
@@ -406,10 +421,14 @@ class Context:
         self._check(self._lib.la_wake(self._h))
 
     # -- host-buffer entry points ------------------------------------------------
-    def compute_lag(self, begin, end, committed, reset_mode: int) -> np.ndarray:
+    def compute_lag(self, begin, end, committed, reset_mode: int, out=None) -> np.ndarray:
+        """`out`: a caller-owned contiguous int64[N] for the lags (as for assign_batch)."""
         end, committed = _a64(end), _a64(committed)
         begin = None if begin is None else _a64(begin)
-        out = np.empty_like(end)
+        if out is None:
+            out = np.empty_like(end)
+        elif not (isinstance(out, np.ndarray) and out.dtype == np.int64 and out.size == end.size and out.flags.c_contiguous):
+            raise ValueError("out must be a contiguous int64[N]")
         self._check(self._lib.la_compute_lag(self._h, end.size, _p64(begin), _p64(end), _p64(committed),
                                              reset_mode, _p64(out)))
         return out
@@ -465,18 +484,22 @@ class Context:
         return out_p, out_m, out_t
 
     def assign_batch_grouped_sparse(self, part_off, partition_id, end, committed, reset_mode: int, none_index, none_begin,
-                                    cons_off, cons_rank, n_members: int, want_totals: bool = True, want_topic: bool = True):
-        """la_assign_batch_grouped_sparse -> (member_off, grouped_topic or None, grouped_partition, totals or None)."""
+                                    cons_off, cons_rank, n_members: int, want_totals: bool = True, want_topic: bool = True, out=None):
+        """la_assign_batch_grouped_sparse -> (member_off, grouped_topic or None, grouped_partition, totals or None).
+        `out`: caller-owned buffers of those four (None entries: not wanted), as for assign_batch_grouped."""
         part_off, cons_off = _a64(part_off), _a64(cons_off)
         partition_id, cons_rank = _a32(partition_id), _a32(cons_rank)
         end, committed = _a64(end), _a64(committed)
         none_index = None if none_index is None else _a64(none_index)
         none_begin = None if none_begin is None else _a64(none_begin)
         n_none = 0 if none_index is None else none_index.size
-        off = np.zeros(n_members + 1, dtype=np.int64)
-        g_t = np.empty(partition_id.size, dtype=np.int32) if want_topic else None
-        g_p = np.empty(partition_id.size, dtype=np.int32)
-        out_t = np.zeros(cons_rank.size, dtype=np.int64) if want_totals else None
+        if out is not None:
+            off, g_t, g_p, out_t = _check_out_grouped(out, n_members, partition_id.size, cons_rank.size)
+        else:
+            off = np.zeros(n_members + 1, dtype=np.int64)
+            g_t = np.empty(partition_id.size, dtype=np.int32) if want_topic else None
+            g_p = np.empty(partition_id.size, dtype=np.int32)
+            out_t = np.zeros(cons_rank.size, dtype=np.int64) if want_totals else None
         self._check(self._lib.la_assign_batch_grouped_sparse(self._h, part_off.size - 1, _p64(part_off), _p32(partition_id),
                                                              _p64(end), _p64(committed), reset_mode, n_none,
                                                              _p64(none_index), _p64(none_begin), _p64(cons_off),
@@ -503,18 +526,23 @@ class Context:
         return out_p, out_m, out_t
 
     def assign_batch_grouped(self, part_off, partition_id, begin, end, committed, reset_mode: int, cons_off, cons_rank,
-                             n_members: int, want_totals: bool = True, want_topic: bool = True
+                             n_members: int, want_totals: bool = True, want_topic: bool = True, out=None
                              ) -> Tuple[np.ndarray, Optional[np.ndarray], np.ndarray, Optional[np.ndarray]]:
         """la_assign_batch_grouped: assign and every member's list in ONE call (for a small batch: one upload, one
-        download).  Returns (member_off [M+1], grouped_topic [N] or None, grouped_partition [N], totals [K] or None)."""
+        download).  Returns (member_off [M+1], grouped_topic [N] or None, grouped_partition [N], totals [K] or None).
+        `out` = caller-owned (member_off int64[M+1], grouped_topic int32[N] or None, grouped_partition int32[N], totals int64[K]
+        or None) to reuse across calls; its None entries replace want_topic / want_totals."""
         part_off, cons_off = _a64(part_off), _a64(cons_off)
         partition_id, cons_rank = _a32(partition_id), _a32(cons_rank)
         end, committed = _a64(end), _a64(committed)
         begin = None if begin is None else _a64(begin)
-        off = np.zeros(n_members + 1, dtype=np.int64)
-        g_t = np.empty(partition_id.size, dtype=np.int32) if want_topic else None
-        g_p = np.empty(partition_id.size, dtype=np.int32)
-        out_t = np.zeros(cons_rank.size, dtype=np.int64) if want_totals else None
+        if out is not None:
+            off, g_t, g_p, out_t = _check_out_grouped(out, n_members, partition_id.size, cons_rank.size)
+        else:
+            off = np.zeros(n_members + 1, dtype=np.int64)
+            g_t = np.empty(partition_id.size, dtype=np.int32) if want_topic else None
+            g_p = np.empty(partition_id.size, dtype=np.int32)
+            out_t = np.zeros(cons_rank.size, dtype=np.int64) if want_totals else None
         self._check(self._lib.la_assign_batch_grouped(self._h, part_off.size - 1, _p64(part_off), _p32(partition_id),
                                                       _p64(begin), _p64(end), _p64(committed), reset_mode,
                                                       _p64(cons_off), _p32(cons_rank), n_members, _p64(off), _p32(g_t),

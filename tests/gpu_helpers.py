@@ -205,4 +205,92 @@ def _wire_call(ctx, w, fmt, bounds, latest=False, flags=0, hint=None):
     return raw, out_total.cpu().numpy()[: w.cons_rank.size]
 
 
-__all__ = ['ROOT', '_expected', '_workload', '_pinned', '_batch_of', '_device_call', '_same3', '_sort_topic', '_pinned_copy', '_grouped_expect', '_one_topic', '_wire_call']
+# ---- guarded buffers: writes outside the results, inputs that must not change, element-aligned views --------------------------
+GUARD_BYTES = 4096                      # each side; stray stores of the wide-store forms land inside the test's own allocation
+SENTINEL = -7                           # what an output holds before the call (and where the header says nothing is written)
+SHIFTS = (0, 1, 3)                      # element offsets of a view: 1 and 3 leave int32 / int64 arrays off every 16-byte boundary
+
+
+def guard_pattern(nbytes):
+    """The fixed byte pattern of a guard band (varied, so a store of any constant shows)."""
+    i = np.arange(nbytes, dtype=np.uint32)
+    return ((i * 37 + 0xA5) & 0xFF).astype(np.uint8)
+
+
+def guard_violation(raw, start, end):
+    """First byte of `raw` outside [start, end) that differs from guard_pattern: None, or ("before" | "after", offset in bytes
+    from the array's first byte (negative) or from its end (>= 0), the byte found)."""
+    raw = np.asarray(raw, np.uint8)
+    pat = guard_pattern(raw.size)
+    bad = np.flatnonzero(raw[:start] != pat[:start])
+    if bad.size:
+        j = int(bad[-1])                                        # the one nearest the array: where a tail store would land
+        return "before", j - start, int(raw[j])
+    bad = np.flatnonzero(raw[end:] != pat[end:])
+    if bad.size:
+        j = int(bad[0])
+        return "after", j, int(raw[end + j])
+    return None
+
+
+class Guarded:
+    """n elements of `dtype` inside one larger byte allocation: GUARD_BYTES of guard pattern on each side, the array at
+    GUARD_BYTES + shift * itemsize (element-aligned only).  kind: "device" (torch cuda uint8), "numpy" (pageable host) or
+    "pinned" (ctx.host_alloc: pinned and device-mapped).  `values` is the initial content (default: SENTINEL)."""
+
+    def __init__(self, kind, n, dtype, shift=0, values=None, ctx=None, name=""):
+        self.kind, self.n, self.dtype, self.shift, self.name = kind, int(n), np.dtype(dtype), int(shift), name
+        isz = self.dtype.itemsize
+        self.start = GUARD_BYTES + self.shift * isz
+        self.end = self.start + self.n * isz
+        total = self.end + GUARD_BYTES
+        init = guard_pattern(total)
+        content = np.full(self.n, SENTINEL, np.int64).astype(self.dtype) if values is None else np.ascontiguousarray(values, self.dtype)
+        assert content.size == self.n, (name, content.size, self.n)
+        init[self.start:self.end] = content.view(np.uint8)
+        if kind == "device":
+            import torch
+            self.raw = torch.from_numpy(init).to(torch.device("cuda", 0))
+            self.ptr = self.raw.data_ptr() + self.start
+            self.array = None
+        else:
+            if kind == "pinned":
+                self.raw = ctx.host_alloc((total,), np.uint8)
+                self.raw[...] = init
+            else:
+                assert kind == "numpy", kind
+                self.raw = init
+            self.array = self.raw[self.start:self.end].view(self.dtype)          # what the binding is given
+            self.ptr = self.array.ctypes.data
+        assert self.ptr % isz == 0
+        self.initial = init.copy()
+
+    def raw_bytes(self):
+        return self.raw.cpu().numpy() if self.kind == "device" else np.array(self.raw, copy=True)
+
+    def values(self):
+        return self.raw_bytes()[self.start:self.end].view(self.dtype)
+
+    def check_guards(self, what=""):
+        v = guard_violation(self.raw_bytes(), self.start, self.end)
+        assert v is None, "guard band of %s (shift %d) %s: byte %d %s the array is 0x%02x %s" % (
+            self.name, self.shift, what, v[1], v[0], v[2], "(first corrupted byte)")
+
+    def check_unchanged(self, what=""):
+        """Bit for bit what it held before the call, guard bands included (inputs)."""
+        now = self.raw_bytes()
+        bad = np.flatnonzero(now != self.initial)
+        assert bad.size == 0, "input %s (shift %d) %s was written: first changed byte at %d from the array's start (0x%02x -> 0x%02x)" % (
+            self.name, self.shift, what, int(bad[0]) - self.start, int(self.initial[bad[0]]), int(now[bad[0]]))
+
+
+def shifts_for(pattern, names):
+    """Per-array element shifts: "aligned" (all 0), "odd" (all 1), "three" (all 3) or "mixed" (inputs and outputs vary
+    independently over SHIFTS)."""
+    if pattern in ("aligned", "odd", "three"):
+        return {k: {"aligned": 0, "odd": 1, "three": 3}[pattern] for k in names}
+    return {k: SHIFTS[(i * 2 + 1) % 3 if i % 2 else i % 3] for i, k in enumerate(names)}
+
+
+__all__ = ['ROOT', '_expected', '_workload', '_pinned', '_batch_of', '_device_call', '_same3', '_sort_topic', '_pinned_copy', '_grouped_expect', '_one_topic', '_wire_call',
+           'GUARD_BYTES', 'SENTINEL', 'SHIFTS', 'guard_pattern', 'guard_violation', 'Guarded', 'shifts_for']

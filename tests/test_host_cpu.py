@@ -578,3 +578,57 @@ def test_binding_refuses_result_buffers_the_library_cannot_fill():
                 (p, m, np.empty(k + 1, np.int64)), (list(p), m, t)):
         with pytest.raises(ValueError):
             _native._check_out3(bad, n, k)
+
+
+def test_guarded_host_array_reports_a_flipped_byte_on_either_side():
+    """The guard check of the buffer-contract tests (gpu_helpers.Guarded): a byte changed just before, just after, or far out in
+    either band is reported with its side and its offset from the array; the array's own bytes are not the guard's business."""
+    import numpy as np
+    from gpu_helpers import GUARD_BYTES, SENTINEL, Guarded
+    for dtype in (np.int32, np.int64, np.uint16):
+        for shift in (0, 1, 3):
+            g = Guarded("numpy", 10, dtype, shift, name="a")
+            assert g.array.ctypes.data % np.dtype(dtype).itemsize == 0 and (g.array == np.array(SENTINEL).astype(dtype)).all()
+            g.check_guards()
+            g.array[:] = 5                                      # writing the array itself is fine
+            g.check_guards()
+            nb = 10 * np.dtype(dtype).itemsize
+            for side, off in (("before", -1), ("before", -GUARD_BYTES), ("after", 0), ("after", GUARD_BYTES - 1), ("after", 3)):
+                j = g.start + off if side == "before" else g.end + off
+                old = g.raw[j]
+                g.raw[j] ^= 0x40
+                with pytest.raises(AssertionError) as e:
+                    g.check_guards()
+                assert "byte %d %s the array" % (off, side) in str(e.value), (str(e.value), side, off)
+                g.raw[j] = old
+            g.check_guards()
+            assert g.end - g.start == nb
+    inp = Guarded("numpy", 4, np.int64, 1, np.arange(4), name="in")
+    inp.check_unchanged()
+    inp.array[2] += 1
+    with pytest.raises(AssertionError, match="first changed byte at 16"):
+        inp.check_unchanged()
+
+
+def test_binding_refuses_grouped_and_lag_buffers_the_library_cannot_fill():
+    """out= of compute_lag / assign_batch_grouped / assign_batch_grouped_sparse: contiguous arrays of the right type and size
+    (None allowed where the library takes NULL), anything else refused before the library sees it."""
+    import numpy as np
+    m, n, k = 4, 12, 5
+    off, t, p, tot = np.empty(m + 1, np.int64), np.empty(n, np.int32), np.empty(n, np.int32), np.empty(k, np.int64)
+    assert _native._check_out_grouped((off, t, p, tot), m, n, k) == (off, t, p, tot)
+    assert _native._check_out_grouped((off, None, p, None), m, n, k)[1] is None
+    for bad in ((off[:-1], t, p, tot), (off, t.astype(np.int64), p, tot), (off, t, None, tot), (off, t, np.empty(2 * n, np.int32)[::2], tot),
+                (off, t, p, np.empty(k + 1, np.int64)), (None, t, p, tot), (list(off), t, p, tot)):
+        with pytest.raises(ValueError):
+            _native._check_out_grouped(bad, m, n, k)
+    ctx = _native.Context.__new__(_native.Context)               # (no device: the check comes before any library call)
+    ctx._lib, ctx._h = None, None
+    e = np.arange(n, dtype=np.int64)
+    for bad in (np.empty(n, np.int32), np.empty(n + 1, np.int64), np.empty(2 * n, np.int64)[::2]):
+        with pytest.raises(ValueError):
+            ctx.compute_lag(None, e, e, 0, out=bad)
+    for fn, extra in (("assign_batch_grouped", (None, e, e, 0)), ("assign_batch_grouped_sparse", (e, e, 0, None, None))):
+        with pytest.raises(ValueError):
+            getattr(ctx, fn)(np.array([0, n]), np.arange(n), *extra, np.array([0, k]), np.arange(k), m,
+                             out=(off, t, p, np.empty(k + 1, np.int64)))
