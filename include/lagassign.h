@@ -27,6 +27,8 @@
  *                           assignment on every GPU, one RCCL all-gather over xGMI
  *   la_pack_results_on, la_unpack_results_on, la_allgather_packed, la_wire_format_for
  *                           the same gather in 2 (or 4) bytes per assigned partition instead of 8
+ *   la_member_loads_device  nothing in the reference: the cross-topic sum, per member, of what its per-topic debug summary
+ *                           prints (Main.java:279-306) -- partitions and total lag every member ended up with
  *   la_hint_next_call       nothing in the reference's arithmetic: what the marshalling loop of readTopicPartitionLags
  *                           (Main.java:344-356) knows for free -- the largest end offset and partition id it walked past
  *   la_last_phase_times     nothing: measurement hook (radix-sort phase against the HBM roofline)
@@ -240,7 +242,9 @@ const char *la_last_error(const la_ctx *ctx);
  *                where there is no committed offset); every entry point restores the caller's current HIP device
  *   0.4.0 (400)  round 5: la_hint_next_call (the caller's bounds on lags and ids reach the host-buffer calls: one tile launch
  *                instead of two), la_last_launches, la_last_phase_times_sized
- *   0.5.0 (500)  round 6: la_wake (the device's queues woken while the host still fetches offsets); LA_FLAG values unchanged */
+ *   0.5.0 (500)  round 6: la_wake (the device's queues woken while the host still fetches offsets); LA_FLAG values unchanged
+ *                later, WITHOUT a bump: la_member_loads_device / la_member_loads_device_on (per-member roll-up of an assignment);
+ *                a shim detects them by symbol lookup (dlsym / getattr) instead of by version */
 #define LA_VERSION 500
 int la_version(void);
 
@@ -530,6 +534,34 @@ int la_group_by_member_device_on(la_ctx *ctx, int shard, int32_t n_topics, int64
                                  const int32_t *d_out_member_rank, int32_t n_members,
                                  int64_t *d_member_off, int32_t *d_grouped_topic, int32_t *d_grouped_partition,
                                  void *stream);
+
+/* Per-member roll-up of an assignment (nothing in the reference computes it; it is the cross-topic sum of what the
+ * debug summary prints per topic, Main.java:283-291).  With M = n_members:
+ *   d_member_partitions[r] = #{ i in [0,N) : d_out_member_rank[i] == r }                       r in [0, M)
+ *   d_unassigned[0]        = #{ i in [0,N) : d_out_member_rank[i] == -1 }   (topics without consumers, Main.java:211-213)
+ *   d_member_lag[r]        = sum of d_out_total_lag[k] over k in [0,K) with d_cons_rank[k] == r,
+ *                            Java long arithmetic (64-bit two's-complement wrap)
+ * Either half may be left out: d_out_member_rank == NULL (then d_member_partitions and d_unassigned must be NULL),
+ * or d_cons_rank == NULL (then d_out_total_lag and d_member_lag must be NULL); both NULL is LA_EINVAL.  (The input pointer
+ * decides, also when its size is 0: an empty half that is present still has its outputs zeroed.)
+ * d_unassigned may be NULL.  Outputs are OVERWRITTEN (a member that received nothing reads 0).
+ * Enqueues on `stream` and returns -- behind la_assign_batch_device on the same stream it reads that call's results, no sync in
+ * between; a rank outside [-1, M) in d_out_member_rank or outside [0, M) in d_cons_rank is not counted, never written
+ * through, and reported by la_sync as LA_EINVAL (what the other entries added to the outputs is then unspecified).
+ * N == 0 / K == 0 are valid.  At most one kernel launch (la_last_launches) behind the memsets that zero the outputs; the call
+ * needs no scratch, so the results kept for la_group_last_by_member stay valid.
+ * Buffer contract as everywhere in this header (element alignment only, no write outside [0,M) / [0,1), inputs
+ * never written). */
+int la_member_loads_device(la_ctx *ctx, int64_t n_partitions, const int32_t *d_out_member_rank,
+                           int64_t n_consumers, const int32_t *d_cons_rank, const int64_t *d_out_total_lag,
+                           int32_t n_members, int64_t *d_member_partitions, int64_t *d_member_lag,
+                           int64_t *d_unassigned, void *stream);
+/* The same on shard `shard` (buffers and stream on that shard's device; la_sync_on reports a bad rank).  Shards hold disjoint
+ * topic ranges, so the element-wise (wrapping) sum of their roll-ups is the roll-up of the whole batch. */
+int la_member_loads_device_on(la_ctx *ctx, int shard, int64_t n_partitions, const int32_t *d_out_member_rank,
+                              int64_t n_consumers, const int32_t *d_cons_rank, const int64_t *d_out_total_lag,
+                              int32_t n_members, int64_t *d_member_partitions, int64_t *d_member_lag,
+                              int64_t *d_unassigned, void *stream);
 
 #ifdef __cplusplus
 }

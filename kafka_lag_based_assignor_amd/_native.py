@@ -30,6 +30,9 @@ LA_FEATURE_ATOMIC_RANK = 1
 LA_PIPELINE_ONE_COPY, LA_PIPELINE_LANES, LA_PIPELINE_STREAMS, LA_PIPELINE_ZERO_COPY, LA_PIPELINE_MAPPED = 0, 1, 2, 3, 4
 LA_CREATE_LANES_MASK, LA_CREATE_SPLIT_ALWAYS = 0xF, 0x10
 LA_HINT_BOUNDS = 1
+# la_member_loads_device: up to this many members the bins of the roll-up live in LDS, beyond it every element is one global
+# atomic add (kLoadsLdsMaxMembers of csrc/la_kernels.h; results are the same, tests run both sides)
+LOADS_LDS_MAX_MEMBERS = 4095
 
 EXPORTED_SYMBOLS = (
     "la_create", "la_destroy", "la_last_error", "la_version", "la_compute_lag",
@@ -42,6 +45,7 @@ EXPORTED_SYMBOLS = (
     "la_wire_format_for", "la_pack_results_on", "la_unpack_results_on", "la_allgather_packed",
     "la_assign_batch_sparse", "la_assign_batch_grouped_sparse",
     "la_hint_next_call", "la_last_launches", "la_last_phase_times_sized", "la_wake",
+    "la_member_loads_device", "la_member_loads_device_on",
 )
 
 _i64p = ctypes.POINTER(ctypes.c_int64)
@@ -214,6 +218,14 @@ def load() -> ctypes.CDLL:
     L.la_wake.argtypes = [ctypes.c_void_p]
     L.la_last_phase_times_sized.restype = ctypes.c_int
     L.la_last_phase_times_sized.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
+    # added without an ABI bump: found by symbol lookup (an older library simply lacks them)
+    if hasattr(L, "la_member_loads_device_on"):
+        _loads = [ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
+                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        L.la_member_loads_device.restype = ctypes.c_int
+        L.la_member_loads_device.argtypes = [ctypes.c_void_p] + _loads
+        L.la_member_loads_device_on.restype = ctypes.c_int
+        L.la_member_loads_device_on.argtypes = [ctypes.c_void_p, ctypes.c_int] + _loads
     _lib = L
     return L
 
@@ -588,6 +600,23 @@ class Context:
                                                            d_out_partition, d_out_member_rank, n_members,
                                                            d_member_off, d_grouped_topic, d_grouped_partition,
                                                            ctypes.c_void_p(stream)))
+
+    def member_loads_device(self, n_partitions: int, d_out_member_rank: int, n_consumers: int, d_cons_rank: int,
+                            d_out_total_lag: int, n_members: int, d_member_partitions: int, d_member_lag: int,
+                            d_unassigned: int = 0, stream: int = 0, shard: int = 0) -> None:
+        """la_member_loads_device_on: per-member partition counts (int64[M]), total lags (int64[M], Java long sums) and the
+        number of unassigned partitions (int64[1]) of an assignment, device addresses as ints (0 = NULL: either half --
+        d_out_member_rank with its two outputs, d_cons_rank / d_out_total_lag with d_member_lag -- may be left out).
+        Enqueued on `stream`; sync() reports a rank out of range.  sharding.member_loads_numpy is the same on the host."""
+        fn = getattr(self._lib, "la_member_loads_device_on", None)
+        if fn is None:
+            raise LagAssignError(LA_EINVAL, "this liblagassign.so has no la_member_loads_device_on")
+
+        def p(x):
+            return ctypes.c_void_p(int(x)) if x else None
+
+        self._check(fn(self._h, shard, n_partitions, p(d_out_member_rank), n_consumers, p(d_cons_rank), p(d_out_total_lag),
+                       n_members, p(d_member_partitions), p(d_member_lag), p(d_unassigned), ctypes.c_void_p(stream)))
 
     # -- device-resident entry point ------------------------------------------------
     def assign_batch_device(self, batch: DeviceBatch, stream: int = 0, shard: int = 0) -> None:

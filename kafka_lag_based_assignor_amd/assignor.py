@@ -88,6 +88,19 @@ class LagBasedPartitionAssignor:
         bounds: la_hint_next_call), `max_lag` / `max_partition_id`, the library's `pipeline` and kernel `launches`."""
         return dict(_host().LagBasedPartitionAssignor.last_native_call())
 
+    @staticmethod
+    def last_member_loads() -> Dict[str, Tuple[int, int]]:
+        """Per-member roll-up of the last assign() / assign_lags() on this thread: memberId -> (partitions, total_lag) over
+        all its topics, total_lag in Java long arithmetic (the cross-topic sum of what the reference's debug summary prints per
+        topic, Main.java:283-291).  Every member of the subscription appears, also one that got nothing (Main.java:171-174)."""
+        return {m: (int(v[0]), int(v[1])) for m, v in _host().LagBasedPartitionAssignor.last_member_loads().items()}
+
+    @staticmethod
+    def last_unassigned() -> int:
+        """Partitions the last assign() / assign_lags() on this thread left unassigned (topics without consumers,
+        Main.java:211-213)."""
+        return int(_host().LagBasedPartitionAssignor.last_unassigned())
+
     def set_warn(self, fn: Callable[[str], None]) -> None:
         self._impl.set_warn(fn)
 

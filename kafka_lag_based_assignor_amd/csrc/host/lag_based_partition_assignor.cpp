@@ -36,6 +36,7 @@ la_ctx* shared_ctx_locked() {
 // handling, unverified against a JVM).
 thread_local bool t_last_order_exact = true;
 thread_local LagBasedPartitionAssignor::NativeCallStats t_last_native;
+thread_local LagBasedPartitionAssignor::MemberLoads t_last_loads;
 
 void check(la_ctx* ctx, int rc) {
     if (rc == LA_OK) return;
@@ -140,6 +141,7 @@ struct Flat {
 // tile-sized topics instead of two; a caller that saw a negative value promises nothing.
 void hint_bounds(la_ctx* ctx, const Flat& f) {
     t_last_native = LagBasedPartitionAssignor::NativeCallStats{};
+    t_last_loads = LagBasedPartitionAssignor::MemberLoads{};     // (a call that fails leaves no roll-up of an earlier one behind)
     if (f.any_negative || f.pid.empty()) return;
     la_call_hints h{};
     h.struct_size = (int32_t)sizeof h;
@@ -214,6 +216,16 @@ Assignment run_native(const Plan& plan, const std::vector<const TopicData*>& dat
             t_last_native.launches = la_last_launches(ctx);
         }
     }
+    // the call's roll-up per member (lastMemberLoads): counts from the lists' offsets, lags as wrapping sums of the K totals
+    {
+        LagBasedPartitionAssignor::MemberLoads loads;
+        std::vector<uint64_t> lag_of((size_t)n_members, 0);
+        for (size_t c = 0; c < k; ++c) lag_of[(size_t)f.cons_rank[c]] += (uint64_t)out_total[c];
+        for (int32_t r = 0; r < n_members; ++r)
+            loads.per_member[plan.members[plan.member_of_rank[r]]] = {member_off[r + 1] - member_off[r], (int64_t)lag_of[(size_t)r]};
+        loads.unassigned = member_off[0];
+        t_last_loads = std::move(loads);
+    }
     // partition id -> the element's own topic string (normally the map key), per topic
     std::vector<std::unordered_map<int32_t, const std::string*>> topic_of(plan.topics.size());
     for (size_t t = 0; t < plan.topics.size(); ++t)
@@ -284,6 +296,7 @@ std::vector<std::string> consumersPerTopicOrder(const GroupSubscription& subscri
 
 bool LagBasedPartitionAssignor::lastStaticOrderExact() { return t_last_order_exact; }
 LagBasedPartitionAssignor::NativeCallStats LagBasedPartitionAssignor::lastNativeCall() { return t_last_native; }
+LagBasedPartitionAssignor::MemberLoads LagBasedPartitionAssignor::lastMemberLoads() { return t_last_loads; }
 
 LagBasedPartitionAssignor::LagBasedPartitionAssignor() = default;
 LagBasedPartitionAssignor::~LagBasedPartitionAssignor() = default;

@@ -122,6 +122,17 @@ class LagBasedPartitionAssignor {
     };
     static NativeCallStats lastNativeCall();
 
+    // Per-member roll-up of the last assign (either form) on the calling thread: memberId -> (partitions, total lag) over all
+    // its topics -- the cross-topic sum of what the debug summary prints per topic (Main.java:283-291), total lag in Java long
+    // arithmetic.  Every member of the subscription appears, also one that got nothing (Main.java:171-174).  `unassigned` =
+    // partitions of topics without consumers (Main.java:211-213).  Host arithmetic over the K totals of the call; the device
+    // form for resident results is la_member_loads_device.
+    struct MemberLoads {
+        std::map<std::string, std::pair<int64_t, int64_t>> per_member;
+        int64_t unassigned = 0;
+    };
+    static MemberLoads lastMemberLoads();
+
     // Hook for log lines the reference emits through slf4j (warn on missing metadata, :359).
     std::function<void(const std::string&)> warn = [](const std::string&) {};
 

@@ -115,6 +115,8 @@ PYBIND11_MODULE(_host, m) {
             d["launches"] = st.launches;
             return d;
         })
+        .def_static("last_member_loads", [] { return LagBasedPartitionAssignor::lastMemberLoads().per_member; })
+        .def_static("last_unassigned", [] { return LagBasedPartitionAssignor::lastMemberLoads().unassigned; })
         .def("set_warn", [](LagBasedPartitionAssignor& self, std::function<void(const std::string&)> f) { self.warn = std::move(f); })
         .def("set_debug", [](LagBasedPartitionAssignor& self, std::function<void(const std::string&)> f) { self.debug = std::move(f); })
         .def("assign",

@@ -728,6 +728,8 @@ int status_error(la_ctx* ctx, uint32_t st) {
         return fail(ctx, LA_EINVAL, "none_index must hold ascending positions inside the batch");
     if (st & la::kStatusWire)
         return fail(ctx, LA_EINVAL, "a partition id or member rank does not fit the wire format given to la_pack_results_on");
+    if (st & la::kStatusLoads)
+        return fail(ctx, LA_EINVAL, "la_member_loads_device: a member rank outside [-1, n_members) or a consumer rank outside [0, n_members)");
     return fail(ctx, LA_ESHAPE, "a topic exceeds the batch's shape hint");
 }
 
@@ -2338,6 +2340,45 @@ LA_API int la_group_by_member_device_on(la_ctx* ctx, int shard, int32_t n_topics
         return LA_OK;
     } catch (...) {
         return fail(ctx, LA_ENOMEM, "exception in la_group_by_member_device");
+    }
+}
+
+// Per-member roll-up of an assignment (la_loads.hip).  Owns no scratch: the bins are LDS and the caller's outputs, so the
+// results kept for la_group_last_by_member stay as they are.
+LA_API int la_member_loads_device(la_ctx* ctx, int64_t n_partitions, const int32_t* d_out_member_rank, int64_t n_consumers,
+                                  const int32_t* d_cons_rank, const int64_t* d_out_total_lag, int32_t n_members,
+                                  int64_t* d_member_partitions, int64_t* d_member_lag, int64_t* d_unassigned, void* stream) {
+    return la_member_loads_device_on(ctx, 0, n_partitions, d_out_member_rank, n_consumers, d_cons_rank, d_out_total_lag,
+                                     n_members, d_member_partitions, d_member_lag, d_unassigned, stream);
+}
+
+LA_API int la_member_loads_device_on(la_ctx* ctx, int shard, int64_t n_partitions, const int32_t* d_out_member_rank,
+                                     int64_t n_consumers, const int32_t* d_cons_rank, const int64_t* d_out_total_lag,
+                                     int32_t n_members, int64_t* d_member_partitions, int64_t* d_member_lag,
+                                     int64_t* d_unassigned, void* stream) {
+    DeviceGuard restore_device;
+    LaunchSpan span(ctx);
+    if (!ctx) return LA_EINVAL;
+    try {
+        if (shard < 0 || shard >= (int)ctx->shards.size()) return fail(ctx, LA_EINVAL, "shard %d of %d", shard, (int)ctx->shards.size());
+        if (n_partitions < 0 || n_consumers < 0 || n_members < 0) return fail(ctx, LA_EINVAL, "negative size");
+        if (!d_out_member_rank && !d_cons_rank) return fail(ctx, LA_EINVAL, "d_out_member_rank and d_cons_rank are both NULL");
+        if (!d_out_member_rank && (d_member_partitions || d_unassigned))
+            return fail(ctx, LA_EINVAL, "d_member_partitions / d_unassigned given without d_out_member_rank");
+        if (!d_cons_rank && (d_out_total_lag || d_member_lag))
+            return fail(ctx, LA_EINVAL, "d_out_total_lag / d_member_lag given without d_cons_rank");
+        if (d_out_member_rank && !d_member_partitions && n_members > 0) return fail(ctx, LA_EINVAL, "d_member_partitions is NULL");
+        if (d_cons_rank && ((!d_member_lag && n_members > 0) || (!d_out_total_lag && n_consumers > 0)))
+            return fail(ctx, LA_EINVAL, "d_member_lag or d_out_total_lag is NULL");
+        Shard& sh = ctx->shards[(size_t)shard];
+        LA_HIP(ctx, hipSetDevice(sh.device));
+        hipError_t e = la::member_loads_launch(n_partitions, d_out_member_rank, n_consumers, d_cons_rank, d_out_total_lag,
+                                               n_members, d_member_partitions, d_member_lag, d_unassigned,
+                                               sh.lanes[0].d_status, (hipStream_t)stream);
+        if (e != hipSuccess) return fail(ctx, LA_EHIP, "member_loads: %s", hipGetErrorString(e));
+        return LA_OK;
+    } catch (...) {
+        return fail(ctx, LA_ENOMEM, "exception in la_member_loads_device");
     }
 }
 

@@ -51,6 +51,8 @@ constexpr uint32_t kStatusSparse = 32u;    // la_assign_batch_sparse: none_index
 
 constexpr uint32_t kStatusBounds = 64u;    // LA_FLAG_BOUNDS: a lag or a partition id lies outside the bounds the caller guaranteed
 
+constexpr uint32_t kStatusLoads = 128u;    // la_member_loads_device: a member rank outside [-1, M) / a consumer rank outside [0, M)
+
 constexpr int32_t kTileNoDefer = 8;       // TileArgs::flags: the bounds prove that every tile packs -- no deferred list, no wide
                                           // launch; a tile that does not pack after all raises kStatusBounds
 constexpr int32_t kTileWireOut = 16;      // TileArgs::flags: out_wire instead of out_pid / out_rank (needs kTileNoDefer)
@@ -271,5 +273,15 @@ hipError_t wire_pack_launch(int64_t n, const int32_t* pid, const int32_t* rank, 
                             uint32_t* status, hipStream_t stream);
 hipError_t wire_unpack_launch(int64_t n, const void* in, int elem_bytes, int id_bits, int32_t* pid, int32_t* rank,
                               hipStream_t stream);
+
+// ---- per-member roll-up of an assignment (la_loads.hip) -----------------------------------------------------------------
+// Up to this many members the bins live in LDS (per-workgroup tables, one global atomic per non-zero bin and workgroup); beyond
+// it every element is one 64-bit global atomic add.  4096 sums of 8 bytes = the 32 KiB of LDS a workgroup takes.
+constexpr int32_t kLoadsLdsMaxMembers = 4095;
+// Zeroes the outputs on `stream`, then ONE launch over both inputs.  member_rank == null: no counts (member_partitions and
+// unassigned are not touched); cons_rank == null: no sums.  A rank out of range is skipped and raises kStatusLoads.
+hipError_t member_loads_launch(int64_t n, const int32_t* member_rank, int64_t k, const int32_t* cons_rank,
+                               const int64_t* total_lag, int32_t n_members, int64_t* member_partitions, int64_t* member_lag,
+                               int64_t* unassigned, uint32_t* status, hipStream_t stream);
 
 }  // namespace la

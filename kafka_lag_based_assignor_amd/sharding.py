@@ -152,3 +152,47 @@ def gather_results(local_pid, local_rank, counts: List[int], group=None):
         return strip_padding(recv, counts, cap)
 
     return one(local_pid), one(local_rank)
+
+
+def member_loads_numpy(out_member_rank, cons_rank, out_total_lag, n_members: int):
+    """la_member_loads_device restated on the host -> (partitions int64[M], lag int64[M], unassigned int):
+    partitions[r] = entries of out_member_rank equal to r, unassigned = its entries equal to -1 (topics without consumers,
+    Main.java:211-213), lag[r] = sum of out_total_lag[k] over cons_rank[k] == r in Java long arithmetic (wraps).  A rank
+    outside [-1, M) / [0, M) raises ValueError.  The yardstick of the GPU tests, and what a gloo-only launcher uses."""
+    m = int(n_members)
+    rank = np.asarray(out_member_rank, dtype=np.int64).ravel()
+    cr = np.asarray(cons_rank, dtype=np.int64).ravel()
+    tot = np.ascontiguousarray(np.asarray(out_total_lag, dtype=np.int64).ravel())
+    if m < 0 or cr.size != tot.size:
+        raise ValueError("n_members < 0, or cons_rank and out_total_lag differ in length")
+    if (rank.size and (rank.min() < -1 or rank.max() >= m)) or (cr.size and (cr.min() < 0 or cr.max() >= m)):
+        raise ValueError("a member rank lies outside [-1, n_members) or a consumer rank outside [0, n_members)")
+    counts = np.bincount(rank + 1, minlength=m + 1).astype(np.int64)
+    lag = np.zeros(m, dtype=np.uint64)
+    np.add.at(lag, cr, tot.view(np.uint64))          # unsigned adds wrap silently: the bits of Java's long sum
+    return counts[1:].copy(), lag.view(np.int64), int(counts[0])
+
+
+def reduce_member_loads(partitions, lag, unassigned, group=None):
+    """Partial roll-ups of the ranks' shards -> the group-wide roll-up on every rank: ONE all_reduce(SUM) over a single int64
+    tensor of 2 * M + 1 entries (shards are disjoint topic ranges, so the sum of the partial roll-ups IS the roll-up; int64
+    sums wrap like Java's).  numpy arrays / host tensors travel as a host tensor (gloo), device tensors stay on their device
+    (nccl = RCCL).  Returns (partitions, lag, unassigned) in the kind that came in (numpy in, numpy out)."""
+    import torch
+    import torch.distributed as dist
+
+    as_numpy = not isinstance(partitions, torch.Tensor)
+    p = torch.from_numpy(np.ascontiguousarray(partitions, dtype=np.int64)) if as_numpy else partitions
+    g = torch.from_numpy(np.ascontiguousarray(lag, dtype=np.int64)) if not isinstance(lag, torch.Tensor) else lag
+    m = p.numel()
+    if g.numel() != m:
+        raise ValueError("partitions and lag differ in length")
+    buf = torch.empty(2 * m + 1, dtype=torch.int64, device=p.device)
+    buf[:m] = p
+    buf[m:2 * m] = g.to(p.device)
+    buf[2 * m] = unassigned if isinstance(unassigned, torch.Tensor) else int(unassigned)
+    dist.all_reduce(buf, op=dist.ReduceOp.SUM, group=group)
+    if as_numpy:
+        out = buf.numpy()
+        return out[:m].copy(), out[m:2 * m].copy(), int(out[2 * m])
+    return buf[:m], buf[m:2 * m], buf[2 * m]
