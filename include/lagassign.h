@@ -29,6 +29,8 @@
  *                           the same gather in 2 (or 4) bytes per assigned partition instead of 8
  *   la_member_loads_device  nothing in the reference: the cross-topic sum, per member, of what its per-topic debug summary
  *                           prints (Main.java:279-306) -- partitions and total lag every member ended up with
+ *   la_assignment_moves_device  nothing in the reference (its assignor is eager: every rebalance deals all partitions out again):
+ *                           how many partitions changed owner between two rebalances, and who gained or lost them
  *   la_hint_next_call       nothing in the reference's arithmetic: what the marshalling loop of readTopicPartitionLags
  *                           (Main.java:344-356) knows for free -- the largest end offset and partition id it walked past
  *   la_last_phase_times     nothing: measurement hook (radix-sort phase against the HBM roofline)
@@ -244,6 +246,7 @@ const char *la_last_error(const la_ctx *ctx);
  *                instead of two), la_last_launches, la_last_phase_times_sized
  *   0.5.0 (500)  round 6: la_wake (the device's queues woken while the host still fetches offsets); LA_FLAG values unchanged
  *                later, WITHOUT a bump: la_member_loads_device / la_member_loads_device_on (per-member roll-up of an assignment);
+ *                la_assignment_moves_device / la_assignment_moves_device_on (who moved between two rebalances);
  *                a shim detects them by symbol lookup (dlsym / getattr) instead of by version */
 #define LA_VERSION 500
 int la_version(void);
@@ -562,6 +565,55 @@ int la_member_loads_device_on(la_ctx *ctx, int shard, int64_t n_partitions, cons
                               int64_t n_consumers, const int32_t *d_cons_rank, const int64_t *d_out_total_lag,
                               int32_t n_members, int64_t *d_member_partitions, int64_t *d_member_lag,
                               int64_t *d_unassigned, void *stream);
+
+/* Who moved between two rebalances (nothing in the reference computes it).  Both assignments are results of an assign call
+ * over ONE layout (the same d_part_off; topics whose partition count changed are out of scope) -- each in its own assignment
+ * order, so the previous owner of an entry is found by a join on (topic, partition id), not by position.  With M = n_members,
+ * for entry i of topic t of the current assignment:
+ *   p = d_prev_member_rank[j] of the entry j of topic t of the previous assignment with d_prev_partition[j] == d_out_partition[i]
+ *   q = p < 0 ? -1 : (d_prev_rank_map ? d_prev_rank_map[p] : p)          that owner in TODAY's ranks (-1: none, or it left)
+ *   c = d_out_member_rank[i]
+ *   d_prev_owner[i] = q;   the entry has MOVED iff q != c  (-1 -> -1 is no move: a topic without consumers both times, or an
+ *                          owner that left with nobody taking over)
+ *   a moved entry adds 1 to d_topic_moved[t] and d_moved[0], to d_member_gained[c] when c >= 0, to d_member_lost[q] when q >= 0
+ * Outputs are OVERWRITTEN; each may be NULL, all NULL is LA_EINVAL.  Enqueues on `stream` and returns -- behind
+ * la_assign_batch_device on the same stream it reads that call's results, no sync in between.  N == 0 and T == 0 are valid
+ * (the outputs are zeroed).
+ * Input contract: inside one topic the ids of each assignment are distinct and the two id sets are equal; ids are any int32.
+ * n_members < 2^30.  Reported by la_sync as LA_EINVAL: a duplicate id inside a topic (either assignment), a current id without
+ * a previous one, a previous rank outside [-1, M_prev), a mapped or current rank outside [-1, M).  Such an entry is never
+ * stored through; what the rest of the call wrote is then unspecified, but inside the arrays.
+ * Shape: max_partitions_per_topic is the hint of la_device_batch.  Within 4096 partitions (one workgroup joins a topic in
+ * LDS) a topic over the hint is reported by la_sync as LA_ESHAPE and nothing is written for it (neither its d_prev_owner
+ * entries nor its d_topic_moved; the other topics are done as usual); with a larger hint the library finds the larger topics
+ * from h_part_off, which is then required (LA_EINVAL without it).
+ * At most one kernel launch with a hint within that limit, three otherwise (la_last_launches; memsets do not count).  The table
+ * of the larger topics is a buffer of the shard's own (LA_ENOMEM when it cannot be had), so the results kept for
+ * la_group_last_by_member stay valid.  Buffer contract as everywhere in this header. */
+typedef struct la_moves_args {
+    int32_t struct_size;              /* sizeof(la_moves_args) of the caller's header */
+    int32_t n_topics;                 /* T */
+    int64_t n_partitions;             /* N = part_off[T] */
+    int64_t max_partitions_per_topic; /* shape hint, as in la_device_batch */
+    const int64_t *d_part_off;        /* [T+1], the layout BOTH assignments share */
+    const int64_t *h_part_off;        /* host copy; required when the hint exceeds the one-workgroup limit */
+    const int32_t *d_out_partition;   /* [N] current assignment (results of an assign call) */
+    const int32_t *d_out_member_rank; /* [N] */
+    const int32_t *d_prev_partition;  /* [N] previous assignment, same layout */
+    const int32_t *d_prev_member_rank;/* [N] */
+    int32_t n_members;                /* M: ranks of the CURRENT membership */
+    int32_t n_prev_members;           /* M_prev; read only when d_prev_rank_map != NULL */
+    const int32_t *d_prev_rank_map;   /* [M_prev] previous rank -> current rank, -1 = member left; NULL = identity (M_prev = M) */
+    int32_t *d_prev_owner;            /* [N] or NULL */
+    int64_t *d_topic_moved;           /* [T] or NULL */
+    int64_t *d_member_gained;         /* [M] or NULL */
+    int64_t *d_member_lost;           /* [M] or NULL */
+    int64_t *d_moved;                 /* [1] or NULL */
+} la_moves_args;
+int la_assignment_moves_device(la_ctx *ctx, const la_moves_args *args, void *stream);
+/* The same on shard `shard` (buffers and stream on that shard's device; la_sync_on reports the errors).  Shards hold disjoint
+ * topic ranges, so the element-wise sum of their gained / lost / moved is that of the whole batch. */
+int la_assignment_moves_device_on(la_ctx *ctx, int shard, const la_moves_args *args, void *stream);
 
 #ifdef __cplusplus
 }

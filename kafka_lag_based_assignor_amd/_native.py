@@ -33,6 +33,11 @@ LA_HINT_BOUNDS = 1
 # la_member_loads_device: up to this many members the bins of the roll-up live in LDS, beyond it every element is one global
 # atomic add (kLoadsLdsMaxMembers of csrc/la_kernels.h; results are the same, tests run both sides)
 LOADS_LDS_MAX_MEMBERS = 4095
+# la_assignment_moves_device: topics up to MOVES_LDS_MAX_PARTITIONS are joined in one workgroup's LDS (larger ones through a table
+# in device memory, found from h_part_off); up to MOVES_LDS_MAX_MEMBERS the gained / lost counts are LDS bins (kMovesLdsMaxPartitions /
+# kMovesLdsMaxMembers of csrc/la_kernels.h; results are the same, tests run both sides)
+MOVES_LDS_MAX_PARTITIONS = 4096
+MOVES_LDS_MAX_MEMBERS = 4096
 
 EXPORTED_SYMBOLS = (
     "la_create", "la_destroy", "la_last_error", "la_version", "la_compute_lag",
@@ -46,6 +51,7 @@ EXPORTED_SYMBOLS = (
     "la_assign_batch_sparse", "la_assign_batch_grouped_sparse",
     "la_hint_next_call", "la_last_launches", "la_last_phase_times_sized", "la_wake",
     "la_member_loads_device", "la_member_loads_device_on",
+    "la_assignment_moves_device", "la_assignment_moves_device_on",
 )
 
 _i64p = ctypes.POINTER(ctypes.c_int64)
@@ -92,6 +98,21 @@ class WireFormat(ctypes.Structure):
     @property
     def dtype(self):
         return {2: np.uint16, 4: np.uint32, 8: np.uint64}[int(self.elem_bytes)]
+
+
+class MovesArgs(ctypes.Structure):
+    """struct la_moves_args (device addresses as ints, None / 0 = NULL; struct_size is filled in by assignment_moves_device)"""
+    _fields_ = [
+        ("struct_size", ctypes.c_int32), ("n_topics", ctypes.c_int32),
+        ("n_partitions", ctypes.c_int64), ("max_partitions_per_topic", ctypes.c_int64),
+        ("d_part_off", ctypes.c_void_p), ("h_part_off", _i64p),
+        ("d_out_partition", ctypes.c_void_p), ("d_out_member_rank", ctypes.c_void_p),
+        ("d_prev_partition", ctypes.c_void_p), ("d_prev_member_rank", ctypes.c_void_p),
+        ("n_members", ctypes.c_int32), ("n_prev_members", ctypes.c_int32),
+        ("d_prev_rank_map", ctypes.c_void_p),
+        ("d_prev_owner", ctypes.c_void_p), ("d_topic_moved", ctypes.c_void_p),
+        ("d_member_gained", ctypes.c_void_p), ("d_member_lost", ctypes.c_void_p), ("d_moved", ctypes.c_void_p),
+    ]
 
 
 class PhaseTimes(ctypes.Structure):
@@ -226,6 +247,11 @@ def load() -> ctypes.CDLL:
         L.la_member_loads_device.argtypes = [ctypes.c_void_p] + _loads
         L.la_member_loads_device_on.restype = ctypes.c_int
         L.la_member_loads_device_on.argtypes = [ctypes.c_void_p, ctypes.c_int] + _loads
+    if hasattr(L, "la_assignment_moves_device_on"):
+        L.la_assignment_moves_device.restype = ctypes.c_int
+        L.la_assignment_moves_device.argtypes = [ctypes.c_void_p, ctypes.POINTER(MovesArgs), ctypes.c_void_p]
+        L.la_assignment_moves_device_on.restype = ctypes.c_int
+        L.la_assignment_moves_device_on.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(MovesArgs), ctypes.c_void_p]
     _lib = L
     return L
 
@@ -617,6 +643,19 @@ class Context:
 
         self._check(fn(self._h, shard, n_partitions, p(d_out_member_rank), n_consumers, p(d_cons_rank), p(d_out_total_lag),
                        n_members, p(d_member_partitions), p(d_member_lag), p(d_unassigned), ctypes.c_void_p(stream)))
+
+    def assignment_moves_device(self, args: MovesArgs, stream: int = 0, shard: int = 0) -> None:
+        """la_assignment_moves_device_on: who moved between the previous and the current assignment of one layout -- the previous
+        owner of every entry in today's ranks (int32[N]), moved entries per topic (int64[T]), gained / lost per member
+        (int64[M]) and the moved total (int64[1]); each output may be left out.  Enqueued on `stream`; sync() reports duplicate or
+        missing ids, ranks out of range (LA_EINVAL) and topics over a hint within MOVES_LDS_MAX_PARTITIONS (LA_ESHAPE).
+        sharding.assignment_moves_numpy is the same on the host."""
+        fn = getattr(self._lib, "la_assignment_moves_device_on", None)
+        if fn is None:
+            raise LagAssignError(LA_EINVAL, "this liblagassign.so has no la_assignment_moves_device_on")
+        if not args.struct_size:
+            args.struct_size = ctypes.sizeof(MovesArgs)
+        self._check(fn(self._h, shard, ctypes.byref(args), ctypes.c_void_p(stream)))
 
     # -- device-resident entry point ------------------------------------------------
     def assign_batch_device(self, batch: DeviceBatch, stream: int = 0, shard: int = 0) -> None:

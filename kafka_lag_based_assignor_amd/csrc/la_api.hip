@@ -108,6 +108,7 @@ struct Shard {
     // through these two staging buffers (device, pinned host) instead of eight copies of caller arrays
     DevBuf small_d, small_g;
     HostBuf small_h, small_gh;
+    la::MovesScratch moves;              // la_assignment_moves_device: the global form's table and topic list
     HostBuf zc_h;                        // zero-copy small calls: coherent, device-mapped staging the kernels read and write in place
     // pinned caller arrays (la_host_alloc): one host thread, three streams -- every H2D of the call in order on copy_in,
     // the kernels on lane 0's stream, every D2H on copy_out, chained per chunk by events (run_shard_async)
@@ -730,6 +731,8 @@ int status_error(la_ctx* ctx, uint32_t st) {
         return fail(ctx, LA_EINVAL, "a partition id or member rank does not fit the wire format given to la_pack_results_on");
     if (st & la::kStatusLoads)
         return fail(ctx, LA_EINVAL, "la_member_loads_device: a member rank outside [-1, n_members) or a consumer rank outside [0, n_members)");
+    if (st & la::kStatusMoves)
+        return fail(ctx, LA_EINVAL, "la_assignment_moves_device: a duplicate partition id inside a topic, a current id without a previous one, or a rank out of range");
     return fail(ctx, LA_ESHAPE, "a topic exceeds the batch's shape hint");
 }
 
@@ -2009,6 +2012,7 @@ LA_API void la_destroy(la_ctx* ctx) {
             release(*b);
         for (HostBuf* h : {&sh.g_off, &sh.g_topic, &sh.g_part, &sh.small_h, &sh.small_gh, &sh.zc_h})
             if (h->p) (void)hipHostFree(h->p);
+        la::moves_scratch_release(sh.moves);
         if (sh.ready) (void)hipEventDestroy(sh.ready);
         for (hipEvent_t e : sh.chunk_ev) (void)hipEventDestroy(e);
         for (hipStream_t st : sh.copy_in)
@@ -2379,6 +2383,67 @@ LA_API int la_member_loads_device_on(la_ctx* ctx, int shard, int64_t n_partition
         return LA_OK;
     } catch (...) {
         return fail(ctx, LA_ENOMEM, "exception in la_member_loads_device");
+    }
+}
+
+// Who moved between two assignments (la_moves.hip).  The global form's table is the shard's own buffer, not the assign scratch:
+// the results kept for la_group_last_by_member stay as they are.
+LA_API int la_assignment_moves_device(la_ctx* ctx, const la_moves_args* args, void* stream) {
+    return la_assignment_moves_device_on(ctx, 0, args, stream);
+}
+
+LA_API int la_assignment_moves_device_on(la_ctx* ctx, int shard, const la_moves_args* args, void* stream) {
+    DeviceGuard restore_device;
+    LaunchSpan span(ctx);
+    if (!ctx) return LA_EINVAL;
+    try {
+        if (shard < 0 || shard >= (int)ctx->shards.size()) return fail(ctx, LA_EINVAL, "shard %d of %d", shard, (int)ctx->shards.size());
+        if (!args) return fail(ctx, LA_EINVAL, "args is NULL");
+        if (args->struct_size < (int32_t)sizeof(la_moves_args)) return fail(ctx, LA_EINVAL, "la_moves_args.struct_size is %d, this library's is %d", (int)args->struct_size, (int)sizeof(la_moves_args));
+        const la_moves_args& g = *args;
+        if (g.n_topics < 0 || g.n_partitions < 0 || g.n_members < 0) return fail(ctx, LA_EINVAL, "negative size");
+        if (g.n_members > la::kMovesMaxMembers) return fail(ctx, LA_EINVAL, "n_members must be below 2^30");
+        if (g.d_prev_rank_map && g.n_prev_members < 0) return fail(ctx, LA_EINVAL, "negative n_prev_members");
+        if (!g.d_prev_owner && !g.d_topic_moved && !g.d_member_gained && !g.d_member_lost && !g.d_moved)
+            return fail(ctx, LA_EINVAL, "every output is NULL");
+        if (g.n_topics == 0 && g.n_partitions != 0) return fail(ctx, LA_EINVAL, "partitions without topics");
+        if (g.n_partitions > 0 && (!g.d_part_off || !g.d_out_partition || !g.d_out_member_rank || !g.d_prev_partition ||
+                                   !g.d_prev_member_rank))
+            return fail(ctx, LA_EINVAL, "null buffer");
+        if (g.max_partitions_per_topic > la::kMovesLdsMaxPartitions && g.n_partitions > 0) {
+            // topics beyond one workgroup's table are found on the host
+            if (!g.h_part_off)
+                return fail(ctx, LA_EINVAL, "h_part_off is required when max_partitions_per_topic exceeds %lld", (long long)la::kMovesLdsMaxPartitions);
+            if (g.h_part_off[0] != 0 || g.h_part_off[g.n_topics] != g.n_partitions)
+                return fail(ctx, LA_EINVAL, "h_part_off must run from 0 to n_partitions");
+            for (int32_t t = 0; t < g.n_topics; ++t)
+                if (g.h_part_off[t + 1] < g.h_part_off[t]) return fail(ctx, LA_EINVAL, "offsets of topic %d decrease", t);
+        }
+        la::MovesCall c{};
+        c.n_topics = g.n_topics;
+        c.n_members = g.n_members;
+        c.n_prev_members = g.d_prev_rank_map ? g.n_prev_members : g.n_members;
+        c.n_partitions = g.n_partitions;
+        c.max_partitions_per_topic = g.max_partitions_per_topic;
+        c.part_off = g.d_part_off;
+        c.out_partition = g.d_out_partition;
+        c.out_member_rank = g.d_out_member_rank;
+        c.prev_partition = g.d_prev_partition;
+        c.prev_member_rank = g.d_prev_member_rank;
+        c.map = g.d_prev_rank_map;
+        c.prev_owner = g.d_prev_owner;
+        c.topic_moved = g.d_topic_moved;
+        c.member_gained = g.d_member_gained;
+        c.member_lost = g.d_member_lost;
+        c.moved = g.d_moved;
+        Shard& sh = ctx->shards[(size_t)shard];
+        LA_HIP(ctx, hipSetDevice(sh.device));
+        hipError_t e = la::assignment_moves_launch(sh.moves, c, g.h_part_off, sh.lanes[0].d_status, (hipStream_t)stream);
+        if (e != hipSuccess)
+            return fail(ctx, e == hipErrorOutOfMemory ? LA_ENOMEM : LA_EHIP, "assignment_moves: %s", hipGetErrorString(e));
+        return LA_OK;
+    } catch (...) {
+        return fail(ctx, LA_ENOMEM, "exception in la_assignment_moves_device");
     }
 }
 

@@ -53,6 +53,9 @@ constexpr uint32_t kStatusBounds = 64u;    // LA_FLAG_BOUNDS: a lag or a partiti
 
 constexpr uint32_t kStatusLoads = 128u;    // la_member_loads_device: a member rank outside [-1, M) / a consumer rank outside [0, M)
 
+constexpr uint32_t kStatusMoves = 256u;    // la_assignment_moves_device: a duplicate partition id inside a topic, a current id without a
+                                           // previous one, or a rank (previous, mapped or current) out of range
+
 constexpr int32_t kTileNoDefer = 8;       // TileArgs::flags: the bounds prove that every tile packs -- no deferred list, no wide
                                           // launch; a tile that does not pack after all raises kStatusBounds
 constexpr int32_t kTileWireOut = 16;      // TileArgs::flags: out_wire instead of out_pid / out_rank (needs kTileNoDefer)
@@ -283,5 +286,40 @@ constexpr int32_t kLoadsLdsMaxMembers = 4095;
 hipError_t member_loads_launch(int64_t n, const int32_t* member_rank, int64_t k, const int32_t* cons_rank,
                                const int64_t* total_lag, int32_t n_members, int64_t* member_partitions, int64_t* member_lag,
                                int64_t* unassigned, uint32_t* status, hipStream_t stream);
+
+// ---- who moved between two rebalances (la_moves.hip) ----------------------------------------------------------------------
+// A topic of up to kMovesLdsMaxPartitions partitions is joined in one workgroup's LDS (a 64 KiB table at the limit); larger
+// topics go through a table in device memory.  Up to kMovesLdsMaxMembers members the gained / lost counts are 32-bit LDS bins
+// beside the table (2 x 4096 counters = 32 KiB: 96 KiB of the 160 KiB a gfx950 workgroup may take), beyond it global atomics.
+constexpr int64_t kMovesLdsMaxPartitions = 4096;
+constexpr int32_t kMovesLdsMaxMembers = 4096;
+constexpr int32_t kMovesMaxMembers = (1 << 30) - 1;     // a slot keeps owner + 2 in 31 bits next to its matched mark
+
+struct MovesScratch {           // of one shard, grown lazily: never the assign scratch (results kept on the device stay valid)
+    void* table = nullptr;      // the global form's hash table
+    size_t table_cap = 0;
+    void* d_items = nullptr;    // its topic list, built in h_items (pinned) and copied on the call's stream
+    size_t d_items_cap = 0;
+    void* h_items = nullptr;
+    size_t h_items_cap = 0;
+    hipEvent_t copied = nullptr;    // the last copy out of h_items
+};
+
+struct MovesCall {              // la_moves_args (lagassign.h), validated
+    int32_t n_topics, n_members, n_prev_members;
+    int64_t n_partitions, max_partitions_per_topic;
+    const int64_t* part_off;
+    const int32_t *out_partition, *out_member_rank, *prev_partition, *prev_member_rank;
+    const int32_t* map;         // null: identity
+    int32_t* prev_owner;        // outputs, each may be null
+    int64_t *topic_moved, *member_gained, *member_lost, *moved;
+};
+
+// Zeroes the outputs on `stream`, then at most one launch (hint within kMovesLdsMaxPartitions) or three (LDS form for the
+// small topics, insert and lookup of the global form for the others, found from h_part_off).  hipErrorOutOfMemory when the
+// table cannot be had.  Sets kStatusMoves / kStatusShape / kStatusInternal.
+hipError_t assignment_moves_launch(MovesScratch& s, const MovesCall& c, const int64_t* h_part_off, uint32_t* status,
+                                   hipStream_t stream);
+void moves_scratch_release(MovesScratch& s);
 
 }  // namespace la

@@ -173,10 +173,60 @@ def member_loads_numpy(out_member_rank, cons_rank, out_total_lag, n_members: int
     return counts[1:].copy(), lag.view(np.int64), int(counts[0])
 
 
+def assignment_moves_numpy(part_off, out_partition, out_member_rank, prev_partition, prev_member_rank, n_members: int,
+                           prev_rank_map=None):
+    """la_assignment_moves_device restated on the host -> (prev_owner int32[N], topic_moved int64[T], gained int64[M],
+    lost int64[M], moved int).  Both assignments share the layout `part_off` and come in their own assignment order: each side is
+    sorted by (topic, partition id) with np.lexsort, after which the two line up position by position.  prev_owner[i] is the
+    previous owner of current entry i in today's ranks (prev_rank_map[p], or p itself without a map; -1 stays -1); an entry
+    moved when that differs from out_member_rank[i]; a moved entry counts for its topic, for the member that gained it (>= 0)
+    and the one that lost it (>= 0).  ValueError for what the device reports as LA_EINVAL: a duplicate id inside a topic, id
+    sets that differ, a previous rank outside [-1, M_prev), a mapped or current rank outside [-1, M).  The yardstick of the GPU
+    tests."""
+    m = int(n_members)
+    po = np.asarray(part_off, dtype=np.int64).ravel()
+    cur_id = np.asarray(out_partition, dtype=np.int64).ravel()
+    prev_id = np.asarray(prev_partition, dtype=np.int64).ravel()
+    c = np.asarray(out_member_rank, dtype=np.int64).ravel()
+    p = np.asarray(prev_member_rank, dtype=np.int64).ravel()
+    if m < 0 or po.size < 1 or po[0] != 0 or (np.diff(po) < 0).any():
+        raise ValueError("n_members < 0, or part_off does not ascend from 0")
+    t, n = po.size - 1, int(po[-1])
+    if not (cur_id.size == prev_id.size == c.size == p.size == n):
+        raise ValueError("the four assignment arrays must hold part_off[T] entries each")
+    if prev_rank_map is None:
+        m_prev, q = m, p
+    else:
+        rank_map = np.asarray(prev_rank_map, dtype=np.int64).ravel()
+        m_prev = rank_map.size
+    if n and (p.min() < -1 or p.max() >= m_prev):
+        raise ValueError("a previous member rank lies outside [-1, n_prev_members)")
+    if prev_rank_map is not None:
+        q = np.where(p < 0, -1, rank_map[np.maximum(p, 0)]) if m_prev else p
+    if n and (q.min() < -1 or q.max() >= m or c.min() < -1 or c.max() >= m):
+        raise ValueError("a mapped previous rank or a current member rank lies outside [-1, n_members)")
+    topic = np.repeat(np.arange(t, dtype=np.int64), np.diff(po))
+    by_cur, by_prev = np.lexsort((cur_id, topic)), np.lexsort((prev_id, topic))
+    a, b = cur_id[by_cur], prev_id[by_prev]                 # (topic is ascending already: both sorted sides share it)
+    for ids in (a, b):
+        if n > 1 and ((ids[1:] == ids[:-1]) & (topic[1:] == topic[:-1])).any():
+            raise ValueError("a partition id appears twice inside a topic")
+    if (a != b).any():
+        raise ValueError("a topic's current and previous partition ids differ")
+    owner = np.empty(n, dtype=np.int64)
+    owner[by_cur] = q[by_prev]
+    moved = owner != c
+    topic_moved = np.bincount(topic[moved], minlength=t).astype(np.int64)[:t]
+    gained = np.bincount(c[moved & (c >= 0)], minlength=m).astype(np.int64)[:m]
+    lost = np.bincount(owner[moved & (owner >= 0)], minlength=m).astype(np.int64)[:m]
+    return owner.astype(np.int32), topic_moved, gained, lost, int(moved.sum())
+
+
 def reduce_member_loads(partitions, lag, unassigned, group=None):
     """Partial roll-ups of the ranks' shards -> the group-wide roll-up on every rank: ONE all_reduce(SUM) over a single int64
     tensor of 2 * M + 1 entries (shards are disjoint topic ranges, so the sum of the partial roll-ups IS the roll-up; int64
-    sums wrap like Java's).  numpy arrays / host tensors travel as a host tensor (gloo), device tensors stay on their device
+    sums wrap like Java's).  It is also the group-wide reduction of la_assignment_moves_device's per-shard results, for the same
+    reason: reduce_member_loads(gained, lost, moved) gives every rank the gained / lost counts and the moved total of the batch.  numpy arrays / host tensors travel as a host tensor (gloo), device tensors stay on their device
     (nccl = RCCL).  Returns (partitions, lag, unassigned) in the kind that came in (numpy in, numpy out)."""
     import torch
     import torch.distributed as dist
