@@ -31,6 +31,8 @@
  *                           prints (Main.java:279-306) -- partitions and total lag every member ended up with
  *   la_assignment_moves_device  nothing in the reference (its assignor is eager: every rebalance deals all partitions out again):
  *                           how many partitions changed owner between two rebalances, and who gained or lost them
+ *   la_verify_assignment_device  nothing in the reference: a certificate that a result IS what assignTopic (Main.java:204-266)
+ *                           would have produced for these inputs, checked without running it again
  *   la_hint_next_call       nothing in the reference's arithmetic: what the marshalling loop of readTopicPartitionLags
  *                           (Main.java:344-356) knows for free -- the largest end offset and partition id it walked past
  *   la_last_phase_times     nothing: measurement hook (radix-sort phase against the HBM roofline)
@@ -247,6 +249,7 @@ const char *la_last_error(const la_ctx *ctx);
  *   0.5.0 (500)  round 6: la_wake (the device's queues woken while the host still fetches offsets); LA_FLAG values unchanged
  *                later, WITHOUT a bump: la_member_loads_device / la_member_loads_device_on (per-member roll-up of an assignment);
  *                la_assignment_moves_device / la_assignment_moves_device_on (who moved between two rebalances);
+ *                la_verify_assignment_device / la_verify_assignment_device_on (certify an assignment);
  *                a shim detects them by symbol lookup (dlsym / getattr) instead of by version */
 #define LA_VERSION 500
 int la_version(void);
@@ -614,6 +617,49 @@ int la_assignment_moves_device(la_ctx *ctx, const la_moves_args *args, void *str
 /* The same on shard `shard` (buffers and stream on that shard's device; la_sync_on reports the errors).  Shards hold disjoint
  * topic ranges, so the element-wise sum of their gained / lost / moved is that of the whole batch. */
 int la_assignment_moves_device_on(la_ctx *ctx, int shard, const la_moves_args *args, void *stream);
+
+/* Certify an assignment (nothing in the reference computes it).  `batch` is the struct an assign call took, inputs and results:
+ * the same memory, stream-ordered behind la_assign_batch_device with no sync in between, or any other arrays of that layout
+ * (what la_unpack_results_on wrote on the far side of the all-gather, for instance).  Per topic with P partitions, C consumers,
+ * distinct partition ids and strictly ascending cons_rank the reference's result is unique (Main.java:204-266), and the topic's
+ * (d_out_partition, d_out_member_rank, d_out_total_lag) equal it if and only if
+ *   V1 ids     every d_out_partition[i] of the segment is an id of the topic's d_partition_id segment, none used twice; lag_i is
+ *              then the Java lag of that input partition (d_lag, or begin / end / committed with reset_mode, as the assign
+ *              call computes it)
+ *   V2 order   neighbours i, i+1: lag_i > lag_(i+1) signed, or the lags are equal and id_i < id_(i+1)
+ *   V3 owners  C == 0: every rank is -1.  Otherwise every rank is one of the topic's cons_rank values; inside a round (positions
+ *              [rC, min(P, rC + C))) the owners are distinct and the keys (the owner's wrapping int64 total over the earlier
+ *              rounds, rank) ascend strictly along the positions, compared signed as Long.compare does; in a partial last
+ *              round every consumer that was not picked has a key greater than the last picked one
+ *   V4 totals  d_out_total_lag[k] is consumer k's final wrapping total (skipped when d_out_total_lag == NULL)
+ * Outputs are OVERWRITTEN; either may be NULL, both NULL is LA_EINVAL:
+ *   d_topic_verdict[t]  0: topic t is certified.  Otherwise a mask of LA_VERDICT_*.  A topic that is not certified never reads
+ *                       0, and LA_VERDICT_UNCHECKED is exact (it stands alone: such a topic reports no other bit).  The class
+ *                       bits 1-16 are diagnostics: a single fault sets the bit of its class, and once V1 fails what the later
+ *                       checks report for that topic is unspecified.
+ *   d_summary[4]        [0] topics with any of the bits 1-16, [1] topics UNCHECKED, [2] / [3] the lowest topic index counted in
+ *                       [0] / [1], or -1
+ * A non-zero verdict is data, not an error: la_sync still returns LA_OK.  Offsets that leave [0, N) / [0, K) are LA_ESHAPE from
+ * la_sync: nothing is read through them, and the topic reads UNCHECKED.  T == 0 and N == 0 are valid (summary 0, 0, -1, -1).
+ * Of the batch's other fields: algo and h_part_off / h_cons_off are not looked at; flags with LA_FLAG_WIRE_OUT is LA_EINVAL
+ * (unpack first), every other flag is ignored; the shape hints size the workgroups' LDS and nothing else -- a hint that is not
+ * positive or lies beyond the limit asks for the limit, and a topic within the limit but over a hint is, as in the assign call,
+ * LA_ESHAPE from la_sync (it reads UNCHECKED, the other topics are verified as usual).
+ * At most one kernel launch (la_last_launches) behind the memsets that initialise the summary; no scratch, so the results kept
+ * for la_group_last_by_member stay valid.  Buffer contract as everywhere in this header: element alignment only, writes only
+ * inside [0, T) / [0, 4), the inputs and the results under test are never written. */
+#define LA_VERDICT_IDS        1   /* V1 */
+#define LA_VERDICT_ORDER      2   /* V2 */
+#define LA_VERDICT_OWNER      4   /* V3: not a subscriber, the -1 rule broken, or twice in a round */
+#define LA_VERDICT_GREEDY     8   /* V3: the keys of a round do not ascend, or a consumer left out should have been picked */
+#define LA_VERDICT_TOTALS    16   /* V4 */
+#define LA_VERDICT_UNCHECKED 32   /* the topic could not be verified: more than 4096 partitions or more than 4096 consumers,  *
+                                   * duplicate ids in the INPUT segment, or a cons_rank segment that is not strictly ascending */
+int la_verify_assignment_device(la_ctx *ctx, const la_device_batch *batch, int32_t *d_topic_verdict, int64_t *d_summary,
+                                void *stream);
+/* The same on shard `shard` (buffers and stream on that shard's device; la_sync_on reports the errors). */
+int la_verify_assignment_device_on(la_ctx *ctx, int shard, const la_device_batch *batch, int32_t *d_topic_verdict,
+                                   int64_t *d_summary, void *stream);
 
 #ifdef __cplusplus
 }

@@ -38,6 +38,11 @@ LOADS_LDS_MAX_MEMBERS = 4095
 # kMovesLdsMaxMembers of csrc/la_kernels.h; results are the same, tests run both sides)
 MOVES_LDS_MAX_PARTITIONS = 4096
 MOVES_LDS_MAX_MEMBERS = 4096
+# la_verify_assignment_device: d_topic_verdict[t] is 0 (certified) or a mask of these; a topic of more than VERIFY_MAX_PARTITIONS
+# partitions or VERIFY_MAX_CONSUMERS consumers reads LA_VERDICT_UNCHECKED (kVerifyMax* of csrc/la_kernels.h)
+LA_VERDICT_IDS, LA_VERDICT_ORDER, LA_VERDICT_OWNER, LA_VERDICT_GREEDY, LA_VERDICT_TOTALS, LA_VERDICT_UNCHECKED = 1, 2, 4, 8, 16, 32
+VERIFY_MAX_PARTITIONS = 4096
+VERIFY_MAX_CONSUMERS = 4096
 
 EXPORTED_SYMBOLS = (
     "la_create", "la_destroy", "la_last_error", "la_version", "la_compute_lag",
@@ -52,6 +57,7 @@ EXPORTED_SYMBOLS = (
     "la_hint_next_call", "la_last_launches", "la_last_phase_times_sized", "la_wake",
     "la_member_loads_device", "la_member_loads_device_on",
     "la_assignment_moves_device", "la_assignment_moves_device_on",
+    "la_verify_assignment_device", "la_verify_assignment_device_on",
 )
 
 _i64p = ctypes.POINTER(ctypes.c_int64)
@@ -252,6 +258,13 @@ def load() -> ctypes.CDLL:
         L.la_assignment_moves_device.argtypes = [ctypes.c_void_p, ctypes.POINTER(MovesArgs), ctypes.c_void_p]
         L.la_assignment_moves_device_on.restype = ctypes.c_int
         L.la_assignment_moves_device_on.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(MovesArgs), ctypes.c_void_p]
+    if hasattr(L, "la_verify_assignment_device_on"):
+        L.la_verify_assignment_device.restype = ctypes.c_int
+        L.la_verify_assignment_device.argtypes = [ctypes.c_void_p, ctypes.POINTER(DeviceBatch), ctypes.c_void_p, ctypes.c_void_p,
+                                                  ctypes.c_void_p]
+        L.la_verify_assignment_device_on.restype = ctypes.c_int
+        L.la_verify_assignment_device_on.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(DeviceBatch), ctypes.c_void_p,
+                                                     ctypes.c_void_p, ctypes.c_void_p]
     _lib = L
     return L
 
@@ -656,6 +669,26 @@ class Context:
         if not args.struct_size:
             args.struct_size = ctypes.sizeof(MovesArgs)
         self._check(fn(self._h, shard, ctypes.byref(args), ctypes.c_void_p(stream)))
+
+    def verify_assignment_device(self, batch: Optional[DeviceBatch], d_topic_verdict: int, d_summary: int, stream: Optional[int] = None,
+                                 shard: Optional[int] = None) -> None:
+        """la_verify_assignment_device[_on]: certifies the results `batch` points at against its inputs -- the struct an assign
+        call took, verified behind it on the same stream without a sync, or any arrays of that layout.  d_topic_verdict (int32[T])
+        reads 0 per certified topic, otherwise a mask of LA_VERDICT_*; d_summary (int64[4]) = topics failed, topics unchecked,
+        the lowest index of each or -1.  Device addresses as ints, either may be 0 (NULL).  A non-zero verdict is data: sync()
+        raises only for offsets that leave the arrays or a topic over its hint (LA_ESHAPE).  stream None = HIP's default
+        stream; shard None = the form without a shard argument.  sharding.verify_assignment_numpy is the same on the host."""
+        name = "la_verify_assignment_device" if shard is None else "la_verify_assignment_device_on"
+        fn = getattr(self._lib, name, None)
+        if fn is None:
+            raise LagAssignError(LA_EINVAL, "this liblagassign.so has no %s" % name)
+
+        def p(x):
+            return ctypes.c_void_p(int(x)) if x else None
+
+        b = ctypes.byref(batch) if batch is not None else None
+        head = (self._h,) if shard is None else (self._h, int(shard))
+        self._check(fn(*head, b, p(d_topic_verdict), p(d_summary), ctypes.c_void_p(stream or 0)))
 
     # -- device-resident entry point ------------------------------------------------
     def assign_batch_device(self, batch: DeviceBatch, stream: int = 0, shard: int = 0) -> None:

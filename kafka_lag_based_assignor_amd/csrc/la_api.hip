@@ -2447,6 +2447,64 @@ LA_API int la_assignment_moves_device_on(la_ctx* ctx, int shard, const la_moves_
     }
 }
 
+// Certifies an assignment (la_verify.hip).  Owns no scratch: everything lives in the workgroups' LDS and the caller's outputs,
+// so the results kept for la_group_last_by_member stay as they are.
+LA_API int la_verify_assignment_device(la_ctx* ctx, const la_device_batch* batch, int32_t* d_topic_verdict, int64_t* d_summary,
+                                       void* stream) {
+    return la_verify_assignment_device_on(ctx, 0, batch, d_topic_verdict, d_summary, stream);
+}
+
+LA_API int la_verify_assignment_device_on(la_ctx* ctx, int shard, const la_device_batch* batch, int32_t* d_topic_verdict,
+                                          int64_t* d_summary, void* stream) {
+    DeviceGuard restore_device;
+    LaunchSpan span(ctx);
+    if (!ctx) return LA_EINVAL;
+    try {
+        if (shard < 0 || shard >= (int)ctx->shards.size()) return fail(ctx, LA_EINVAL, "shard %d of %d", shard, (int)ctx->shards.size());
+        if (!batch) return fail(ctx, LA_EINVAL, "batch is NULL");
+        const la_device_batch& b = *batch;
+        if (b.n_topics < 0 || b.n_partitions < 0 || b.n_consumers < 0) return fail(ctx, LA_EINVAL, "negative size");
+        if (!d_topic_verdict && !d_summary) return fail(ctx, LA_EINVAL, "d_topic_verdict and d_summary are both NULL");
+        if (b.flags & LA_FLAG_WIRE_OUT)
+            return fail(ctx, LA_EINVAL, "LA_FLAG_WIRE_OUT: unpack the results with la_unpack_results_on before verifying them");
+        if (b.n_topics == 0 && (b.n_partitions != 0 || b.n_consumers != 0)) return fail(ctx, LA_EINVAL, "partitions or consumers without topics");
+        if (b.n_topics > 0 && (!b.d_part_off || !b.d_cons_off)) return fail(ctx, LA_EINVAL, "null offsets");
+        if (b.n_partitions > 0 && (!b.d_out_partition || !b.d_out_member_rank)) return fail(ctx, LA_EINVAL, "null results");
+        if (b.n_partitions > 0 && (!b.d_partition_id || (!b.d_lag && (!b.d_end_off || !b.d_committed_off))))
+            return fail(ctx, LA_EINVAL, "null per-partition input");
+        if (b.n_consumers > 0 && !b.d_cons_rank) return fail(ctx, LA_EINVAL, "null cons_rank");
+        if (!b.d_lag && b.reset_mode != LA_RESET_LATEST && !b.d_begin_off && b.n_partitions > 0)
+            return fail(ctx, LA_EINVAL, "begin_off is required unless reset_mode is LA_RESET_LATEST");
+        la::VerifyCall c{};
+        c.n_topics = b.n_topics;
+        c.reset_latest = b.reset_mode == LA_RESET_LATEST ? 1 : 0;
+        c.n_partitions = b.n_partitions;
+        c.n_consumers = b.n_consumers;
+        c.max_partitions_per_topic = b.max_partitions_per_topic;
+        c.max_consumers_per_topic = b.max_consumers_per_topic;
+        c.part_off = b.d_part_off;
+        c.cons_off = b.d_cons_off;
+        c.pid = b.d_partition_id;
+        c.begin = b.d_begin_off;
+        c.end = b.d_end_off;
+        c.committed = b.d_committed_off;
+        c.lag = b.d_lag;
+        c.cons_rank = b.d_cons_rank;
+        c.out_pid = b.d_out_partition;
+        c.out_rank = b.d_out_member_rank;
+        c.out_total = b.d_out_total_lag;
+        c.verdict = d_topic_verdict;
+        c.summary = d_summary;
+        Shard& sh = ctx->shards[(size_t)shard];
+        LA_HIP(ctx, hipSetDevice(sh.device));
+        hipError_t e = la::verify_assignment_launch(c, sh.lanes[0].d_status, (hipStream_t)stream);
+        if (e != hipSuccess) return fail(ctx, LA_EHIP, "verify_assignment: %s", hipGetErrorString(e));
+        return LA_OK;
+    } catch (...) {
+        return fail(ctx, LA_ENOMEM, "exception in la_verify_assignment_device");
+    }
+}
+
 // Every member's list from the results the shards hold (Shard::last_*): one shard -> its CSR straight into the caller's
 // arrays; several -> grouped per shard on its device, merged by offset on the host.
 static int group_last_impl(la_ctx* ctx, int32_t n_members, int64_t* member_off, int32_t* grouped_topic,

@@ -322,4 +322,28 @@ hipError_t assignment_moves_launch(MovesScratch& s, const MovesCall& c, const in
                                    hipStream_t stream);
 void moves_scratch_release(MovesScratch& s);
 
+// ---- certify an assignment (la_verify.hip) ---------------------------------------------------------------------------------
+// One workgroup verifies a topic in LDS: the id join (la_join.h), the topic's lags, its consumers' ranks and one slot per
+// (round, consumer) -- 136 KiB at the limit of both, within the 160 KiB a gfx950 workgroup may take.
+constexpr int64_t kVerifyMaxPartitions = 4096;
+constexpr int64_t kVerifyMaxConsumers = 4096;
+constexpr uint32_t kVerdictIds = 1u, kVerdictOrder = 2u, kVerdictOwner = 4u, kVerdictGreedy = 8u, kVerdictTotals = 16u,
+                   kVerdictUnchecked = 32u;      // LA_VERDICT_* of lagassign.h
+
+struct VerifyCall {             // la_device_batch (lagassign.h) as la_verify_assignment_device reads it, validated
+    int32_t n_topics, reset_latest;
+    int64_t n_partitions, n_consumers, max_partitions_per_topic, max_consumers_per_topic;
+    const int64_t *part_off, *cons_off;
+    const int32_t* pid;
+    const int64_t *begin, *end, *committed, *lag;      // lag non-null: precomputed lags, offsets ignored; begin may be null
+    const int32_t* cons_rank;
+    const int32_t *out_pid, *out_rank;                 // the results under test
+    const int64_t* out_total;                          // null: the totals are not checked
+    int32_t* verdict;           // [T] or null
+    int64_t* summary;           // [4] or null
+};
+
+// Initialises the summary on `stream`, then at most ONE launch.  Sets kStatusShape / kStatusInternal.
+hipError_t verify_assignment_launch(const VerifyCall& c, uint32_t* status, hipStream_t stream);
+
 }  // namespace la

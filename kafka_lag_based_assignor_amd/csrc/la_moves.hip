@@ -13,7 +13,7 @@
 // table is at most half full (2^ceil(log2(2 P)) slots), so a walk always ends at a hit or an empty slot; every walk is bounded
 // by the slot count all the same and raises kStatusInternal when it runs out.  No thread ever waits for another.
 //
-// The ONE probing routine (table_insert / table_lookup) runs in two address spaces:
+// The ONE probing routine (table_insert / table_lookup, la_join.h) runs in two address spaces:
 //   LDS form     topics up to kMovesLdsMaxPartitions.  Persistent workgroups walk topics blockIdx.x, + gridDim.x, ...; per topic:
 //                clear the slots the topic needs, insert the previous entries, barrier, look the current entries up, store
 //                prev_owner, reduce the moved count, ONE plain store to topic_moved[t].  The table is sized from the call's
@@ -29,6 +29,7 @@
 
 #include "la_kernels.h"
 #include "la_device.h"
+#include "la_join.h"
 
 namespace la {
 
@@ -36,7 +37,6 @@ namespace {
 
 constexpr int kMovesThreads = 256;
 constexpr int kMovesChunk = 4 * kMovesThreads;      // global form: entries of one workgroup step
-constexpr uint64_t kSlotMark = 1ull << 63;
 constexpr int kMovesMaxTables = 16;                 // copies of the bins ...
 constexpr int kMovesFewBins = 2048;                 // ... while all of them stay within this many counters (8 KiB)
 constexpr int64_t kMovesMaxBinned = 1ll << 32;      // entries of a call whose moves 32-bit bins can count without wrapping
@@ -74,47 +74,6 @@ __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) v += (uint32_t)__shfl_xor((int)v, d);
     return v;
-}
-
-__device__ __forceinline__ uint64_t first_slot(int32_t id, int bits) {      // Fibonacci hashing: strided ids spread out
-    return ((uint64_t)(uint32_t)id * 0x9E3779B97F4A7C15ull) >> (64 - bits);
-}
-
-// 0: inserted; kStatusMoves: the id is there already; kStatusInternal: no empty slot within the table (never expected)
-template <int SCOPE>
-__device__ __forceinline__ uint32_t table_insert(uint64_t* table, int bits, int32_t id, int32_t owner) {
-    const uint64_t mask = (1ull << bits) - 1;
-    const uint64_t word = ((uint64_t)(uint32_t)(owner + 2) << 32) | (uint32_t)id;
-    uint64_t h = first_slot(id, bits);
-    for (uint64_t n = 0; n <= mask; ++n) {
-        unsigned long long seen = 0;
-        if (__hip_atomic_compare_exchange_strong((unsigned long long*)(table + h), &seen, (unsigned long long)word,
-                                                 __ATOMIC_RELAXED, __ATOMIC_RELAXED, SCOPE))
-            return 0;
-        if ((uint32_t)seen == (uint32_t)id) return kStatusMoves;
-        h = (h + 1) & mask;
-    }
-    return kStatusInternal;
-}
-
-// 0: *owner <- the id's previous owner, its slot marked; kStatusMoves: no such id, or marked before (a duplicate)
-template <int SCOPE>
-__device__ __forceinline__ uint32_t table_lookup(uint64_t* table, int bits, int32_t id, int32_t* owner) {
-    const uint64_t mask = (1ull << bits) - 1;
-    uint64_t h = first_slot(id, bits);
-    for (uint64_t n = 0; n <= mask; ++n) {
-        const uint64_t w = __hip_atomic_load((unsigned long long*)(table + h), __ATOMIC_RELAXED, SCOPE);
-        if (w == 0) return kStatusMoves;
-        if ((uint32_t)w == (uint32_t)id) {
-            const uint64_t old = __hip_atomic_fetch_or((unsigned long long*)(table + h), (unsigned long long)kSlotMark,
-                                                       __ATOMIC_RELAXED, SCOPE);
-            if (old & kSlotMark) return kStatusMoves;
-            *owner = (int32_t)((uint32_t)(old >> 32) & 0x7FFFFFFFu) - 2;
-            return 0;
-        }
-        h = (h + 1) & mask;
-    }
-    return kStatusInternal;
 }
 
 // previous rank -> that owner in today's ranks; false: a rank out of range (nothing is read or stored through it)

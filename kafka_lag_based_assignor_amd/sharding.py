@@ -222,6 +222,114 @@ def assignment_moves_numpy(part_off, out_partition, out_member_rank, prev_partit
     return owner.astype(np.int32), topic_moved, gained, lost, int(moved.sum())
 
 
+VERDICT_IDS, VERDICT_ORDER, VERDICT_OWNER, VERDICT_GREEDY, VERDICT_TOTALS, VERDICT_UNCHECKED = 1, 2, 4, 8, 16, 32
+
+
+def verify_assignment_numpy(part_off, partition_id, cons_off, cons_rank, out_partition, out_member_rank, out_total_lag=None, *,
+                            lag=None, begin=None, end=None, committed=None, reset_latest: bool = True,
+                            max_partitions: int = 4096, max_consumers: int = 4096):
+    """la_verify_assignment_device restated on the host -> (verdict int32[T], summary int64[4]).  Written from the statement of
+    the reference's result (Main.java:204-266), not by computing that result: per topic with distinct ids and strictly ascending
+    ranks,
+      V1  the output ids are the topic's input ids, none twice; lag_i is the lag of the input partition with that id
+          (`lag`, or Java's computePartitionLag of begin / end / committed; no begin array: 0)
+      V2  neighbours: lag_i > lag_(i+1) signed, or equal lags and id_i < id_(i+1)
+      V3  no consumers: every owner is -1.  Otherwise every owner subscribes, the owners of a round of C positions are
+          distinct, their keys (the owner's wrapping total over the earlier rounds, rank) ascend strictly along the round,
+          and every consumer a partial last round left out has a key above the last picked one
+      V4  out_total_lag (when given) holds every consumer's final wrapping total
+    verdict[t] is 0 or a mask of VERDICT_*; VERDICT_UNCHECKED stands alone: more than max_partitions / max_consumers, duplicate
+    input ids, ranks that do not ascend.  Once a class fails the later ones are not looked at (their bits are diagnostics).
+    summary = topics failed, topics unchecked, the lowest index of each or -1.  Offsets that leave the arrays raise ValueError.
+    The yardstick of the GPU tests; tests/test_verify_cpu.py holds it against the oracle."""
+    po = np.asarray(part_off, dtype=np.int64).ravel()
+    co = np.asarray(cons_off, dtype=np.int64).ravel()
+    pid = np.asarray(partition_id, dtype=np.int32).ravel()
+    ranks = np.asarray(cons_rank, dtype=np.int32).ravel()
+    o_pid = np.asarray(out_partition, dtype=np.int32).ravel()
+    o_own = np.asarray(out_member_rank, dtype=np.int32).ravel()
+    o_tot = None if out_total_lag is None else np.asarray(out_total_lag, dtype=np.int64).ravel()
+    n, k_all, t_all = pid.size, ranks.size, po.size - 1
+    if lag is not None:
+        lag = np.ascontiguousarray(np.asarray(lag, dtype=np.int64).ravel())
+    else:
+        e = np.ascontiguousarray(np.asarray(end, dtype=np.int64).ravel())
+        c = np.asarray(committed, dtype=np.int64).ravel()
+        fallback = e if reset_latest else (np.zeros_like(e) if begin is None else np.asarray(begin, dtype=np.int64).ravel())
+        nxt = np.ascontiguousarray(np.where(c >= 0, c, fallback))
+        d = (e.view(np.uint64) - nxt.view(np.uint64)).view(np.int64)         # Java's wrapping subtract
+        lag = np.ascontiguousarray(np.where(d > 0, d, np.int64(0)))
+    if t_all < 0 or co.size != po.size or not (lag.size == o_pid.size == o_own.size == n) or (o_tot is not None and o_tot.size != k_all):
+        raise ValueError("array sizes do not fit one layout")
+    verdict = np.zeros(t_all, dtype=np.int32)
+    u64 = np.uint64
+    for t in range(t_all):
+        a, z, ca, cz = int(po[t]), int(po[t + 1]), int(co[t]), int(co[t + 1])
+        if not (0 <= a <= z <= n and 0 <= ca <= cz <= k_all):
+            raise ValueError("the offsets of topic %d leave the arrays" % t)
+        p, c = z - a, cz - ca
+        ids, r = pid[a:z], ranks[ca:cz]
+        if p > max_partitions or c > max_consumers or np.unique(ids).size != p or (np.diff(r.astype(np.int64)) <= 0).any():
+            verdict[t] = VERDICT_UNCHECKED
+            continue
+        oid, own = o_pid[a:z], o_own[a:z]
+        # V1: the join
+        by_id = np.argsort(ids, kind="stable")
+        sorted_ids = ids[by_id]
+        at = np.minimum(np.searchsorted(sorted_ids, oid), max(p - 1, 0))
+        if p and ((sorted_ids[at] != oid).any() or np.unique(oid).size != p):
+            verdict[t] = VERDICT_IDS
+            continue
+        l = np.ascontiguousarray(lag[a:z][by_id[at]]) if p else np.empty(0, np.int64)
+        v = 0
+        # V2
+        if p > 1 and not ((l[:-1] > l[1:]) | ((l[:-1] == l[1:]) & (oid[:-1] < oid[1:]))).all():
+            v |= VERDICT_ORDER
+        # V3, V4
+        if c == 0:
+            if (own != -1).any():
+                v |= VERDICT_OWNER
+            verdict[t] = v
+            continue
+        k = np.minimum(np.searchsorted(r, own), c - 1)
+        rnd = np.arange(p, dtype=np.int64) // c
+        if (r[k] != own).any() or np.unique(rnd * c + k).size != p:
+            verdict[t] = v | VERDICT_OWNER
+            continue
+        lu = l.view(u64)
+        tot = np.zeros(c, dtype=u64)
+        np.add.at(tot, k, lu)                                               # unsigned adds wrap: the bits of Java's long sum
+        if p:
+            by_k = np.argsort(k, kind="stable")                             # a consumer's entries, in position order
+            ls, ks = lu[by_k], k[by_k]
+            excl = np.cumsum(ls, dtype=u64) - ls
+            first = np.r_[True, ks[1:] != ks[:-1]]
+            before = np.empty(p, dtype=u64)
+            before[by_k] = excl - excl[first][np.cumsum(first) - 1]
+            before = before.view(np.int64)                                  # compared signed, as Long.compare does
+            rk = r[k]
+            asc = (before[:-1] < before[1:]) | ((before[:-1] == before[1:]) & (rk[:-1] < rk[1:]))
+            if ((rnd[:-1] == rnd[1:]) & ~asc).any():
+                v |= VERDICT_GREEDY
+            if p % c:
+                lo = (p // c) * c
+                left_out = np.ones(c, dtype=bool)
+                left_out[k[lo:]] = False
+                start = tot.copy()
+                np.subtract.at(start, k[lo:], lu[lo:])                      # totals at the start of the last round
+                start = start.view(np.int64)
+                above = (start > before[p - 1]) | ((start == before[p - 1]) & (r > rk[p - 1]))
+                if (left_out & ~above).any():
+                    v |= VERDICT_GREEDY
+        if o_tot is not None and (tot.view(np.int64) != o_tot[ca:cz]).any():
+            v |= VERDICT_TOTALS
+        verdict[t] = v
+    unchecked = (verdict & VERDICT_UNCHECKED) != 0
+    failed = (verdict != 0) & ~unchecked
+    first = lambda m: int(np.flatnonzero(m)[0]) if m.any() else -1
+    return verdict, np.array([int(failed.sum()), int(unchecked.sum()), first(failed), first(unchecked)], dtype=np.int64)
+
+
 def reduce_member_loads(partitions, lag, unassigned, group=None):
     """Partial roll-ups of the ranks' shards -> the group-wide roll-up on every rank: ONE all_reduce(SUM) over a single int64
     tensor of 2 * M + 1 entries (shards are disjoint topic ranges, so the sum of the partial roll-ups IS the roll-up; int64
