@@ -3135,7 +3135,7 @@ __global__ __launch_bounds__(1024) void group_small_kernel(int n, int32_t n_memb
                                          grouped_partition, grouped_entry, start, wsum, &turn);
 #endif
     if (fin_flag) {
-        // the last launch of a zero-copy call (la_api.hip, assign_small_zc): this ONE workgroup's stores into the host's memory
+        // the last launch of a zero-copy call (la_host.hip, assign_small_zc): this ONE workgroup's stores into the host's memory
         // are out, then `done | status` goes where the calling thread is spinning -- no separate finishing launch
         __threadfence_system();
         __syncthreads();

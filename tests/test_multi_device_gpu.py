@@ -514,7 +514,7 @@ def test_inline_launch_between_deferring_launches():
 
 
 def test_small_batches_take_the_one_copy_form_and_agree_with_the_pipeline(ctx1, ctx1_chunked):
-    """A call whose inputs and results fit 2 MB travels as one H2D + one D2H through a staging buffer (la_api.hip,
+    """A call whose inputs and results fit 2 MB travels as one H2D + one D2H through a staging buffer (la_host.hip,
     assign_small); everything else takes the chunked pipeline.  Same results either way, around the threshold, with
     offsets or lags, with the results kept on the device for la_group_last_by_member, and when calls of both kinds
     alternate on one context."""
