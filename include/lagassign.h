@@ -154,6 +154,9 @@ extern "C" {
                                  * for: every topic tile-sized (shape hint within 1024 x 64, no LA_FLAG_RAGGED), LA_FLAG_BOUNDS proving that every    *
                                  * tile packs, fewer than 2^29 partitions; anything else is LA_EINVAL (run the batch without the flag and pack).     *
                                  * A pair that does not fit the format is reported by la_sync as LA_EINVAL.  d_out_total_lag is written as usual.     */
+#define LA_FLAG_VERIFY_LARGE 8192 /* la_verify_assignment_device[_on] only (every other entry ignores it): topics of more than 4096 partitions or  *
+                                  * consumers are found from h_part_off / h_cons_off (then required) and verified through tables in device memory  *
+                                  * instead of reading LA_VERDICT_UNCHECKED -- see that call.  It reads host memory and may allocate: not capturable */
 #define LA_FLAG_SERIAL_LARGE 512 /* large path: the batch's large topics one after another (round 3's form) instead of side by   *
                                  * side in shared launches (test hook / A-B)                                            */
 
@@ -641,20 +644,42 @@ int la_assignment_moves_device_on(la_ctx *ctx, int shard, const la_moves_args *a
  *                       [0] / [1], or -1
  * A non-zero verdict is data, not an error: la_sync still returns LA_OK.  Offsets that leave [0, N) / [0, K) are LA_ESHAPE from
  * la_sync: nothing is read through them, and the topic reads UNCHECKED.  T == 0 and N == 0 are valid (summary 0, 0, -1, -1).
- * Of the batch's other fields: algo and h_part_off / h_cons_off are not looked at; flags with LA_FLAG_WIRE_OUT is LA_EINVAL
- * (unpack first), every other flag is ignored; the shape hints size the workgroups' LDS and nothing else -- a hint that is not
+ * Of the batch's other fields: algo is not looked at, h_part_off / h_cons_off only with LA_FLAG_VERIFY_LARGE (below); flags with
+ * LA_FLAG_WIRE_OUT is LA_EINVAL (unpack first), every flag but these two is ignored; the shape hints size the workgroups' LDS and nothing else -- a hint that is not
  * positive or lies beyond the limit asks for the limit, and a topic within the limit but over a hint is, as in the assign call,
  * LA_ESHAPE from la_sync (it reads UNCHECKED, the other topics are verified as usual).
  * At most one kernel launch (la_last_launches) behind the memsets that initialise the summary; no scratch, so the results kept
  * for la_group_last_by_member stay valid.  Buffer contract as everywhere in this header: element alignment only, writes only
- * inside [0, T) / [0, 4), the inputs and the results under test are never written. */
+ * inside [0, T) / [0, 4), the inputs and the results under test are never written.
+ *
+ * One workgroup verifies a topic in its LDS, which holds 4096 partitions and 4096 consumers: WITHOUT LA_FLAG_VERIFY_LARGE a larger
+ * topic reads LA_VERDICT_UNCHECKED (data, not an error), no host array is read and nothing is allocated.
+ * WITH LA_FLAG_VERIFY_LARGE (the flag means nothing to any other entry point) such topics are verified too:
+ *   - h_part_off and h_cons_off are required (LA_EINVAL without them, or when they do not ascend inside [0, N] / [0, K]).  The
+ *     host walks them and lists the LARGE topics: more than 4096 partitions or more than 4096 consumers.
+ *   - Topics within the limit are verified as without the flag, verdict for verdict, the hint rules included.
+ *   - Every large topic goes through the same join and the same V1-V4 in tables in device memory (about 60 B per partition and
+ *     20 B per consumer of the large topics, a buffer of the shard's own that is grown on first use and freed by la_destroy --
+ *     never the assign scratch, so kept results stay valid; LA_ENOMEM, with nothing enqueued, when it cannot be had).  Its verdict
+ *     is 0 or a mask of LA_VERDICT_* under the rules above; d_summary counts it like any other topic.  Any consumer count is
+ *     accepted; a topic of more than 2^30 - 2 partitions still reads LA_VERDICT_UNCHECKED.
+ *   - The large topics are read through the HOST offsets alone.  Where they differ from d_part_off[t], d_part_off[t+1],
+ *     d_cons_off[t], d_cons_off[t+1] the topic reads LA_VERDICT_UNCHECKED and la_sync returns LA_ESHAPE; so does a topic that is
+ *     over the limit by the device's offsets but not by the host's.  Every verdict word is written, and counted, exactly once.
+ *   - Launches: at most 7 kernel launches (la_last_launches) -- one for the topics within the limit, at most six for ALL large
+ *     topics of the call side by side, whatever their number and size -- behind memsets and one copy of the topic list.  A
+ *     flagged call whose batch holds no large topic enqueues what the unflagged call does and allocates nothing.
+ *   - The call reads host memory while it is issued and may allocate: like an assign call that routes by h_part_off it must not
+ *     be captured into a graph. */
 #define LA_VERDICT_IDS        1   /* V1 */
 #define LA_VERDICT_ORDER      2   /* V2 */
 #define LA_VERDICT_OWNER      4   /* V3: not a subscriber, the -1 rule broken, or twice in a round */
 #define LA_VERDICT_GREEDY     8   /* V3: the keys of a round do not ascend, or a consumer left out should have been picked */
 #define LA_VERDICT_TOTALS    16   /* V4 */
-#define LA_VERDICT_UNCHECKED 32   /* the topic could not be verified: more than 4096 partitions or more than 4096 consumers,  *
-                                   * duplicate ids in the INPUT segment, or a cons_rank segment that is not strictly ascending */
+#define LA_VERDICT_UNCHECKED 32   /* the topic could not be verified: more than 4096 partitions or more than 4096 consumers    *
+                                   * (with LA_FLAG_VERIFY_LARGE: more than 2^30 - 2 partitions, or host and device offsets that *
+                                   * disagree), duplicate ids in the INPUT segment, or a cons_rank segment that is not strictly  *
+                                   * ascending                                                                                   */
 int la_verify_assignment_device(la_ctx *ctx, const la_device_batch *batch, int32_t *d_topic_verdict, int64_t *d_summary,
                                 void *stream);
 /* The same on shard `shard` (buffers and stream on that shard's device; la_sync_on reports the errors). */

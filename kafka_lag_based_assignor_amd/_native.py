@@ -26,6 +26,7 @@ LA_FLAG_NO_MOVED_SORT = 2048
 LA_FLAG_SERIAL_LARGE = 512
 LA_FLAG_BOUNDS = 1024
 LA_FLAG_WIRE_OUT = 4096
+LA_FLAG_VERIFY_LARGE = 8192
 LA_FEATURE_ATOMIC_RANK = 1
 LA_PIPELINE_ONE_COPY, LA_PIPELINE_LANES, LA_PIPELINE_STREAMS, LA_PIPELINE_ZERO_COPY, LA_PIPELINE_MAPPED = 0, 1, 2, 3, 4
 LA_CREATE_LANES_MASK, LA_CREATE_SPLIT_ALWAYS = 0xF, 0x10
@@ -39,10 +40,14 @@ LOADS_LDS_MAX_MEMBERS = 4095
 MOVES_LDS_MAX_PARTITIONS = 4096
 MOVES_LDS_MAX_MEMBERS = 4096
 # la_verify_assignment_device: d_topic_verdict[t] is 0 (certified) or a mask of these; a topic of more than VERIFY_MAX_PARTITIONS
-# partitions or VERIFY_MAX_CONSUMERS consumers reads LA_VERDICT_UNCHECKED (kVerifyMax* of csrc/la_kernels.h)
+# partitions or VERIFY_MAX_CONSUMERS consumers reads LA_VERDICT_UNCHECKED (kVerifyMax* of csrc/la_kernels.h) unless the batch carries
+# LA_FLAG_VERIFY_LARGE: such topics then go through tables in device memory, up to VERIFY_GLOBAL_MAX_PARTITIONS partitions and any
+# consumer count, in at most VERIFY_MAX_LAUNCHES kernel launches per call (kVerifyGlobalMaxPartitions / kVerifyMaxLaunches)
 LA_VERDICT_IDS, LA_VERDICT_ORDER, LA_VERDICT_OWNER, LA_VERDICT_GREEDY, LA_VERDICT_TOTALS, LA_VERDICT_UNCHECKED = 1, 2, 4, 8, 16, 32
 VERIFY_MAX_PARTITIONS = 4096
 VERIFY_MAX_CONSUMERS = 4096
+VERIFY_GLOBAL_MAX_PARTITIONS = (1 << 30) - 2
+VERIFY_MAX_LAUNCHES = 7
 
 EXPORTED_SYMBOLS = (
     "la_create", "la_destroy", "la_last_error", "la_version", "la_compute_lag",
@@ -677,7 +682,16 @@ class Context:
         reads 0 per certified topic, otherwise a mask of LA_VERDICT_*; d_summary (int64[4]) = topics failed, topics unchecked,
         the lowest index of each or -1.  Device addresses as ints, either may be 0 (NULL).  A non-zero verdict is data: sync()
         raises only for offsets that leave the arrays or a topic over its hint (LA_ESHAPE).  stream None = HIP's default
-        stream; shard None = the form without a shard argument.  sharding.verify_assignment_numpy is the same on the host."""
+        stream; shard None = the form without a shard argument.  sharding.verify_assignment_numpy is the same on the host.
+
+        A topic of more than VERIFY_MAX_PARTITIONS partitions or VERIFY_MAX_CONSUMERS consumers reads LA_VERDICT_UNCHECKED unless
+        batch.flags carries LA_FLAG_VERIFY_LARGE.  With the flag batch.h_part_off / h_cons_off are required (LA_EINVAL without
+        them, or when they do not ascend inside the arrays): the library lists those topics from the HOST offsets and verifies
+        them through tables in device memory, verdict and summary as for any other topic (the yardstick with max_partitions /
+        max_consumers raised); a topic whose host and device offsets disagree reads UNCHECKED and sync() raises LA_ESHAPE.  The
+        flagged call reads host memory and may allocate on first use (LA_ENOMEM, nothing enqueued), so it is not capturable in a
+        graph; it enqueues at most VERIFY_MAX_LAUNCHES kernels whatever the number and size of the large topics, and without a
+        large topic what the unflagged call enqueues."""
         name = "la_verify_assignment_device" if shard is None else "la_verify_assignment_device_on"
         fn = getattr(self._lib, name, None)
         if fn is None:

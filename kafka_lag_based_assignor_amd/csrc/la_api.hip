@@ -594,6 +594,7 @@ LA_API void la_destroy(la_ctx* ctx) {
         for (HostBuf* h : {&sh.g_off, &sh.g_topic, &sh.g_part, &sh.small_h, &sh.small_gh, &sh.zc_h})
             if (h->p) (void)hipHostFree(h->p);
         la::moves_scratch_release(sh.moves);
+        la::verify_scratch_release(sh.verify);
         if (sh.ready) (void)hipEventDestroy(sh.ready);
         for (hipEvent_t e : sh.chunk_ev) (void)hipEventDestroy(e);
         for (hipStream_t st : sh.copy_in)
@@ -986,8 +987,9 @@ LA_API int la_assignment_moves_device_on(la_ctx* ctx, int shard, const la_moves_
     });
 }
 
-// Certifies an assignment (la_verify.hip).  Owns no scratch: everything lives in the workgroups' LDS and the caller's outputs,
-// so the results kept for la_group_last_by_member stay as they are.
+// Certifies an assignment (la_verify.hip).  Without LA_FLAG_VERIFY_LARGE it owns no scratch: everything lives in the workgroups'
+// LDS and the caller's outputs.  With the flag the topics over the LDS limit go through tables in device memory -- the shard's
+// own buffer, not the assign scratch.  Either way the results kept for la_group_last_by_member stay as they are.
 LA_API int la_verify_assignment_device(la_ctx* ctx, const la_device_batch* batch, int32_t* d_topic_verdict, int64_t* d_summary,
                                        void* stream) {
     return la_verify_assignment_device_on(ctx, 0, batch, d_topic_verdict, d_summary, stream);
@@ -1010,6 +1012,17 @@ LA_API int la_verify_assignment_device_on(la_ctx* ctx, int shard, const la_devic
         if (b.n_consumers > 0 && !b.d_cons_rank) return fail(ctx, LA_EINVAL, "null cons_rank");
         if (!b.d_lag && b.reset_mode != LA_RESET_LATEST && !b.d_begin_off && b.n_partitions > 0)
             return fail(ctx, LA_EINVAL, "begin_off is required unless reset_mode is LA_RESET_LATEST");
+        const bool large = (b.flags & LA_FLAG_VERIFY_LARGE) != 0;
+        if (large) {
+            // topics beyond one workgroup's LDS are found on the host; the global form works from these offsets alone
+            if (!b.h_part_off || !b.h_cons_off)
+                return fail(ctx, LA_EINVAL, "LA_FLAG_VERIFY_LARGE: h_part_off and h_cons_off are required");
+            for (int32_t t = 0; t <= b.n_topics; ++t) {
+                const int64_t p = b.h_part_off[t], k = b.h_cons_off[t];
+                if (p < 0 || p > b.n_partitions || k < 0 || k > b.n_consumers || (t > 0 && (p < b.h_part_off[t - 1] || k < b.h_cons_off[t - 1])))
+                    return fail(ctx, LA_EINVAL, "LA_FLAG_VERIFY_LARGE: h_part_off / h_cons_off must ascend inside [0, n_partitions] / [0, n_consumers] (topic %d)", t < b.n_topics ? t : t - 1);
+            }
+        }
         la::VerifyCall c{};
         c.n_topics = b.n_topics;
         c.reset_latest = b.reset_mode == LA_RESET_LATEST ? 1 : 0;
@@ -1030,9 +1043,9 @@ LA_API int la_verify_assignment_device_on(la_ctx* ctx, int shard, const la_devic
         c.out_total = b.d_out_total_lag;
         c.verdict = d_topic_verdict;
         c.summary = d_summary;
-        hipError_t e = la::verify_assignment_launch(c, sh.lanes[0].d_status, (hipStream_t)stream);
-        if (e != hipSuccess) return fail(ctx, LA_EHIP, "verify_assignment: %s", hipGetErrorString(e));
-        return LA_OK;
+        hipError_t e = la::verify_assignment_launch(large ? &sh.verify : nullptr, c, b.h_part_off, b.h_cons_off,
+                                                    sh.lanes[0].d_status, (hipStream_t)stream);
+        return e != hipSuccess ? hip_fail(ctx, e, "verify_assignment: %s") : LA_OK;
     });
 }
 

@@ -103,6 +103,7 @@ struct Shard {
     DevBuf small_d, small_g;
     HostBuf small_h, small_gh;
     la::MovesScratch moves;              // la_assignment_moves_device: the global form's table and topic list
+    la::VerifyScratch verify;            // la_verify_assignment_device with LA_FLAG_VERIFY_LARGE: the global form's tables and topic list
     HostBuf zc_h;                        // zero-copy small calls: coherent, device-mapped staging the kernels read and write in place
     // pinned caller arrays (la_host_alloc): one host thread, three streams -- every H2D of the call in order on copy_in,
     // the kernels on lane 0's stream, every D2H on copy_out, chained per chunk by events (run_shard_async)

@@ -324,11 +324,26 @@ void moves_scratch_release(MovesScratch& s);
 
 // ---- certify an assignment (la_verify.hip) ---------------------------------------------------------------------------------
 // One workgroup verifies a topic in LDS: the id join (la_join.h), the topic's lags, its consumers' ranks and one slot per
-// (round, consumer) -- 136 KiB at the limit of both, within the 160 KiB a gfx950 workgroup may take.
+// (round, consumer) -- 136 KiB at the limit of both, within the 160 KiB a gfx950 workgroup may take.  Topics beyond that go,
+// with LA_FLAG_VERIFY_LARGE, through the same tables in device memory (the global form: all large topics of a call side by side
+// in kVerifyGlobalLaunches launches ordered by their boundaries), found on the host from h_part_off / h_cons_off.
 constexpr int64_t kVerifyMaxPartitions = 4096;
 constexpr int64_t kVerifyMaxConsumers = 4096;
+constexpr int64_t kVerifyGlobalMaxPartitions = (1 << 30) - 2;      // the join's payload (an index + 2) keeps bit 63 for the mark
+constexpr int kVerifyGlobalLaunches = 6;      // insert | lookup | order + chunk sums | chunk scan | apply | rounds + left out
+constexpr int kVerifyMaxLaunches = 1 + kVerifyGlobalLaunches;      // what la_last_launches reports at most (lagassign.h)
 constexpr uint32_t kVerdictIds = 1u, kVerdictOrder = 2u, kVerdictOwner = 4u, kVerdictGreedy = 8u, kVerdictTotals = 16u,
                    kVerdictUnchecked = 32u;      // LA_VERDICT_* of lagassign.h
+
+struct VerifyScratch {          // of one shard, grown lazily: never the assign scratch (results kept on the device stay valid)
+    void* work = nullptr;       // the global form's tables, one allocation carved into regions
+    size_t work_cap = 0;
+    void* d_items = nullptr;    // its topic list, built in h_items (pinned) and copied on the call's stream
+    size_t d_items_cap = 0;
+    void* h_items = nullptr;
+    size_t h_items_cap = 0;
+    hipEvent_t copied = nullptr;    // the last copy out of h_items
+};
 
 struct VerifyCall {             // la_device_batch (lagassign.h) as la_verify_assignment_device reads it, validated
     int32_t n_topics, reset_latest;
@@ -344,6 +359,12 @@ struct VerifyCall {             // la_device_batch (lagassign.h) as la_verify_as
 };
 
 // Initialises the summary on `stream`, then at most ONE launch.  Sets kStatusShape / kStatusInternal.
-hipError_t verify_assignment_launch(const VerifyCall& c, uint32_t* status, hipStream_t stream);
+// With `large` (LA_FLAG_VERIFY_LARGE; h_part_off / h_cons_off validated by the caller: ascending inside [0, N] / [0, K]) the
+// topics over the limit are listed from the host offsets and verified by the global form in front of that launch: at most
+// kVerifyGlobalLaunches more, whatever their number and size; hipErrorOutOfMemory, with nothing enqueued, when its tables
+// cannot be had.  Without a large topic the flagged call enqueues what the unflagged one does and touches no scratch.
+hipError_t verify_assignment_launch(VerifyScratch* large, const VerifyCall& c, const int64_t* h_part_off,
+                                    const int64_t* h_cons_off, uint32_t* status, hipStream_t stream);
+void verify_scratch_release(VerifyScratch& s);
 
 }  // namespace la

@@ -25,6 +25,25 @@
 // Every phase is safe on any content: an index comes from the join's own payload or from a bisection, never from an id or a
 // rank, so a failing topic is walked to the end like any other and leaves nothing behind -- every word a later topic reads it
 // has written itself behind a barrier.  Accesses are one element wide.  No thread waits for another; every walk is bounded.
+//
+// GLOBAL FORM (LA_FLAG_VERIFY_LARGE): topics of more than kVerifyMaxPartitions partitions or kVerifyMaxConsumers consumers, listed
+// by the host from h_part_off / h_cons_off (VerifyBig, a pinned list one copy brings over), all of a call side by side.  The
+// same regions live in device memory -- table, lag[P], kidx[P] (64 bits: any consumer count), slot[rounds x C] of 32 bits,
+// before[P], tot_last[C], the chunk sums, one word of verdict bits per topic -- and the same phases are launches; the ONLY
+// grid-wide order is the launch boundary (no grid barrier, no spin, no cooperative launch).  Workgroup steps are numbered
+// through the topics per domain (partitions, consumers, (chunk, consumer) pairs); a workgroup bisects the list for its step.
+//   memsets  table = 0, slot = none, bits = 0
+//   G0  insert the input ids (duplicate: UNCHECKED) | neighbouring ranks | the host's offsets against the device's (a mismatch:
+//       UNCHECKED + kStatusShape; everything below works from the HOST's offsets, validated on the host, whatever the device's say)
+//   G1  look every output id up, lag[i], bisect the owner in the topic's cons_rank segment, slot[round x C + k] = i, kidx[i] = k
+//   G2  neighbours' order, the slot read back | per (chunk of ~sqrt(rounds) rounds, consumer): the sum of lag[slot]
+//   G3  per consumer: exclusive scan over its chunk sums (in place), the final total against out_total_lag (V4)
+//   G4  per (chunk, consumer): walk the chunk's rounds from the scanned sum -> before[i], tot_last[k]
+//   G5  (before, rank) of neighbours in a round | the consumers a partial last round left out
+// The totals are wrapping unsigned 64-bit sums, so the two-level association gives the reference's bits; no thread walks more
+// than ~sqrt(rounds) entries.  The LDS kernel runs LAST and is the one place a verdict is stored and counted: for a topic of
+// the list it records the bits the global form left, for an over-limit topic that is NOT in the list (the device's offsets
+// disagree with the host's) UNCHECKED + kStatusShape -- every topic exactly once.
 #include <algorithm>
 
 #include "la_kernels.h"
@@ -43,9 +62,32 @@ static_assert(kVerifyMaxPartitions <= kNoIndex && kVerifyMaxConsumers <= kNoInde
 
 inline size_t up16(size_t x) { return (x + 15) & ~(size_t)15; }
 
+struct VerifyBig {              // one topic of the global form; every offset and size is the HOST's, inside [0, N] / [0, K]
+    int64_t p0, np, c0, nc;
+    int64_t wp, wc;             // what is verified: np, nc -- or 0, 0 for a topic the join cannot hold (skip: UNCHECKED)
+    int64_t rounds, chunk_rounds, n_chunks;      // ceil(wp / wc) rounds in n_chunks chunks of chunk_rounds ~ sqrt(rounds)
+    int64_t table0, part0, slot0, cons0, sum0;   // its regions: table slots, lag / kidx / before, slot, tot_last, chunk sums
+    int64_t step0[3];           // first workgroup step per domain (kDomPart / kDomCons / kDomPair), numbered through the topics
+    int32_t topic, bits;        // the table region has 1 << bits slots
+    int32_t skip, pad_;
+};
+
+struct VerifyWork {             // the global form's device memory
+    uint64_t* table;
+    int64_t *lag, *kidx, *before, *tot_last;
+    uint32_t* slot;
+    uint64_t* sums;
+    uint32_t* bits;             // [n_big] verdict bits, OR-ed with agent-scope atomics only when non-zero
+    const VerifyBig* big;       // ascending in topic
+    int32_t n_big;
+    int64_t steps[3];           // workgroup steps per domain
+};
+
 struct VerifyArgs {
     VerifyCall c;
     uint32_t* status;
+    VerifyWork g;               // n_big == 0: no topic went through the global form
+    int32_t large;              // LA_FLAG_VERIFY_LARGE: an over-limit topic outside the list is a shape error
     int32_t cap_p, cap_c;       // partitions / consumers of a topic the LDS request holds
     uint32_t off_lag, off_rank, off_slot, off_kidx, off_bits;      // byte offsets of the regions behind A
 };
@@ -129,8 +171,20 @@ __global__ __launch_bounds__(kVerifyThreads) void verify_kernel(VerifyArgs a) {
         const bool outside = p0 < 0 || p1 < p0 || p1 > c.n_partitions || c0 < 0 || c1 < c0 || c1 > c.n_consumers;
         const bool over_limit = !outside && (np > kVerifyMaxPartitions || nc > kVerifyMaxConsumers);
         const bool over_hint = !outside && !over_limit && (np > a.cap_p || nc > a.cap_c);
+        if (a.g.n_big > 0) {                        // a topic of the host's list: the global form has left its bits
+            int lo = 0, hi = a.g.n_big;
+            while (hi - lo > 1) {
+                const int mid = (lo + hi) >> 1;
+                if ((int64_t)a.g.big[mid].topic <= t) lo = mid;
+                else hi = mid;
+            }
+            if ((int64_t)a.g.big[lo].topic == t) {
+                if (tid == 0) record(c, tally, t, a.g.bits[lo]);
+                continue;
+            }
+        }
         if (outside || over_limit || over_hint) {   // nothing is read through such offsets
-            if (outside || over_hint) bad |= kStatusShape;
+            if (outside || over_hint || (over_limit && a.large)) bad |= kStatusShape;      // (the host's list would have held it)
             if (tid == 0) record(c, tally, t, kVerdictUnchecked);
             continue;
         }
@@ -262,6 +316,336 @@ __global__ __launch_bounds__(kVerifyThreads) void verify_kernel(VerifyArgs a) {
     if (bad) atomicOr(a.status, bad);
 }
 
+// ---- the global form -----------------------------------------------------------------------------------------------------------
+constexpr int kVgThreads = 256;
+constexpr int kVgPer = 4;                           // partitions / consumers of a thread per workgroup step
+constexpr int64_t kVgStep = (int64_t)kVgPer * kVgThreads;
+constexpr int64_t kVgPairStep = kVgThreads;         // (chunk, consumer) pairs of a step: one per thread, each walks a chunk's rounds
+constexpr uint32_t kNoPos = 0xFFFFFFFFu;            // slot: nobody (what the memset leaves)
+constexpr int kDomPart = 0, kDomCons = 1, kDomPair = 2;
+static_assert(kVerifyGlobalMaxPartitions < (int64_t)kNoPos, "32-bit positions inside a topic");
+
+struct VerifyGlobalArgs {
+    VerifyCall c;
+    uint32_t* status;
+    VerifyWork g;
+};
+
+__device__ __forceinline__ int big_of_step(const VerifyWork& g, int dom, int64_t step) {      // the last topic that starts at or before it
+    int lo = 0, hi = g.n_big;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (g.big[mid].step0[dom] <= step) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// G0 .. G5 of the file comment.  A step belongs to ONE topic, so its threads' bits are OR-ed per wavefront into that topic's word.
+template <int PHASE>
+__global__ __launch_bounds__(kVgThreads) void verify_global_kernel(VerifyGlobalArgs a) {
+    constexpr int kScope = __HIP_MEMORY_SCOPE_AGENT;
+    constexpr int kDomA = PHASE == 3 ? kDomCons : (PHASE == 4 ? kDomPair : kDomPart);      // the launch's first domain ...
+    constexpr int kDomB = PHASE == 0 || PHASE == 5 ? kDomCons : (PHASE == 2 ? kDomPair : -1);      // ... and its second, if any
+    const VerifyCall& c = a.c;
+    const VerifyWork& g = a.g;
+    const int tid = (int)threadIdx.x;
+    const int64_t steps_a = g.steps[kDomA], n_steps = steps_a + (kDomB >= 0 ? g.steps[kDomB >= 0 ? kDomB : kDomA] : 0);
+    uint32_t bad = 0;
+    for (int64_t step = blockIdx.x; step < n_steps; step += gridDim.x) {
+        const int dom = step < steps_a ? kDomA : kDomB;                        // workgroup-uniform, as all that follows from it
+        const int idx = big_of_step(g, dom, step < steps_a ? step : step - steps_a);
+        const VerifyBig b = g.big[idx];
+        const int64_t s = (step < steps_a ? step : step - steps_a) - b.step0[dom];
+        const int64_t P = b.wp, C = b.wc;
+        uint64_t* table = g.table + b.table0;
+        int64_t* lag = g.lag + b.part0;
+        int64_t* kidx = g.kidx + b.part0;
+        int64_t* before = g.before + b.part0;
+        uint32_t* slot = g.slot + b.slot0;
+        int64_t* tot_last = g.tot_last + b.cons0;
+        uint64_t* sums = g.sums + b.sum0;
+        const int32_t* rank = c.cons_rank + b.c0;
+        uint32_t v = 0;
+
+        if (dom == kDomPart) {
+            if (PHASE == 0 && s == 0 && tid == 0) {
+                if (b.skip) v |= kVerdictUnchecked;
+                if (c.part_off[b.topic] != b.p0 || c.part_off[b.topic + 1] != b.p0 + b.np || c.cons_off[b.topic] != b.c0 ||
+                    c.cons_off[b.topic + 1] != b.c0 + b.nc) {
+                    v |= kVerdictUnchecked;
+                    bad |= kStatusShape;
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < kVgPer; ++u) {
+                const int64_t i = s * kVgStep + u * kVgThreads + tid;
+                if (i >= P) continue;
+                if (PHASE == 0) {
+                    const uint32_t st = table_insert<kScope>(table, b.bits, c.pid[b.p0 + i], (int32_t)i);
+                    if (st) v |= kVerdictUnchecked;
+                    bad |= st & kStatusInternal;
+                } else if (PHASE == 1) {
+                    int32_t j = 0;
+                    const uint32_t st = table_lookup<kScope>(table, b.bits, c.out_pid[b.p0 + i], &j);
+                    int64_t l = 0;
+                    if (st) {
+                        v |= kVerdictIds;
+                        bad |= st & kStatusInternal;
+                    } else if (j >= 0 && (int64_t)j < P) {      // (the payload this topic's insert stored)
+                        l = lag_of(c, b.p0 + j);
+                    } else {
+                        v |= kVerdictIds;
+                        bad |= kStatusInternal;
+                    }
+                    lag[i] = l;
+                    const int32_t r = c.out_rank[b.p0 + i];
+                    int64_t k = -1;
+                    if (C == 0) {
+                        if (r != -1) v |= kVerdictOwner;
+                    } else {
+                        int64_t lo = 0, hi = C;     // first k with rank[k] >= r; the interval shrinks whatever the ranks hold
+                        while (lo < hi) {
+                            const int64_t mid = lo + ((hi - lo) >> 1);
+                            if (rank[mid] < r) lo = mid + 1;
+                            else hi = mid;
+                        }
+                        if (lo < C && rank[lo] == r) {
+                            k = lo;
+                            slot[(i / C) * C + lo] = (uint32_t)i;
+                        } else {
+                            v |= kVerdictOwner;
+                        }
+                    }
+                    kidx[i] = k;
+                } else if (PHASE == 2) {
+                    if (i + 1 < P) {
+                        const int64_t l0 = lag[i], l1 = lag[i + 1];
+                        if (!(l0 > l1) && (l0 != l1 || !(c.out_pid[b.p0 + i] < c.out_pid[b.p0 + i + 1]))) v |= kVerdictOrder;
+                    }
+                    const int64_t k = kidx[i];
+                    if (k >= 0 && k < C && slot[(i / C) * C + k] != (uint32_t)i) v |= kVerdictOwner;
+                } else if (PHASE == 5) {
+                    if (C == 0 || i + 1 >= P || (i + 1) % C == 0) continue;      // i closes its round
+                    if (kidx[i] < 0 || kidx[i + 1] < 0) continue;
+                    const int64_t b0 = before[i], b1 = before[i + 1];
+                    // (an owner that was found IS its consumer's rank)
+                    if (!(b0 < b1 || (b0 == b1 && c.out_rank[b.p0 + i] < c.out_rank[b.p0 + i + 1]))) v |= kVerdictGreedy;
+                }
+            }
+        } else if (dom == kDomCons) {
+            int64_t k_last = -1, b_last = 0;
+            int32_t r_last = 0;
+            if (PHASE == 5 && C > 0 && P % C != 0) {                            // (P > 0 then)
+                k_last = kidx[P - 1];
+                if (k_last >= 0 && k_last < C) {
+                    b_last = before[P - 1];
+                    r_last = rank[k_last];
+                } else {
+                    k_last = -1;
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < kVgPer; ++u) {
+                const int64_t k = s * kVgStep + u * kVgThreads + tid;
+                if (k >= C) continue;
+                if (PHASE == 0) {
+                    if (k + 1 < C && !(rank[k] < rank[k + 1])) v |= kVerdictUnchecked;
+                } else if (PHASE == 3) {
+                    uint64_t run = 0;
+                    for (int64_t ch = 0; ch < b.n_chunks; ++ch) {
+                        const uint64_t x = sums[ch * C + k];
+                        sums[ch * C + k] = run;
+                        run += x;
+                    }
+                    if (c.out_total && c.out_total[b.c0 + k] != (int64_t)run) v |= kVerdictTotals;
+                } else if (PHASE == 5) {
+                    if (k_last < 0 || slot[(b.rounds - 1) * C + k] != kNoPos) continue;
+                    const int64_t t0 = tot_last[k];
+                    if (!(t0 > b_last || (t0 == b_last && rank[k] > r_last))) v |= kVerdictGreedy;
+                }
+            }
+        } else {                                    // kDomPair: PHASE 2 sums a chunk, PHASE 4 walks it from the scanned sum
+            const int64_t q = s * kVgPairStep + tid;
+            if (q < b.n_chunks * C) {
+                const int64_t ch = q / C, k = q - ch * C;
+                const int64_t r0 = ch * b.chunk_rounds, r1 = r0 + b.chunk_rounds < b.rounds ? r0 + b.chunk_rounds : b.rounds;
+                uint64_t tot = PHASE == 4 ? sums[q] : 0;
+                for (int64_t r = r0; r < r1; ++r) {
+                    if (PHASE == 4 && r == b.rounds - 1) tot_last[k] = (int64_t)tot;
+                    const uint32_t i = slot[r * C + k];
+                    if (i == kNoPos || (int64_t)i >= P) continue;               // (only positions of this topic are ever stored)
+                    if (PHASE == 4) before[i] = (int64_t)tot;
+                    tot += (uint64_t)lag[i];
+                }
+                if (PHASE == 2) sums[q] = tot;
+            }
+        }
+
+        v = wave_or_u32(v);
+        if ((tid & (kWave - 1)) == 0 && v) __hip_atomic_fetch_or(g.bits + idx, v, __ATOMIC_RELAXED, kScope);
+    }
+    if (bad) atomicOr(a.status, bad);
+}
+
+// a x b and a + b in size_t; false: the result does not fit
+inline bool mul_ok(size_t a, size_t b, size_t* out) { return !__builtin_mul_overflow(a, b, out); }
+inline bool add_ok(size_t a, size_t b, size_t* out) { return !__builtin_add_overflow(a, b, out); }
+
+inline int64_t ceil_sqrt(int64_t x) {               // smallest r >= 1 with r r >= x
+    int64_t r = (int64_t)__builtin_sqrt((double)x);
+    if (r < 1) r = 1;
+    while (r * r < x) ++r;
+    while (r > 1 && (r - 1) * (r - 1) >= x) --r;
+    return r;
+}
+
+hipError_t grow_verify_device(void** p, size_t* cap, size_t bytes) {
+    if (bytes <= *cap) return hipSuccess;
+    if (*p) { (void)hipFree(*p); *p = nullptr; *cap = 0; }
+    size_t want = 0;
+    if (!add_ok(bytes, bytes / 4 + 256, &want)) return hipErrorOutOfMemory;
+    const hipError_t e = hipMalloc(p, want);
+    if (e != hipSuccess) { *p = nullptr; (void)hipGetLastError(); return hipErrorOutOfMemory; }
+    *cap = want;
+    return hipSuccess;
+}
+
+hipError_t verify_cus(int* out) {                   // compute units of the current device (asked once per device)
+    static std::atomic<int> s_cus[32];
+    int dev = 0, cus = 0;
+    hipError_t e;
+    if ((e = hipGetDevice(&dev)) != hipSuccess) return e;
+    const bool cached = dev >= 0 && dev < 32;
+    if (cached && (cus = s_cus[dev].load(std::memory_order_relaxed)) > 0) { *out = cus; return hipSuccess; }
+    if ((e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev)) != hipSuccess) return e;
+    if (cus < 1) cus = 1;
+    if (cached) s_cus[dev].store(cus, std::memory_order_relaxed);
+    *out = cus;
+    return hipSuccess;
+}
+
+template <int PHASE>
+hipError_t verify_global_launch(const VerifyGlobalArgs& a, int64_t steps, int cus, hipStream_t stream) {
+    if (steps <= 0) return hipSuccess;
+    const dim3 grid((unsigned)std::min<int64_t>(steps, (int64_t)cus * 8)), block(kVgThreads);
+    LA_LAUNCH((verify_global_kernel<PHASE>), grid, block, 0, stream, a);
+    return hipGetLastError();
+}
+
+// Lists the topics over the LDS limit from the host's offsets, takes their working memory and enqueues the global form.
+// Nothing is enqueued before every buffer is there.  n_big == 0 on return: the batch holds no such topic (nothing was touched).
+hipError_t verify_global_form(VerifyScratch& s, const VerifyCall& c, const int64_t* h_part_off, const int64_t* h_cons_off,
+                              uint32_t* status, hipStream_t stream, VerifyWork* out) {
+    hipError_t e;
+    const int64_t T = c.n_topics;
+    const auto is_big = [&](int64_t t) {
+        return h_part_off[t + 1] - h_part_off[t] > kVerifyMaxPartitions || h_cons_off[t + 1] - h_cons_off[t] > kVerifyMaxConsumers;
+    };
+    int64_t n_big = 0;
+    for (int64_t t = 0; t < T; ++t) n_big += is_big(t) ? 1 : 0;
+    *out = VerifyWork{};
+    if (n_big == 0) return hipSuccess;
+
+    size_t item_bytes = 0;
+    if (!mul_ok((size_t)n_big, sizeof(VerifyBig), &item_bytes)) return hipErrorOutOfMemory;
+    if (s.copied && (e = hipEventSynchronize(s.copied)) != hipSuccess) return e;      // the last call's copy has read h_items
+    if (item_bytes > s.h_items_cap) {
+        if (s.h_items) { (void)hipHostFree(s.h_items); s.h_items = nullptr; s.h_items_cap = 0; }
+        size_t want = 0;
+        if (!add_ok(item_bytes, item_bytes / 4 + 256, &want)) return hipErrorOutOfMemory;
+        if (hipHostMalloc(&s.h_items, want, hipHostMallocDefault) != hipSuccess) {
+            s.h_items = nullptr;
+            (void)hipGetLastError();
+            return hipErrorOutOfMemory;
+        }
+        s.h_items_cap = want;
+    }
+    if ((e = grow_verify_device(&s.d_items, &s.d_items_cap, item_bytes)) != hipSuccess) return e;
+    if (!s.copied && (e = hipEventCreateWithFlags(&s.copied, hipEventDisableTiming)) != hipSuccess) return e;
+
+    // regions, counted in elements; every sum is checked (a count that does not fit cannot be allocated either)
+    VerifyBig* items = static_cast<VerifyBig*>(s.h_items);
+    size_t n_table = 0, n_part = 0, n_slot = 0, n_cons = 0, n_sum = 0;
+    int64_t steps[3] = {0, 0, 0};
+    int64_t j = 0;
+    bool fits = true;
+    for (int64_t t = 0; t < T; ++t) {
+        if (!is_big(t)) continue;
+        VerifyBig& b = items[j++];
+        b = VerifyBig{};
+        b.topic = (int32_t)t;
+        b.p0 = h_part_off[t];
+        b.np = h_part_off[t + 1] - b.p0;
+        b.c0 = h_cons_off[t];
+        b.nc = h_cons_off[t + 1] - b.c0;
+        b.skip = b.np > kVerifyGlobalMaxPartitions ? 1 : 0;
+        b.wp = b.skip ? 0 : b.np;
+        b.wc = b.skip ? 0 : b.nc;
+        b.rounds = b.wc > 0 ? (b.wp + b.wc - 1) / b.wc : 0;
+        b.chunk_rounds = ceil_sqrt(b.rounds);
+        b.n_chunks = (b.rounds + b.chunk_rounds - 1) / b.chunk_rounds;
+        b.bits = ceil_log2(2 * b.wp);
+        b.table0 = (int64_t)n_table;
+        b.part0 = (int64_t)n_part;
+        b.slot0 = (int64_t)n_slot;
+        b.cons0 = (int64_t)n_cons;
+        b.sum0 = (int64_t)n_sum;
+        size_t slots = 0, pairs = 0;                // rounds x C < P + C; chunks x C
+        fits = fits && mul_ok((size_t)b.rounds, (size_t)b.wc, &slots) && mul_ok((size_t)b.n_chunks, (size_t)b.wc, &pairs) &&
+               add_ok(n_table, (size_t)1 << b.bits, &n_table) && add_ok(n_part, (size_t)b.wp, &n_part) &&
+               add_ok(n_slot, slots, &n_slot) && add_ok(n_cons, (size_t)b.wc, &n_cons) && add_ok(n_sum, pairs, &n_sum);
+        if (!fits) return hipErrorOutOfMemory;
+        b.step0[kDomPart] = steps[kDomPart];
+        b.step0[kDomCons] = steps[kDomCons];
+        b.step0[kDomPair] = steps[kDomPair];
+        steps[kDomPart] += std::max<int64_t>(1, (b.wp + kVgStep - 1) / kVgStep);      // (one at least: the offsets are compared there)
+        steps[kDomCons] += (b.wc + kVgStep - 1) / kVgStep;
+        steps[kDomPair] += ((int64_t)pairs + kVgPairStep - 1) / kVgPairStep;
+    }
+    // [table | lag | kidx | before | tot_last | sums : 8-byte words][slot | bits : 4-byte words]
+    size_t words8 = 0, words4 = 0, bytes8 = 0, bytes4 = 0, bytes = 0, three = 0;
+    fits = mul_ok(n_part, 3, &three) && add_ok(n_table, three, &words8) && add_ok(words8, n_cons, &words8) &&
+           add_ok(words8, n_sum, &words8) && add_ok(n_slot, (size_t)n_big, &words4) && mul_ok(words8, 8, &bytes8) &&
+           mul_ok(words4, 4, &bytes4) && add_ok(bytes8, bytes4, &bytes);
+    if (!fits) return hipErrorOutOfMemory;
+    if ((e = grow_verify_device(&s.work, &s.work_cap, bytes)) != hipSuccess) return e;
+    int cus = 0;
+    if ((e = verify_cus(&cus)) != hipSuccess) return e;
+
+    VerifyWork g{};
+    g.table = static_cast<uint64_t*>(s.work);
+    g.lag = reinterpret_cast<int64_t*>(g.table + n_table);
+    g.kidx = g.lag + n_part;
+    g.before = g.kidx + n_part;
+    g.tot_last = g.before + n_part;
+    g.sums = reinterpret_cast<uint64_t*>(g.tot_last + n_cons);
+    g.slot = reinterpret_cast<uint32_t*>(g.sums + n_sum);
+    g.bits = g.slot + n_slot;
+    g.big = static_cast<const VerifyBig*>(s.d_items);
+    g.n_big = (int32_t)std::min<int64_t>(n_big, 0x7FFFFFFF);      // (T is 32 bits wide)
+    for (int d = 0; d < 3; ++d) g.steps[d] = steps[d];
+
+    if ((e = hipMemcpyAsync(s.d_items, s.h_items, item_bytes, hipMemcpyHostToDevice, stream)) != hipSuccess) return e;
+    if ((e = hipEventRecord(s.copied, stream)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(g.table, 0, n_table * 8, stream)) != hipSuccess) return e;
+    if (n_slot && (e = hipMemsetAsync(g.slot, 0xFF, n_slot * 4, stream)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(g.bits, 0, (size_t)n_big * 4, stream)) != hipSuccess) return e;
+
+    VerifyGlobalArgs a{};
+    a.c = c;
+    a.status = status;
+    a.g = g;
+    if ((e = verify_global_launch<0>(a, steps[kDomPart] + steps[kDomCons], cus, stream)) != hipSuccess) return e;
+    if ((e = verify_global_launch<1>(a, steps[kDomPart], cus, stream)) != hipSuccess) return e;
+    if ((e = verify_global_launch<2>(a, steps[kDomPart] + steps[kDomPair], cus, stream)) != hipSuccess) return e;
+    if ((e = verify_global_launch<3>(a, steps[kDomCons], cus, stream)) != hipSuccess) return e;
+    if ((e = verify_global_launch<4>(a, steps[kDomPair], cus, stream)) != hipSuccess) return e;
+    if ((e = verify_global_launch<5>(a, steps[kDomPart] + steps[kDomCons], cus, stream)) != hipSuccess) return e;
+    *out = g;
+    return hipSuccess;
+}
+
 // Resident workgroups of the kernel for a workgroup size and its dynamic LDS, per device; one word per device:
 // LDS bytes << 40 | threads << 24 | workgroups.  It remembers the last request only (host arithmetic otherwise).
 hipError_t verify_resident(int threads, size_t lds, int* out) {
@@ -286,8 +670,21 @@ hipError_t verify_resident(int threads, size_t lds, int* out) {
 
 }  // namespace
 
-hipError_t verify_assignment_launch(const VerifyCall& c, uint32_t* status, hipStream_t stream) {
+void verify_scratch_release(VerifyScratch& s) {
+    if (s.copied) { (void)hipEventSynchronize(s.copied); (void)hipEventDestroy(s.copied); }
+    if (s.work) (void)hipFree(s.work);
+    if (s.d_items) (void)hipFree(s.d_items);
+    if (s.h_items) (void)hipHostFree(s.h_items);
+    s = VerifyScratch{};
+}
+
+hipError_t verify_assignment_launch(VerifyScratch* large, const VerifyCall& c, const int64_t* h_part_off,
+                                    const int64_t* h_cons_off, uint32_t* status, hipStream_t stream) {
     hipError_t e;
+    VerifyWork g{};
+    // the global form first: the LDS kernel behind it stores and counts the verdicts of its topics too
+    if (large && c.n_topics > 0 && (e = verify_global_form(*large, c, h_part_off, h_cons_off, status, stream, &g)) != hipSuccess)
+        return e;
     if (c.summary) {
         if ((e = hipMemsetAsync(c.summary, 0, 16, stream)) != hipSuccess) return e;
         if ((e = hipMemsetAsync(c.summary + 2, 0xFF, 16, stream)) != hipSuccess) return e;
@@ -299,6 +696,8 @@ hipError_t verify_assignment_launch(const VerifyCall& c, uint32_t* status, hipSt
     VerifyArgs a{};
     a.c = c;
     a.status = status;
+    a.g = g;
+    a.large = large ? 1 : 0;
     a.cap_p = (int32_t)cap_of(c.max_partitions_per_topic, kVerifyMaxPartitions);
     a.cap_c = (int32_t)cap_of(c.max_consumers_per_topic, kVerifyMaxConsumers);
     const VerifyLayout l = layout_for(a.cap_p, a.cap_c);
