@@ -573,7 +573,7 @@ int la_member_loads_device_on(la_ctx *ctx, int shard, int64_t n_partitions, cons
                               int64_t *d_unassigned, void *stream);
 
 /* Who moved between two rebalances (nothing in the reference computes it).  Both assignments are results of an assign call
- * over ONE layout (the same d_part_off; topics whose partition count changed are out of scope) -- each in its own assignment
+ * over ONE layout (the same d_part_off; for topics whose partition count changed see TWO LAYOUTS below) -- each in its own assignment
  * order, so the previous owner of an entry is found by a join on (topic, partition id), not by position.  With M = n_members,
  * for entry i of topic t of the current assignment:
  *   p = d_prev_member_rank[j] of the entry j of topic t of the previous assignment with d_prev_partition[j] == d_out_partition[i]
@@ -595,7 +595,35 @@ int la_member_loads_device_on(la_ctx *ctx, int shard, int64_t n_partitions, cons
  * from h_part_off, which is then required (LA_EINVAL without it).
  * At most one kernel launch with a hint within that limit, three otherwise (la_last_launches; memsets do not count).  The table
  * of the larger topics is a buffer of the shard's own (LA_ENOMEM when it cannot be had), so the results kept for
- * la_group_last_by_member stay valid.  Buffer contract as everywhere in this header. */
+ * la_group_last_by_member stay valid.  Buffer contract as everywhere in this header.
+ *
+ * TWO LAYOUTS (d_prev_part_off != NULL): the rebalance happened because topics gained partitions, appeared or were deleted, so
+ * the previous assignment has a layout of its own -- d_prev_part_off [T_prev+1] over N_prev entries of d_prev_partition /
+ * d_prev_member_rank.  Today's topic t is topic s = d_prev_topic[t] of it (t itself without a map, which needs T_prev == T);
+ * its previous segment is [prev_part_off[s], prev_part_off[s+1]), or empty when s == -1 (the topic is new).  Then
+ *   a current entry whose id has a previous entry in that segment is treated as above (d_prev_owner[i] = q, moved iff q != c);
+ *   a current entry whose id has none is ADDED: d_prev_owner[i] = LA_MOVES_NO_PREVIOUS, +1 to d_topic_added[t] and d_added[0],
+ *     +1 to d_member_gained[c] when c >= 0; it counts for neither d_topic_moved nor d_moved;
+ *   a previous entry j of the segment that no current id matched is REMOVED: +1 to d_topic_removed[t] and d_removed[0], +1 to
+ *     d_member_lost[q_j] when q_j >= 0 (q_j: its owner in today's ranks, mapped as above).
+ * So gained[r] counts what r holds now and did not hold before, lost[r] the reverse; with equal id sets every number is the
+ * one-layout call's and added = removed = 0.  A missing id is no error in this form.  la_sync reports as LA_EINVAL: a duplicate
+ * id inside either segment (also among the added ids, and in a new topic), a rank out of range as above, a d_prev_topic[t]
+ * outside [-1, T_prev); such an entry or topic is skipped and nothing is read or stored through it (a current entry with a bad
+ * rank is skipped before its id is looked up, so its previous entry is then counted as removed: the numbers of a call that
+ * ends in LA_EINVAL are unspecified, as above).  Not checked: no previous topic is named twice.
+ * A previous topic that no entry names is not looked at -- list a deleted topic today as a topic without partitions to have
+ * its partitions counted as removed (the assign call accepts such topics).  All nine outputs are overwritten, each may be
+ * NULL, all NULL is LA_EINVAL.  T == 0, N == 0 and N_prev == 0 are valid in any combination (N == 0: everything removed).
+ * Shape: the hint bounds the topics of BOTH layouts; a pair (t, s) is joined in LDS while max(P_t, P_prev_s) <= 4096 and a pair
+ * over a hint within that limit is LA_ESHAPE with nothing written for it.  With a larger hint the larger pairs are found on the
+ * host, from h_part_off, h_prev_part_off and (with d_prev_topic) h_prev_topic, which must equal the device arrays; LA_EINVAL
+ * at the call when one is missing, an offset array does not ascend from 0 to N / N_prev, or a map entry lies outside
+ * [-1, T_prev).  At most one launch with a hint within the limit, four otherwise (LDS form, insert, lookup, sweep).
+ *
+ * struct_size: 128 (the struct up to d_moved: one layout, nothing behind byte 128 is read) or sizeof(la_moves_args) of this
+ * header and above; anything else is LA_EINVAL.  With d_prev_part_off == NULL no field from n_prev_topics on is looked at. */
+#define LA_MOVES_NO_PREVIOUS (-2)
 typedef struct la_moves_args {
     int32_t struct_size;              /* sizeof(la_moves_args) of the caller's header */
     int32_t n_topics;                 /* T */
@@ -605,7 +633,7 @@ typedef struct la_moves_args {
     const int64_t *h_part_off;        /* host copy; required when the hint exceeds the one-workgroup limit */
     const int32_t *d_out_partition;   /* [N] current assignment (results of an assign call) */
     const int32_t *d_out_member_rank; /* [N] */
-    const int32_t *d_prev_partition;  /* [N] previous assignment, same layout */
+    const int32_t *d_prev_partition;  /* [N] previous assignment, same layout ([N_prev] with d_prev_part_off) */
     const int32_t *d_prev_member_rank;/* [N] */
     int32_t n_members;                /* M: ranks of the CURRENT membership */
     int32_t n_prev_members;           /* M_prev; read only when d_prev_rank_map != NULL */
@@ -615,6 +643,20 @@ typedef struct la_moves_args {
     int64_t *d_member_gained;         /* [M] or NULL */
     int64_t *d_member_lost;           /* [M] or NULL */
     int64_t *d_moved;                 /* [1] or NULL */
+    /* ---- two layouts; struct_size 128 ends here ---- */
+    int32_t n_prev_topics;            /* T_prev */
+    int32_t reserved;                 /* 0 */
+    int64_t n_prev_partitions;        /* N_prev = prev_part_off[T_prev]; d_prev_partition / d_prev_member_rank then hold N_prev entries */
+    const int64_t *d_prev_part_off;   /* [T_prev+1] layout of the PREVIOUS assignment.  NULL: one layout -- the call is exactly the
+                                         one above and no field from n_prev_topics on is looked at */
+    const int64_t *h_prev_part_off;   /* host copy; required where h_part_off is (hint beyond the one-workgroup limit) */
+    const int32_t *d_prev_topic;      /* [T] today's topic t is topic d_prev_topic[t] of the previous layout, -1: the topic is new.
+                                         NULL: identity (then T_prev must equal T) */
+    const int32_t *h_prev_topic;      /* host copy; required with d_prev_topic where h_part_off is, not looked at without it */
+    int64_t *d_topic_added;           /* [T] or NULL */
+    int64_t *d_topic_removed;         /* [T] or NULL */
+    int64_t *d_added;                 /* [1] or NULL */
+    int64_t *d_removed;               /* [1] or NULL */
 } la_moves_args;
 int la_assignment_moves_device(la_ctx *ctx, const la_moves_args *args, void *stream);
 /* The same on shard `shard` (buffers and stream on that shard's device; la_sync_on reports the errors).  Shards hold disjoint

@@ -39,6 +39,8 @@ LOADS_LDS_MAX_MEMBERS = 4095
 # kMovesLdsMaxMembers of csrc/la_kernels.h; results are the same, tests run both sides)
 MOVES_LDS_MAX_PARTITIONS = 4096
 MOVES_LDS_MAX_MEMBERS = 4096
+# la_assignment_moves_device with two layouts: d_prev_owner of a partition that has no previous entry (it was added)
+LA_MOVES_NO_PREVIOUS = -2
 # la_verify_assignment_device: d_topic_verdict[t] is 0 (certified) or a mask of these; a topic of more than VERIFY_MAX_PARTITIONS
 # partitions or VERIFY_MAX_CONSUMERS consumers reads LA_VERDICT_UNCHECKED (kVerifyMax* of csrc/la_kernels.h) unless the batch carries
 # LA_FLAG_VERIFY_LARGE: such topics then go through tables in device memory, up to VERIFY_GLOBAL_MAX_PARTITIONS partitions and any
@@ -123,6 +125,12 @@ class MovesArgs(ctypes.Structure):
         ("d_prev_rank_map", ctypes.c_void_p),
         ("d_prev_owner", ctypes.c_void_p), ("d_topic_moved", ctypes.c_void_p),
         ("d_member_gained", ctypes.c_void_p), ("d_member_lost", ctypes.c_void_p), ("d_moved", ctypes.c_void_p),
+        # two layouts (d_prev_part_off set); left at 0 / NULL the call is the one-layout form
+        ("n_prev_topics", ctypes.c_int32), ("reserved", ctypes.c_int32), ("n_prev_partitions", ctypes.c_int64),
+        ("d_prev_part_off", ctypes.c_void_p), ("h_prev_part_off", _i64p),
+        ("d_prev_topic", ctypes.c_void_p), ("h_prev_topic", ctypes.POINTER(ctypes.c_int32)),
+        ("d_topic_added", ctypes.c_void_p), ("d_topic_removed", ctypes.c_void_p),
+        ("d_added", ctypes.c_void_p), ("d_removed", ctypes.c_void_p),
     ]
 
 
@@ -667,7 +675,12 @@ class Context:
         owner of every entry in today's ranks (int32[N]), moved entries per topic (int64[T]), gained / lost per member
         (int64[M]) and the moved total (int64[1]); each output may be left out.  Enqueued on `stream`; sync() reports duplicate or
         missing ids, ranks out of range (LA_EINVAL) and topics over a hint within MOVES_LDS_MAX_PARTITIONS (LA_ESHAPE).
-        sharding.assignment_moves_numpy is the same on the host."""
+        sharding.assignment_moves_numpy is the same on the host.
+        With args.d_prev_part_off the previous assignment has a layout of its own (n_prev_topics, n_prev_partitions,
+        d_prev_topic: today's topic -> its previous topic or -1): a partition without a previous entry is ADDED
+        (d_prev_owner = LA_MOVES_NO_PREVIOUS, d_topic_added, d_added, gained), a previous entry nobody matched is REMOVED
+        (d_topic_removed, d_removed, lost), and a missing id is no error.  sharding.assignment_moves_layouts_numpy is that
+        form on the host."""
         fn = getattr(self._lib, "la_assignment_moves_device_on", None)
         if fn is None:
             raise LagAssignError(LA_EINVAL, "this liblagassign.so has no la_assignment_moves_device_on")

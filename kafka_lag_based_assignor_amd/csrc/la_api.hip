@@ -936,8 +936,80 @@ LA_API int la_member_loads_device_on(la_ctx* ctx, int shard, int64_t n_partition
     });
 }
 
-// Who moved between two assignments (la_moves.hip).  The global form's table is the shard's own buffer, not the assign scratch:
-// the results kept for la_group_last_by_member stay as they are.
+constexpr int kMovesArgsSizeOneLayout = 128;      // la_moves_args up to d_moved: what the struct was before the two-layout fields
+static_assert(offsetof(la_moves_args, n_prev_topics) == kMovesArgsSizeOneLayout, "the two-layout fields follow the one-layout struct");
+static_assert(LA_MOVES_NO_PREVIOUS == la::kMovesNoPrevious, "lagassign.h and la_kernels.h");
+
+// the fields both forms of la_assignment_moves_device share
+static la::MovesCall moves_call_of(const la_moves_args& g) {
+    la::MovesCall c{};
+    c.n_topics = g.n_topics;
+    c.n_members = g.n_members;
+    c.n_prev_members = g.d_prev_rank_map ? g.n_prev_members : g.n_members;
+    c.n_partitions = g.n_partitions;
+    c.max_partitions_per_topic = g.max_partitions_per_topic;
+    c.part_off = g.d_part_off;
+    c.out_partition = g.d_out_partition;
+    c.out_member_rank = g.d_out_member_rank;
+    c.prev_partition = g.d_prev_partition;
+    c.prev_member_rank = g.d_prev_member_rank;
+    c.map = g.d_prev_rank_map;
+    c.prev_owner = g.d_prev_owner;
+    c.topic_moved = g.d_topic_moved;
+    c.member_gained = g.d_member_gained;
+    c.member_lost = g.d_member_lost;
+    c.moved = g.d_moved;
+    return c;
+}
+
+// host copy of an offset array: from 0 to `total`, never descending
+static bool offsets_ascend(const int64_t* off, int64_t n, int64_t total) {
+    if (off[0] != 0 || off[n] != total) return false;
+    for (int64_t t = 0; t < n; ++t)
+        if (off[t + 1] < off[t]) return false;
+    return true;
+}
+
+// la_assignment_moves_device with d_prev_part_off: a layout each (la_moves_layouts.hip); sizes, members and "some output" checked
+static int moves_layouts(la_ctx* ctx, Shard& sh, const la_moves_args& g, hipStream_t stream) {
+    const int64_t T = g.n_topics, N = g.n_partitions, NP = g.n_prev_partitions;
+    if (g.n_prev_topics < 0 || NP < 0) return fail(ctx, LA_EINVAL, "negative size");
+    if (g.reserved != 0) return fail(ctx, LA_EINVAL, "la_moves_args.reserved must be 0");
+    if (!g.d_prev_topic && g.n_prev_topics != T) return fail(ctx, LA_EINVAL, "without d_prev_topic both layouts hold the same topics: n_prev_topics must equal n_topics");
+    if ((T == 0 && N != 0) || (g.n_prev_topics == 0 && NP != 0)) return fail(ctx, LA_EINVAL, "partitions without topics");
+    const bool work = T > 0 && (N > 0 || NP > 0);
+    if ((work && !g.d_part_off) || (N > 0 && (!g.d_out_partition || !g.d_out_member_rank)) ||
+        (NP > 0 && (!g.d_prev_partition || !g.d_prev_member_rank)))
+        return fail(ctx, LA_EINVAL, "null buffer");
+    const int32_t* h_prev_topic = g.d_prev_topic ? g.h_prev_topic : nullptr;      // it is the host copy of d_prev_topic, or nothing
+    if (g.max_partitions_per_topic > la::kMovesLdsMaxPartitions && work) {
+        // pairs beyond one workgroup's table are found on the host
+        if (!g.h_part_off || !g.h_prev_part_off || (g.d_prev_topic && !g.h_prev_topic))
+            return fail(ctx, LA_EINVAL, "h_part_off, h_prev_part_off and (with d_prev_topic) h_prev_topic are required when max_partitions_per_topic exceeds %lld", (long long)la::kMovesLdsMaxPartitions);
+        if (!offsets_ascend(g.h_part_off, T, N)) return fail(ctx, LA_EINVAL, "h_part_off must ascend from 0 to n_partitions");
+        if (!offsets_ascend(g.h_prev_part_off, g.n_prev_topics, NP)) return fail(ctx, LA_EINVAL, "h_prev_part_off must ascend from 0 to n_prev_partitions");
+        for (int64_t t = 0; h_prev_topic && t < T; ++t)
+            if (h_prev_topic[t] < -1 || h_prev_topic[t] >= g.n_prev_topics)
+                return fail(ctx, LA_EINVAL, "h_prev_topic[%lld] lies outside [-1, n_prev_topics)", (long long)t);
+    }
+    la::MovesLayoutsCall c{};
+    c.c = moves_call_of(g);
+    c.n_prev_topics = g.n_prev_topics;
+    c.n_prev_partitions = NP;
+    c.prev_part_off = g.d_prev_part_off;
+    c.prev_topic = g.d_prev_topic;
+    c.topic_added = g.d_topic_added;
+    c.topic_removed = g.d_topic_removed;
+    c.added = g.d_added;
+    c.removed = g.d_removed;
+    hipError_t e = la::assignment_moves_layouts_launch(sh.moves, c, g.h_part_off, g.h_prev_part_off, h_prev_topic,
+                                                       sh.lanes[0].d_status, stream);
+    return e != hipSuccess ? hip_fail(ctx, e, "assignment_moves: %s") : LA_OK;
+}
+
+// Who moved between two assignments (la_moves.hip; la_moves_layouts.hip when the previous one has a layout of its own).  The
+// global form's table is the shard's own buffer, not the assign scratch: the results kept for la_group_last_by_member stay as
+// they are.
 LA_API int la_assignment_moves_device(la_ctx* ctx, const la_moves_args* args, void* stream) {
     return la_assignment_moves_device_on(ctx, 0, args, stream);
 }
@@ -945,13 +1017,19 @@ LA_API int la_assignment_moves_device(la_ctx* ctx, const la_moves_args* args, vo
 LA_API int la_assignment_moves_device_on(la_ctx* ctx, int shard, const la_moves_args* args, void* stream) {
     return shard_entry<true>(ctx, shard, "exception in la_assignment_moves_device", [&](Shard& sh) -> int {
         if (!args) return fail(ctx, LA_EINVAL, "args is NULL");
-        if (args->struct_size < (int32_t)sizeof(la_moves_args)) return fail(ctx, LA_EINVAL, "la_moves_args.struct_size is %d, this library's is %d", (int)args->struct_size, (int)sizeof(la_moves_args));
-        const la_moves_args& g = *args;
+        // the struct has grown once: a caller built against the one-layout header says 128, and nothing behind that is read
+        if (args->struct_size != kMovesArgsSizeOneLayout && args->struct_size < (int32_t)sizeof(la_moves_args))
+            return fail(ctx, LA_EINVAL, "la_moves_args.struct_size is %d, this library takes %d or %d and above", (int)args->struct_size, kMovesArgsSizeOneLayout, (int)sizeof(la_moves_args));
+        la_moves_args g{};
+        memcpy(&g, args, args->struct_size == kMovesArgsSizeOneLayout ? (size_t)kMovesArgsSizeOneLayout : sizeof g);
+        const bool layouts = g.d_prev_part_off != nullptr;
         if (g.n_topics < 0 || g.n_partitions < 0 || g.n_members < 0) return fail(ctx, LA_EINVAL, "negative size");
         if (g.n_members > la::kMovesMaxMembers) return fail(ctx, LA_EINVAL, "n_members must be below 2^30");
         if (g.d_prev_rank_map && g.n_prev_members < 0) return fail(ctx, LA_EINVAL, "negative n_prev_members");
-        if (!g.d_prev_owner && !g.d_topic_moved && !g.d_member_gained && !g.d_member_lost && !g.d_moved)
+        if (!g.d_prev_owner && !g.d_topic_moved && !g.d_member_gained && !g.d_member_lost && !g.d_moved &&
+            !(layouts && (g.d_topic_added || g.d_topic_removed || g.d_added || g.d_removed)))
             return fail(ctx, LA_EINVAL, "every output is NULL");
+        if (layouts) return moves_layouts(ctx, sh, g, (hipStream_t)stream);
         if (g.n_topics == 0 && g.n_partitions != 0) return fail(ctx, LA_EINVAL, "partitions without topics");
         if (g.n_partitions > 0 && (!g.d_part_off || !g.d_out_partition || !g.d_out_member_rank || !g.d_prev_partition ||
                                    !g.d_prev_member_rank))
@@ -965,23 +1043,7 @@ LA_API int la_assignment_moves_device_on(la_ctx* ctx, int shard, const la_moves_
             for (int32_t t = 0; t < g.n_topics; ++t)
                 if (g.h_part_off[t + 1] < g.h_part_off[t]) return fail(ctx, LA_EINVAL, "offsets of topic %d decrease", t);
         }
-        la::MovesCall c{};
-        c.n_topics = g.n_topics;
-        c.n_members = g.n_members;
-        c.n_prev_members = g.d_prev_rank_map ? g.n_prev_members : g.n_members;
-        c.n_partitions = g.n_partitions;
-        c.max_partitions_per_topic = g.max_partitions_per_topic;
-        c.part_off = g.d_part_off;
-        c.out_partition = g.d_out_partition;
-        c.out_member_rank = g.d_out_member_rank;
-        c.prev_partition = g.d_prev_partition;
-        c.prev_member_rank = g.d_prev_member_rank;
-        c.map = g.d_prev_rank_map;
-        c.prev_owner = g.d_prev_owner;
-        c.topic_moved = g.d_topic_moved;
-        c.member_gained = g.d_member_gained;
-        c.member_lost = g.d_member_lost;
-        c.moved = g.d_moved;
+        const la::MovesCall c = moves_call_of(g);
         hipError_t e = la::assignment_moves_launch(sh.moves, c, g.h_part_off, sh.lanes[0].d_status, (hipStream_t)stream);
         return e != hipSuccess ? hip_fail(ctx, e, "assignment_moves: %s") : LA_OK;
     });

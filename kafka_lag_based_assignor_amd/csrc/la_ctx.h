@@ -306,7 +306,7 @@ inline int status_error(la_ctx* ctx, uint32_t st) {
     if (st & la::kStatusLoads)
         return fail(ctx, LA_EINVAL, "la_member_loads_device: a member rank outside [-1, n_members) or a consumer rank outside [0, n_members)");
     if (st & la::kStatusMoves)
-        return fail(ctx, LA_EINVAL, "la_assignment_moves_device: a duplicate partition id inside a topic, a current id without a previous one, or a rank out of range");
+        return fail(ctx, LA_EINVAL, "la_assignment_moves_device: a duplicate partition id inside a topic, a current id without a previous one (one layout), or a rank or d_prev_topic entry out of range");
     return fail(ctx, LA_ESHAPE, "a topic exceeds the batch's shape hint");
 }
 

@@ -54,7 +54,8 @@ constexpr uint32_t kStatusBounds = 64u;    // LA_FLAG_BOUNDS: a lag or a partiti
 constexpr uint32_t kStatusLoads = 128u;    // la_member_loads_device: a member rank outside [-1, M) / a consumer rank outside [0, M)
 
 constexpr uint32_t kStatusMoves = 256u;    // la_assignment_moves_device: a duplicate partition id inside a topic, a current id without a
-                                           // previous one, or a rank (previous, mapped or current) out of range
+                                           // previous one (one layout), a rank (previous, mapped or current) or a d_prev_topic
+                                           // entry (two layouts) out of range
 
 constexpr int32_t kTileNoDefer = 8;       // TileArgs::flags: the bounds prove that every tile packs -- no deferred list, no wide
                                           // launch; a tile that does not pack after all raises kStatusBounds
@@ -294,6 +295,7 @@ hipError_t member_loads_launch(int64_t n, const int32_t* member_rank, int64_t k,
 constexpr int64_t kMovesLdsMaxPartitions = 4096;
 constexpr int32_t kMovesLdsMaxMembers = 4096;
 constexpr int32_t kMovesMaxMembers = (1 << 30) - 1;     // a slot keeps owner + 2 in 31 bits next to its matched mark
+constexpr int32_t kMovesNoPrevious = -2;                // LA_MOVES_NO_PREVIOUS (lagassign.h): prev_owner of an added entry
 
 struct MovesScratch {           // of one shard, grown lazily: never the assign scratch (results kept on the device stay valid)
     void* table = nullptr;      // the global form's hash table
@@ -321,6 +323,23 @@ struct MovesCall {              // la_moves_args (lagassign.h), validated
 hipError_t assignment_moves_launch(MovesScratch& s, const MovesCall& c, const int64_t* h_part_off, uint32_t* status,
                                    hipStream_t stream);
 void moves_scratch_release(MovesScratch& s);
+
+// The same question when the two assignments have a layout each (la_moves_layouts.hip; la_moves_args with d_prev_part_off).
+struct MovesLayoutsCall {
+    MovesCall c;                    // as above; part_off / n_topics / n_partitions are TODAY's layout
+    int32_t n_prev_topics;
+    int64_t n_prev_partitions;      // prev_partition / prev_member_rank hold this many entries
+    const int64_t* prev_part_off;   // [n_prev_topics + 1]
+    const int32_t* prev_topic;      // [n_topics] today's topic -> its topic of the previous layout, -1: new; null: identity
+    int64_t *topic_added, *topic_removed, *added, *removed;      // outputs, each may be null
+};
+
+// Zeroes the outputs on `stream`, then at most one launch (hint within kMovesLdsMaxPartitions) or four (LDS form, and insert,
+// lookup and sweep of the global form for the (today, previous) pairs with a side over the limit, found from the host arrays,
+// which the caller has validated).  The table is `s.table`, as above.  Sets kStatusMoves / kStatusShape / kStatusInternal.
+hipError_t assignment_moves_layouts_launch(MovesScratch& s, const MovesLayoutsCall& c, const int64_t* h_part_off,
+                                           const int64_t* h_prev_part_off, const int32_t* h_prev_topic, uint32_t* status,
+                                           hipStream_t stream);
 
 // ---- certify an assignment (la_verify.hip) ---------------------------------------------------------------------------------
 // One workgroup verifies a topic in LDS: the id join (la_join.h), the topic's lags, its consumers' ranks and one slot per

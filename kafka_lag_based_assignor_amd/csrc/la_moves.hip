@@ -25,26 +25,15 @@
 //                boundary.  The table is zeroed by a memset on the stream in front of them.
 // Nothing is stored through a rank or an id: a rank out of range, a duplicate and a missing id raise kStatusMoves and the entry
 // is skipped.  Every access is one element wide, so a view that starts at any element of a larger buffer takes the same path.
-#include <algorithm>
-
-#include "la_kernels.h"
-#include "la_device.h"
-#include "la_join.h"
+#include "la_moves_shared.h"
 
 namespace la {
 
 namespace {
 
-constexpr int kMovesThreads = 256;
-constexpr int kMovesChunk = 4 * kMovesThreads;      // global form: entries of one workgroup step
-constexpr int kMovesMaxTables = 16;                 // copies of the bins ...
-constexpr int kMovesFewBins = 2048;                 // ... while all of them stay within this many counters (8 KiB)
-constexpr int64_t kMovesMaxBinned = 1ll << 32;      // entries of a call whose moves 32-bit bins can count without wrapping
 // table + one copy of the bins (stride made odd) + the topic's counter: what the LDS form asks for at most
 constexpr size_t kMovesMaxLdsBytes = 16 * (size_t)kMovesLdsMaxPartitions + 4 * (2 * (size_t)kMovesLdsMaxMembers + 1) + 8;
-static_assert((kMovesLdsMaxPartitions & (kMovesLdsMaxPartitions - 1)) == 0, "2 x the limit is the table of the largest topic");
 static_assert(kMovesMaxLdsBytes <= 160 * 1024, "table + bins fit one workgroup's LDS on gfx950");
-static_assert(2 * kMovesLdsMaxMembers + 1 >= kMovesFewBins, "one copy of the widest bins is the largest bin area");
 
 struct MovesBig {               // one topic of the global form
     int64_t p0, n_part;         // its entries
@@ -65,36 +54,6 @@ struct MovesArgs {
     int32_t n_big;
     int64_t n_chunks;
 };
-
-__device__ __forceinline__ void global_add(int64_t* p, uint64_t v) {
-    __hip_atomic_fetch_add((unsigned long long*)p, (unsigned long long)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += (uint32_t)__shfl_xor((int)v, d);
-    return v;
-}
-
-// previous rank -> that owner in today's ranks; false: a rank out of range (nothing is read or stored through it)
-__device__ __forceinline__ bool owner_today(const MovesCall& c, int32_t p, int32_t* q) {
-    const int32_t n_prev = c.map ? c.n_prev_members : c.n_members;
-    if (p < -1 || p >= n_prev) return false;
-    const int32_t r = p < 0 ? -1 : (c.map ? c.map[p] : p);
-    if (r < -1 || r >= c.n_members) return false;
-    *q = r;
-    return true;
-}
-
-// one previous entry into its topic's table; returns status bits
-template <int SCOPE>
-__device__ __forceinline__ uint32_t insert_entry(const MovesCall& c, uint64_t* table, int bits, int64_t i) {
-    const int32_t id = __builtin_nontemporal_load(c.prev_partition + i);
-    const int32_t p = __builtin_nontemporal_load(c.prev_member_rank + i);
-    int32_t q;
-    if (!owner_today(c, p, &q)) return kStatusMoves;
-    return table_insert<SCOPE>(table, bits, id, q);
-}
 
 // one current entry: its previous owner, prev_owner[i], the gained / lost counts; *moved += 1 when it moved; returns status bits
 template <int SCOPE, bool BINS>
@@ -117,22 +76,6 @@ __device__ __forceinline__ uint32_t lookup_entry(const MovesCall& c, uint64_t* t
         if (q >= 0 && c.member_lost) global_add(c.member_lost + q, 1);
     }
     return 0;
-}
-
-__device__ __forceinline__ void clear_bins(const MovesArgs& a, uint32_t* bins, int tid) {
-    for (int i = tid; i < a.tables * a.stride; i += kMovesThreads) bins[i] = 0;
-}
-
-// the workgroup's bins into the outputs: one 64-bit global atomic per non-zero bin (behind a barrier)
-__device__ __forceinline__ void flush_bins(const MovesArgs& a, const uint32_t* bins, int tid) {
-    const uint32_t m = (uint32_t)a.c.n_members;
-    for (uint32_t b = (uint32_t)tid; b < 2 * m; b += kMovesThreads) {
-        uint64_t s = 0;
-        for (int t = 0; t < a.tables; ++t) s += bins[(size_t)t * a.stride + b];
-        if (s == 0) continue;
-        if (b < m) { if (a.c.member_gained) global_add(a.c.member_gained + b, s); }
-        else if (a.c.member_lost) global_add(a.c.member_lost + (b - m), s);
-    }
 }
 
 // LDS: [table: 1 << table_bits words][bins: tables x stride counters][the topic's moved count]
@@ -235,54 +178,6 @@ __global__ __launch_bounds__(kMovesThreads) void moves_global_kernel(MovesArgs a
     if (bad) atomicOr(a.status, bad);
 }
 
-// copies of `bins` counters (stride: bins made odd, so that the copies start on different banks): as many as stay within
-// kMovesFewBins, a power of two up to kMovesMaxTables
-inline void tables_for(int64_t bins, int32_t* tables, int32_t* stride) {
-    const int64_t s = (bins < 1 ? 1 : bins) | 1;
-    int t = 1;
-    while (t * 2 <= kMovesMaxTables && (int64_t)t * 2 * s <= kMovesFewBins) t *= 2;
-    *tables = t;
-    *stride = (int32_t)s;
-}
-
-// Resident workgroups of a kernel for its dynamic LDS, per device; one word per (device, kernel): LDS bytes << 32 | workgroups.
-// It remembers the last LDS size only (a caller that alternates between hints asks the runtime again: host arithmetic).
-template <typename K>
-hipError_t moves_resident(K kernel, int form, size_t lds, int* out) {
-    static std::atomic<uint64_t> s_cache[32][6];
-    int dev = 0, cus = 0, per_cu = 0;
-    hipError_t e;
-    if ((e = hipGetDevice(&dev)) != hipSuccess) return e;
-    const bool cached = dev >= 0 && dev < 32;
-    if (cached) {
-        const uint64_t c = s_cache[dev][form].load(std::memory_order_relaxed);
-        if ((uint32_t)c != 0 && (c >> 32) == lds) { *out = (int)(uint32_t)c; return hipSuccess; }
-    }
-    if ((e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev)) != hipSuccess) return e;
-    if ((e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kMovesThreads, lds)) != hipSuccess) return e;
-    if (per_cu < 1) per_cu = 1;
-    if (cus < 1) cus = 1;
-    *out = cus * per_cu;
-    if (cached) s_cache[dev][form].store(((uint64_t)lds << 32) | (uint32_t)*out, std::memory_order_relaxed);
-    return hipSuccess;
-}
-
-inline int ceil_log2(int64_t x) {                  // smallest b with 2^b >= x, at least 1
-    int b = 1;
-    while (((int64_t)1 << b) < x) ++b;
-    return b;
-}
-
-hipError_t grow_device(void** p, size_t* cap, size_t bytes) {
-    if (bytes <= *cap) return hipSuccess;
-    if (*p) { (void)hipFree(*p); *p = nullptr; *cap = 0; }
-    const size_t want = bytes + bytes / 4 + 256;
-    const hipError_t e = hipMalloc(p, want);
-    if (e != hipSuccess) { *p = nullptr; return e; }
-    *cap = want;
-    return hipSuccess;
-}
-
 }  // namespace
 
 void moves_scratch_release(MovesScratch& s) {
@@ -331,15 +226,7 @@ hipError_t assignment_moves_launch(MovesScratch& s, const MovesCall& c, const in
         if (n_big > 0) {
             if (n_big > 0x7FFFFFFF) return hipErrorInvalidValue;
             const size_t item_bytes = (size_t)n_big * sizeof(MovesBig);
-            if (s.copied && (e = hipEventSynchronize(s.copied)) != hipSuccess) return e;      // the last call's copy has read h_items
-            if (item_bytes > s.h_items_cap) {
-                if (s.h_items) { (void)hipHostFree(s.h_items); s.h_items = nullptr; s.h_items_cap = 0; }
-                const size_t want = item_bytes + item_bytes / 4 + 256;
-                if ((e = hipHostMalloc(&s.h_items, want, hipHostMallocDefault)) != hipSuccess) { s.h_items = nullptr; return e; }
-                s.h_items_cap = want;
-            }
-            if ((e = grow_device(&s.d_items, &s.d_items_cap, item_bytes)) != hipSuccess) return e;
-            if (!s.copied && (e = hipEventCreateWithFlags(&s.copied, hipEventDisableTiming)) != hipSuccess) return e;
+            if ((e = moves_items_reserve(s, item_bytes)) != hipSuccess) return e;
             MovesBig* items = static_cast<MovesBig*>(s.h_items);
             int64_t slots = 0, chunks = 0, j = 0;
             for (int64_t t = 0; t < T; ++t) {

@@ -222,6 +222,98 @@ def assignment_moves_numpy(part_off, out_partition, out_member_rank, prev_partit
     return owner.astype(np.int32), topic_moved, gained, lost, int(moved.sum())
 
 
+MOVES_NO_PREVIOUS = -2          # LA_MOVES_NO_PREVIOUS: prev_owner of a partition that was added
+
+
+def prev_topic_map(prev_names, names):
+    """d_prev_topic of la_assignment_moves_device from the topic names of the two layouts -> int32[len(names)]: the index of each
+    of today's names among the previous names, -1 for a name that is new.  ValueError when a list names a topic twice."""
+    prev_names, names = list(prev_names), list(names)
+    index = {name: i for i, name in enumerate(prev_names)}
+    if len(index) != len(prev_names) or len(set(names)) != len(names):
+        raise ValueError("a topic is named twice")
+    return np.array([index.get(name, -1) for name in names], dtype=np.int32).reshape(len(names))
+
+
+def assignment_moves_layouts_numpy(part_off, out_partition, out_member_rank, prev_part_off, prev_partition, prev_member_rank,
+                                   n_members: int, prev_rank_map=None, prev_topic=None):
+    """la_assignment_moves_device with two layouts (d_prev_part_off) restated on the host -> (prev_owner int32[N],
+    topic_moved, topic_added, topic_removed int64[T], gained, lost int64[M], moved, added, removed int).  Today's topic t is
+    topic prev_topic[t] of the previous layout (-1: new; no map: t itself, both layouts then hold the same number of topics).
+    Entries are keyed by (today's topic, id) and both sides sorted; np.searchsorted finds each current key among the previous
+    ones.  A current entry with a previous one: prev_owner is that owner in today's ranks, moved iff it differs from the
+    current owner, counted as in assignment_moves_numpy.  Without one it is ADDED: prev_owner = MOVES_NO_PREVIOUS, it counts
+    for topic_added, added and gained[c] (c >= 0), not as moved.  A previous entry of a named topic that no current entry
+    matched is REMOVED: topic_removed, removed, lost[q] (q >= 0).  Previous topics that no entry of prev_topic names are not
+    looked at.  ValueError for what the device reports as LA_EINVAL: a duplicate id inside a segment, a rank out of range
+    (assignment_moves_numpy's rules, over the segments that are looked at), a map entry outside [-1, T_prev) -- and for a
+    previous topic named twice, which the device leaves to the caller.  The yardstick of the GPU tests."""
+    m = int(n_members)
+    po = np.asarray(part_off, dtype=np.int64).ravel()
+    ppo = np.asarray(prev_part_off, dtype=np.int64).ravel()
+    cur_id = np.asarray(out_partition, dtype=np.int64).ravel()
+    prev_id = np.asarray(prev_partition, dtype=np.int64).ravel()
+    c = np.asarray(out_member_rank, dtype=np.int64).ravel()
+    p = np.asarray(prev_member_rank, dtype=np.int64).ravel()
+    for off in (po, ppo):
+        if off.size < 1 or off[0] != 0 or (np.diff(off) < 0).any():
+            raise ValueError("an offset array does not ascend from 0")
+    if m < 0:
+        raise ValueError("n_members < 0")
+    t, n, t_prev, n_prev = po.size - 1, int(po[-1]), ppo.size - 1, int(ppo[-1])
+    if not (cur_id.size == c.size == n and prev_id.size == p.size == n_prev):
+        raise ValueError("the assignment arrays must hold part_off[T] / prev_part_off[T_prev] entries")
+    if prev_topic is None:
+        if t_prev != t:
+            raise ValueError("without prev_topic both layouts hold the same number of topics")
+        s = np.arange(t, dtype=np.int64)
+    else:
+        s = np.asarray(prev_topic, dtype=np.int64).ravel()
+        if s.size != t or (t and (s.min() < -1 or s.max() >= t_prev)):
+            raise ValueError("prev_topic must hold T entries inside [-1, T_prev)")
+    named = s[s >= 0]
+    if np.unique(named).size != named.size:
+        raise ValueError("a previous topic is named twice")
+    # the previous entries that are looked at, under today's topic numbers
+    today_of = np.full(t_prev, -1, dtype=np.int64)
+    today_of[named] = np.flatnonzero(s >= 0)
+    prev_topic_of_entry = today_of[np.repeat(np.arange(t_prev, dtype=np.int64), np.diff(ppo))]
+    seen = prev_topic_of_entry >= 0
+    b_topic, b_id, p = prev_topic_of_entry[seen], prev_id[seen], p[seen]
+    if prev_rank_map is None:
+        m_prev, q = m, p
+    else:
+        rank_map = np.asarray(prev_rank_map, dtype=np.int64).ravel()
+        m_prev = rank_map.size
+    if p.size and (p.min() < -1 or p.max() >= m_prev):
+        raise ValueError("a previous member rank lies outside [-1, n_prev_members)")
+    if prev_rank_map is not None:
+        q = np.where(p < 0, -1, rank_map[np.maximum(p, 0)]) if m_prev else p
+    if (q.size and (q.min() < -1 or q.max() >= m)) or (n and (c.min() < -1 or c.max() >= m)):
+        raise ValueError("a mapped previous rank or a current member rank lies outside [-1, n_members)")
+    a_topic = np.repeat(np.arange(t, dtype=np.int64), np.diff(po))
+    a_key = (a_topic << 32) | (cur_id & 0xFFFFFFFF)
+    b_key = (b_topic << 32) | (b_id & 0xFFFFFFFF)
+    by_prev = np.argsort(b_key, kind="stable")
+    b_sorted = b_key[by_prev]
+    for keys in (np.sort(a_key), b_sorted):
+        if (keys[1:] == keys[:-1]).any():
+            raise ValueError("a partition id appears twice inside a topic")
+    at = np.minimum(np.searchsorted(b_sorted, a_key), max(b_sorted.size - 1, 0))
+    hit = (b_sorted[at] == a_key) if b_sorted.size else np.zeros(n, dtype=bool)
+    owner = np.full(n, MOVES_NO_PREVIOUS, dtype=np.int64)
+    owner[hit] = q[by_prev[at[hit]]]
+    matched = np.zeros(b_sorted.size, dtype=bool)
+    matched[by_prev[at[hit]]] = True
+    moved = hit & (owner != c)
+    added = ~hit
+    count = lambda idx, size: np.bincount(idx, minlength=size).astype(np.int64)[:size]
+    gained = count(c[(moved | added) & (c >= 0)], m)
+    lost = count(owner[moved & (owner >= 0)], m) + count(q[~matched & (q >= 0)], m)
+    return (owner.astype(np.int32), count(a_topic[moved], t), count(a_topic[added], t), count(b_topic[~matched], t), gained, lost,
+            int(moved.sum()), int(added.sum()), int((~matched).sum()))
+
+
 VERDICT_IDS, VERDICT_ORDER, VERDICT_OWNER, VERDICT_GREEDY, VERDICT_TOTALS, VERDICT_UNCHECKED = 1, 2, 4, 8, 16, 32
 
 

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Time la_assignment_moves_device against a restatement in torch ops on the same device arrays.
 
-    python tools/moves_probe.py [--topics 100000 --partitions 256 --consumers 32 --launches 20 --windows 5] [--out FILE]
+    python tools/moves_probe.py [--topics 100000 --partitions 256 --consumers 32 --launches 20 --windows 5] [--layouts] [--out FILE]
 
 The layout is T topics x P partitions x C consumers (the bench's target shape by default).  The library assigns it several
 times with every lag redrawn; consecutive assignments are the (previous, current) pairs, in enough resident copies that a call
@@ -14,6 +14,11 @@ Prints the median and the spread (min .. max) of both sides in microseconds per 
 per partition, 4 B written for prev_owner), its streaming floor at 8 TB/s and the fraction of it the library reaches, and whether
 the library is not slower than torch.  Both sides' results are compared bit for bit first.  Exit status 1 when the results
 differ or the library is slower.  Needs a GPU: there is nothing to fall back to.
+
+--layouts adds a leg for the two-layout form (d_prev_part_off): 1 % of the topics are grown by 16 partitions and assigned again,
+and that assignment is joined against a previous one over the ungrown layout.  It is timed in the same windows next to the
+one-layout call on the same previous arrays and checked against sharding.assignment_moves_layouts_numpy; its time is a record,
+no threshold hangs on it.
 """
 import argparse
 import ctypes
@@ -37,6 +42,7 @@ def main():
     ap.add_argument("--consumers", type=int, default=32)
     ap.add_argument("--launches", type=int, default=20)
     ap.add_argument("--windows", type=int, default=5)
+    ap.add_argument("--layouts", action="store_true", help="also time the two-layout form with 1 %% of the topics grown by 16")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
 
@@ -118,6 +124,58 @@ def main():
         lo = torch.bincount(own[mv & (own >= 0)], minlength=m)
         return own, tm, g, lo, mv.sum()
 
+    grown = None
+    if args.layouts:
+        # today's layout: every 100th topic has 16 more partitions; assigned once, joined against each resident previous copy
+        from kafka_lag_based_assignor_amd import sharding
+        sizes = np.full(t, p, dtype=np.int64)
+        sizes[::100] += 16
+        g_off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        g_n = int(g_off[-1])
+        g_pid = (np.arange(g_n, dtype=np.int64) - np.repeat(g_off[:-1], sizes)).astype(np.int32)
+        d_g_off, d_g_pid = torch.from_numpy(g_off).to(dev), torch.from_numpy(g_pid).to(dev)
+        g_lag = torch.from_numpy(rng.integers(0, 1 << 40, g_n, dtype=np.int64)).to(dev)
+        g_out = (torch.empty(g_n, dtype=torch.int32, device=dev), torch.empty(g_n, dtype=torch.int32, device=dev))
+        b = N.DeviceBatch()
+        b.n_topics, b.reset_mode, b.algo, b.flags = t, N.LA_RESET_LATEST, N.LA_ALGO_AUTO, 0
+        b.n_partitions, b.n_consumers = g_n, k
+        b.max_partitions_per_topic, b.max_consumers_per_topic = p + 16, c
+        b.d_part_off, b.d_partition_id, b.d_lag = d_g_off.data_ptr(), d_g_pid.data_ptr(), g_lag.data_ptr()
+        b.d_cons_off, b.d_cons_rank = d_cons_off.data_ptr(), d_cons.data_ptr()
+        b.d_out_partition, b.d_out_member_rank, b.d_out_total_lag = g_out[0].data_ptr(), g_out[1].data_ptr(), None
+        b.h_part_off, b.h_cons_off = g_off.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), h_co
+        torch.cuda.synchronize()
+        ctx.assign_batch_device(b, stream)
+        ctx.sync(stream)
+        del g_lag
+        g_owner = torch.empty(g_n, dtype=torch.int32, device=dev)
+        g_topic = [torch.empty(t, dtype=torch.int64, device=dev) for _ in range(3)]
+        g_counts = torch.empty(3, dtype=torch.int64, device=dev)
+        g_gl = (torch.empty(m, dtype=torch.int64, device=dev), torch.empty(m, dtype=torch.int64, device=dev))
+        g = N.MovesArgs()
+        g.n_topics, g.n_partitions, g.max_partitions_per_topic = t, g_n, p + 16
+        g.d_part_off, g.n_members = d_g_off.data_ptr(), m
+        g.d_out_partition, g.d_out_member_rank = g_out[0].data_ptr(), g_out[1].data_ptr()
+        g.n_prev_topics, g.n_prev_partitions, g.d_prev_part_off = t, n, d_part_off.data_ptr()
+        g.d_prev_owner, g.d_topic_moved, g.d_topic_added, g.d_topic_removed = [x.data_ptr() for x in [g_owner] + g_topic]
+        g.d_member_gained, g.d_member_lost = g_gl[0].data_ptr(), g_gl[1].data_ptr()
+        g.d_moved, g.d_added, g.d_removed = [g_counts.data_ptr() + 8 * i for i in range(3)]
+
+        def grown(i):
+            pp, pr = sets[i % copies][1]
+            g.d_prev_partition, g.d_prev_member_rank = pp.data_ptr(), pr.data_ptr()
+            ctx.assignment_moves_device(g, stream)
+
+        grown(0)
+        g_launches = ctx.last_launches()
+        ctx.sync(stream)
+        exp = sharding.assignment_moves_layouts_numpy(g_off, g_out[0].cpu().numpy(), g_out[1].cpu().numpy(), part_off,
+                                                      sets[0][1][0].cpu().numpy(), sets[0][1][1].cpu().numpy(), m)
+        got = [g_owner] + g_topic + list(g_gl)
+        g_same = all(np.array_equal(a.cpu().numpy(), e) for a, e in zip(got, exp[:6])) and g_counts.cpu().tolist() == list(exp[6:])
+        g_bytes = 8 * g_n + 8 * n + 4 * g_n
+        del exp
+
     lib_call(0)
     launches = ctx.last_launches()
     ctx.sync(stream)
@@ -140,9 +198,14 @@ def main():
         for i in range(2 * copies):
             call(i)
     torch.cuda.synchronize()
-    t_lib, t_torch = [], []
+    t_lib, t_torch, t_grown = [], [], []
+    if grown:
+        for i in range(2 * copies):
+            grown(i)
     for w in range(args.windows):
         t_lib.append(window(lib_call, w * args.launches))
+        if grown:
+            t_grown.append(window(grown, w * args.launches))
         t_torch.append(window(torch_call, w * args.launches))
     ctx.sync(stream)
     lib_med, torch_med = float(np.median(t_lib)), float(np.median(t_torch))
@@ -154,6 +217,15 @@ def main():
         "it (%.2f TB/s); library not slower than torch: %s"
         % (lib_med, min(t_lib), max(t_lib), launches, torch_med, min(t_torch), max(t_torch), "equal" if same else "DIFFER",
            100.0 * share, floor_us, floor_us / lib_med, set_bytes / lib_med * 1e6 / 1e12, "yes" if not_slower else "NO"))
+    if grown:
+        g_med = float(np.median(t_grown))
+        say("two layouts (%d of %d topics grown by 16, N = %d against N_prev = %d): %.1f us per call (min %.1f .. max %.1f; %d "
+            "kernel launch(es)), %.2f x the one-layout call in the same windows; %d added, %d removed, %d moved; results %s; %d "
+            "bytes per call, %.2f TB/s"
+            % (len(range(0, t, 100)), t, g_n, n, g_med, min(t_grown), max(t_grown), g_launches, g_med / lib_med,
+               int(g_counts[1]), int(g_counts[2]), int(g_counts[0]), "equal the host restatement" if g_same else "DIFFER",
+               g_bytes, g_bytes / g_med * 1e6 / 1e12))
+        same = same and g_same
     ctx.close()
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
