@@ -172,6 +172,16 @@ def _one_topic(P, C, lag, seed):
                           np.array([0, C], np.int64), ranks, P, C)
 
 
+# ---- one topic with the given lags (large path: the rounds kernel's forms; the packing limit of every greedy form) ----------------
+def _topic_with_lags(lag, c, seed):
+    rng = np.random.default_rng(seed)
+    p = lag.size
+    lag = np.ascontiguousarray(lag, np.int64)
+    return synth.Workload("narrow", 1, np.array([0, p], np.int64), rng.permutation(p).astype(np.int32), np.zeros(p, np.int64),
+                          lag.copy(), np.zeros(p, np.int64), lag, np.array([0, c], np.int64),
+                          np.sort(rng.choice(3 * c + 5, c, replace=False)).astype(np.int32), p, c)
+
+
 # ---- LA_FLAG_WIRE_OUT: the all-gather's wire elements straight from the assignment kernels ------------------
 def _wire_call(ctx, w, fmt, bounds, latest=False, flags=0, hint=None):
     import torch
@@ -292,5 +302,5 @@ def shifts_for(pattern, names):
     return {k: SHIFTS[(i * 2 + 1) % 3 if i % 2 else i % 3] for i, k in enumerate(names)}
 
 
-__all__ = ['ROOT', '_expected', '_workload', '_pinned', '_batch_of', '_device_call', '_same3', '_sort_topic', '_pinned_copy', '_grouped_expect', '_one_topic', '_wire_call',
+__all__ = ['ROOT', '_expected', '_workload', '_pinned', '_batch_of', '_device_call', '_same3', '_sort_topic', '_pinned_copy', '_grouped_expect', '_one_topic', '_topic_with_lags', '_wire_call',
            'GUARD_BYTES', 'SENTINEL', 'SHIFTS', 'guard_pattern', 'guard_violation', 'Guarded', 'shifts_for']

@@ -12,6 +12,7 @@ from kafka_lag_based_assignor_amd import _native as N
 from kafka_lag_based_assignor_amd import synth
 from oracle import oracle
 from round_form import round_form as _round_form
+import packing_cases
 
 pytestmark = pytest.mark.gpu
 
@@ -208,13 +209,15 @@ def test_tile_packed_boundary(ctx, p, c, pid_bits):
     cap_bits = int(np.ceil(np.log2(p)))
     pid_bits = pid_bits or cap_bits
     lb = min(63 - pid_bits, 57 - cap_bits)
+    # ("brim": every lag within 4 096 of lag_hi -- the lag field of every record and the totals of every bin filled to the top)
     for lag_hi in ((1 << lb) - 1, 1 << lb, (1 << lb) + 12345):
-        w = _uniform_batch(pid_bits * 1000 + p, 40, p, c, lag_hi, (1 << pid_bits) - 1, lag_lo=lag_hi // 2)
-        exp = oracle.assign_flat(w.part_off, w.partition_id, w.lag, w.cons_off, w.cons_rank)
-        for algo in (N.LA_ALGO_AUTO, N.LA_ALGO_ROUNDS_WIDE):
-            got = _run_device(ctx, w, algo, use_lag=True)
-            for g, e, what in zip(got, exp, ("partition order", "member", "totals")):
-                np.testing.assert_array_equal(g, e, err_msg="%s lag_hi=%d algo %d" % (what, lag_hi, algo))
+        for lag_lo in (lag_hi // 2, lag_hi - 4095):
+            w = _uniform_batch(pid_bits * 1000 + p, 40, p, c, lag_hi, (1 << pid_bits) - 1, lag_lo=lag_lo)
+            exp = oracle.assign_flat(w.part_off, w.partition_id, w.lag, w.cons_off, w.cons_rank)
+            for algo in (N.LA_ALGO_AUTO, N.LA_ALGO_ROUNDS_WIDE):
+                got = _run_device(ctx, w, algo, use_lag=True)
+                for g, e, what in zip(got, exp, ("partition order", "member", "totals")):
+                    np.testing.assert_array_equal(g, e, err_msg="%s lag_hi=%d lag_lo=%d algo %d" % (what, lag_hi, lag_lo, algo))
 
 
 def test_tile_packed_negative_id_or_lag_falls_back(ctx):
@@ -1052,12 +1055,16 @@ def test_block_one_wave_rounds_at_the_packing_limit(ctx):
             rng = np.random.default_rng(lag_bits * 131 + c)
             lag = rng.integers(0, 1 << lag_bits, p).astype(np.int64)
             lag[0] = (1 << lag_bits) - 1
+            # "brim": every lag within 4 096 of the top, so the totals fill their field to its last usable bit (packing_cases.py)
+            brim = packing_cases.brim(p, c, n_c, lag_bits + round_bits + idx_bits, lag_bits * 131 + c)
+            assert int(brim.max()) == (1 << lag_bits) - 1 and int(brim.min()) >= (1 << lag_bits) - 4096
             pid = rng.permutation(p).astype(np.int32)
             ranks = np.arange(c, dtype=np.int32)
-            exp = oracle.assign_flat([0, p], pid, lag, [0, c], ranks)
-            got = ctx.assign_batch_lags([0, p], pid, lag, [0, c], ranks)
-            for g, e, what in zip(got, exp, ("partition order", "member", "totals")):
-                np.testing.assert_array_equal(g, e, err_msg="%s p=%d c=%d lag_bits=%d" % (what, p, c, lag_bits))
+            for kind, lag in (("spread", lag), ("brim", brim)):
+                exp = oracle.assign_flat([0, p], pid, lag, [0, c], ranks)
+                got = ctx.assign_batch_lags([0, p], pid, lag, [0, c], ranks)
+                for g, e, what in zip(got, exp, ("partition order", "member", "totals")):
+                    np.testing.assert_array_equal(g, e, err_msg="%s p=%d c=%d lag_bits=%d %s" % (what, p, c, lag_bits, kind))
 
 
 def test_block_one_wave_rounds_many_topics(ctx):

@@ -173,15 +173,7 @@ def test_bounds_rule_radix_passes_out_and_a_broken_bound_is_an_error(ctx, p, c, 
 
 
 # ---- the narrow form of what the rounds kernel reads and writes (round 6: rounds_io, la_large.hip) ---------------------------------
-def _topic_with_lags(lag, c, seed):
-    rng = np.random.default_rng(seed)
-    p = lag.size
-    lag = np.ascontiguousarray(lag, np.int64)
-    return synth.Workload("narrow", 1, np.array([0, p], np.int64), rng.permutation(p).astype(np.int32), np.zeros(p, np.int64),
-                          lag.copy(), np.zeros(p, np.int64), lag, np.array([0, c], np.int64),
-                          np.sort(rng.choice(3 * c + 5, c, replace=False)).astype(np.int32), p, c)
-
-
+# (_topic_with_lags: gpu_helpers.py)
 @pytest.mark.parametrize("p,c,top", [
     (8192 * 5, 8192, (1 << 32) - 1),      # consumers fill every slot, full rounds only, the largest lag that still fits 32 bits
     (8192 * 5, 8192, 1 << 32),            # one bit more: the 64-bit form
