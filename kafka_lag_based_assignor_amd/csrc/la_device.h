@@ -238,4 +238,37 @@ __device__ __forceinline__ int wave_max_i32(int v) {
     return v;
 }
 
+// ---- reductions whose result is wanted as a wave-uniform (scalar) value --------------------------------------------------
+// wave_max_i32 above goes through LDS: six dependent ds_bpermute_b32, each waited for.  Where the result only steers
+// wave-uniform control flow, the forms below stay in the VALU / SALU.  Every lane of the wavefront must be active.
+
+// OR over the whole wavefront: four DPP steps inside each row of 16 lanes, then one v_readlane per row and scalar ORs.
+__device__ __forceinline__ uint32_t wave_or_u32_uniform(uint32_t v) {
+    v |= shfl_xor<1>(v);
+    v |= shfl_xor<2>(v);
+    v |= shfl_xor<4>(v);
+    v |= shfl_xor<8>(v);
+    return (uint32_t)__builtin_amdgcn_readlane((int)v, 0) | (uint32_t)__builtin_amdgcn_readlane((int)v, 16) |
+           (uint32_t)__builtin_amdgcn_readlane((int)v, 32) | (uint32_t)__builtin_amdgcn_readlane((int)v, 48);
+}
+
+// Maximum over the wavefront of a value that is the same in all L lanes of a group: one v_readlane per group (its first
+// lane), scalar max.
+template <int L>
+__device__ __forceinline__ int wave_max_of_groups_i32(int v) {
+    int m = __builtin_amdgcn_readlane(v, 0);
+#pragma unroll
+    for (int g = 1; g < kWave / L; ++g) {
+        const int x = __builtin_amdgcn_readlane(v, g * L);
+        m = x > m ? x : m;
+    }
+    return m;
+}
+
+// bits of the largest of the wavefront's non-negative 64-bit values, given the OR of them all (the widest value has the
+// OR's top bit); 64 when any is negative, 0 when all are zero
+__device__ __forceinline__ int bits_of_or_u64(uint32_t hi_or, uint32_t lo_or) {
+    return hi_or ? 64 - __builtin_clz(hi_or) : (lo_or ? 32 - __builtin_clz(lo_or) : 0);
+}
+
 }  // namespace la

@@ -350,6 +350,13 @@ __device__ __forceinline__ uint64_t p64_of_prev_lane(const P64& r) {
     return ((uint64_t)hi << 32) | lo;
 }
 
+// the record of lane + 1 (lane 63 reads zero)
+__device__ __forceinline__ uint64_t p64_of_next_lane(const P64& r) {
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)r.lo, 0x130, 0xF, 0xF, false);   // wave_shl:1
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)r.hi, 0x130, 0xF, 0xF, false);
+    return ((uint64_t)hi << 32) | lo;
+}
+
 // every group of the wavefront ascending already?  (wavefront-uniform answer)
 __device__ __forceinline__ bool lanes_in_order_p64(const P64& r, int gl) {
     // The shift is a cross-lane operation: EVERY lane executes it, before any lane-dependent condition.  (Written as

@@ -9,10 +9,13 @@
 // carries 64/L topics, a 256-thread workgroup 4x that.  Each lane holds E partition
 // records in registers (L*E >= partitions of the topic, L >= consumers of the topic).
 //
+//   0. topics    the wavefront's 64/L + 1 words of part_off and of cons_off: scalar loads at a wave-uniform address for a plain
+//                batch's full wavefront (fetch_desc_uniform), indexed per-lane loads for topic lists and the last wavefront.
 //   1. load      committed / end / partition id, 16 B per lane per array, unconditional and clamped, all
 //                issued back to back; `begin` only where there is no committed offset; lag in registers.
 //   2. format    per wavefront: packed 64-bit records if ids and lags are narrow enough (kernel 1), else
-//                the tile is deferred to the wide-record kernel (kernel 2).
+//                the tile is deferred to the wide-record kernel (kernel 2).  The widths are those of the OR of all ids / all
+//                lags, reduced in DPP + v_readlane (la_device.h): the packed path makes no LDS round trip to agree on anything.
 //   3. sort      32-bit keys (top bits of the record, id as tie-break) through a bitonic network whose steps across
 //                lanes are a DPP move + v_med3_u32 (la_sort32.h); records fetched from the LDS slice by the key's
 //                index and CHECKED to be strictly ascending; the full 64-bit network only if the check fails.  No HBM.
@@ -373,7 +376,7 @@ __device__ __forceinline__ void sort_into_slice(uint64_t* slice, int gl, P64 (&r
     }
     {
         const uint64_t x = p64_value(got[E - 1]);
-        const uint64_t y = ((uint64_t)(uint32_t)__shfl_down((int)got[0].hi, 1) << 32) | (uint32_t)__shfl_down((int)got[0].lo, 1);
+        const uint64_t y = p64_of_next_lane(got[0]);                      // (a DPP wave shift, every lane: no LDS trip)
         bad |= (gl != L - 1) && (x >= y) && (FULL || y != ~0ull);
     }
     wave_lds_fence();
@@ -408,7 +411,7 @@ __device__ __forceinline__ void greedy_rounds_tile(P64& bin, uint64_t* slice, in
             bool mirrored = false;
             if constexpr (LC == L) {
                 const uint64_t mine = p64_value(bin);
-                const uint64_t prev = ((uint64_t)(uint32_t)__shfl_up((int)bin.hi, 1) << 32) | (uint32_t)__shfl_up((int)bin.lo, 1);
+                const uint64_t prev = p64_of_prev_lane(bin);
                 const bool bad = (C != L) || (gl > 0 && !((prev >> 6) > (mine >> 6)));
                 if (__builtin_amdgcn_ballot_w64(bad) == 0) {
                     bin.lo = shfl_mirror<L>(bin.lo);
@@ -450,11 +453,12 @@ __device__ __forceinline__ void assign_packed(const TileArgs& a, uint64_t* slice
 
     P64 bin = p64_from((gl < C) ? (uint64_t)gl : ~0ull);
     const int rounds = (C > 0) ? (P + C - 1) / C : 0;
-    int max_rounds = __builtin_amdgcn_readfirstlane(wave_max_i32(rounds));
+    // rounds and C are the same in all L lanes of a group: their wave maxima are maxima over one lane per group
+    int max_rounds = wave_max_of_groups_i32<L>(rounds);
     if constexpr (kAblate == 1 || kAblate == 3) max_rounds = 0;
     if constexpr (kAblate >= 10) max_rounds = max_rounds < kAblate - 10 ? max_rounds : kAblate - 10;   // lab: cap the rounds
     // the widest consumer list among this wavefront's topics picks the network (wavefront-uniform)
-    const int c_max = __builtin_amdgcn_readfirstlane(wave_max_i32(C));
+    const int c_max = wave_max_of_groups_i32<L>(C);
     bool done = false;
     if constexpr (L > 4) if (!done && c_max <= 4) { greedy_rounds_tile<L, 4>(bin, slice, P, C, gl, sh, lag_max, pid_mask, max_rounds); done = true; }
     if constexpr (L > 8) if (!done && c_max <= 8) { greedy_rounds_tile<L, 8>(bin, slice, P, C, gl, sh, lag_max, pid_mask, max_rounds); done = true; }
@@ -677,6 +681,33 @@ __device__ __forceinline__ DescWords fetch_desc(const TileArgs& a, int64_t t, in
     return w;
 }
 
+// The same words for a plain batch (no topic_list) and a wavefront whose kGroupsPerWave topics all exist: the
+// kGroupsPerWave + 1 consecutive words of each array lie at a wave-uniform address (`t` must be wave-uniform), so they
+// come through the scalar data cache -- not queued in the vector memory pipeline behind the neighbours' streaming loads --
+// and each group selects its own.  Nothing past part_off[n_topics] / cons_off[n_topics] is read: (t + 1) * kGroupsPerWave
+// <= n_topics is the caller's condition.  The arrays are only read by this launch (constant address space).
+template <int L, int E>
+__device__ __forceinline__ DescWords fetch_desc_uniform(const TileArgs& a, int64_t t, int grp) {
+    constexpr int G = TileCfg<L, E>::kGroupsPerWave;
+    typedef const int64_t __attribute__((address_space(4))) * ConstWords;
+    const ConstWords po = (ConstWords)(uintptr_t)a.part_off + t * G;
+    const ConstWords co = (ConstWords)(uintptr_t)a.cons_off + t * G;
+    int64_t pw[G + 1], cw[G + 1];
+#pragma unroll
+    for (int k = 0; k <= G; ++k) { pw[k] = po[k]; cw[k] = co[k]; }
+    DescWords w;
+    w.exists = true;
+    w.p0 = pw[0]; w.p1 = pw[1];
+    w.c0 = cw[0]; w.c1 = cw[1];
+#pragma unroll
+    for (int g = 1; g < G; ++g) {
+        const bool mine = grp >= g;
+        w.p0 = mine ? pw[g] : w.p0; w.p1 = mine ? pw[g + 1] : w.p1;
+        w.c0 = mine ? cw[g] : w.c0; w.c1 = mine ? cw[g + 1] : w.c1;
+    }
+    return w;
+}
+
 template <int L, int E, typename IDX = int64_t>
 __device__ __forceinline__ TopicDescT<IDX> make_desc(const TileArgs& a, const DescWords& w, int gl) {
     using Cfg = TileCfg<L, E>;
@@ -694,6 +725,16 @@ __device__ __forceinline__ TopicDescT<IDX> make_desc(const TileArgs& a, const De
 
 template <int L, int E, typename IDX = int64_t>
 __device__ __forceinline__ TopicDescT<IDX> load_desc(const TileArgs& a, int64_t t, int64_t n_tiles, int grp, int gl) {
+    return make_desc<L, E, IDX>(a, fetch_desc<L, E>(a, t, n_tiles, grp), gl);
+}
+
+// load_desc for a wave-uniform tile index `t` < n_tiles (the packed kernel: one tile per wavefront).  topic_list batches and
+// the last, partly filled wavefront keep the indexed per-lane loads; so does everything about a bogus descriptor (make_desc).
+template <int L, int E, typename IDX = int64_t>
+__device__ __forceinline__ TopicDescT<IDX> load_desc_uniform(const TileArgs& a, int64_t t, int64_t n_tiles, int grp, int gl) {
+    constexpr int G = TileCfg<L, E>::kGroupsPerWave;
+    if (!a.topic_list && (t + 1) * G <= a.n_topics)                       // (wave-uniform)
+        return make_desc<L, E, IDX>(a, fetch_desc_uniform<L, E>(a, t, grp), gl);
     return make_desc<L, E, IDX>(a, fetch_desc<L, E>(a, t, n_tiles, grp), gl);
 }
 
@@ -725,12 +766,10 @@ __device__ __forceinline__ void packed_tile(const TileArgs& a, const TopicDescT<
         uint64_t lag_or = 0;
 #pragma unroll
         for (int v = 0; v < E; ++v) { id_or |= (uint32_t)pid[v]; lag_or |= (uint64_t)lag[v]; }
-        id_or = (uint32_t)__builtin_amdgcn_readfirstlane((int)wave_or_u32(id_or));
+        id_or = wave_or_u32_uniform(id_or);
         sh = 32 - __builtin_clz(id_or | 1u);                             // 1..32 (32: a negative id)
-        // bits of the wavefront's largest lag (64: a negative lag)
-        const uint32_t hi = (uint32_t)(lag_or >> 32), lo = (uint32_t)lag_or;
-        const int my_bits = hi ? 64 - __builtin_clz(hi) : (lo ? 32 - __builtin_clz(lo) : 0);
-        lbw = __builtin_amdgcn_readfirstlane(wave_max_i32(my_bits));
+        // bits of the wavefront's largest lag (64: a negative lag): those of the OR of all lags
+        lbw = bits_of_or_u64(wave_or_u32_uniform((uint32_t)(lag_or >> 32)), wave_or_u32_uniform((uint32_t)lag_or));
         int lim = 63 - sh;
         if (lim > 57 - Cfg::kLog2Cap) lim = 57 - Cfg::kLog2Cap;
         fits = sh < 32 && lbw <= lim;                                    // wave-uniform
@@ -800,7 +839,7 @@ __global__ __launch_bounds__(256) LA_WPE_ATTR void wave_tile_packed_kernel(TileA
     __shared__ int32_t rank_lds[Cfg::kTopicsPerBlock * L];
 
     const int lane = threadIdx.x & (kWave - 1);
-    const int wave = threadIdx.x >> 6;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));      // wave-uniform, and known to be
     const int gl = lane & (L - 1);            // lane within group
     const int grp = lane / L;                 // group within wave
     uint64_t* slice = lds + (wave * Cfg::kGroupsPerWave + grp) * Cfg::kSlots;
@@ -818,14 +857,14 @@ __global__ __launch_bounds__(256) LA_WPE_ATTR void wave_tile_packed_kernel(TileA
         if (blockIdx.x == 0 && threadIdx.x == 0) *a.defer_count_next = 0;
         // the single-launch form may carry a tail (a small rebalance's lists and completion word): every wavefront stays to the end
         if (tile < n_tiles) {
-            const TopicDescT<IDX> cur = load_desc<L, E, IDX>(a, tile, n_tiles, grp, gl);
+            const TopicDescT<IDX> cur = load_desc_uniform<L, E, IDX>(a, tile, n_tiles, grp, gl);
             packed_tile<L, E, IDX, true, false>(a, cur, slice, rank_tab, tile, gl, lane);
         }
         if (a.tail.enabled) tile_tail(a.tail, a.status);                 // (kernel-uniform)
         return;
     }
     if (tile >= n_tiles) return;
-    const TopicDescT<IDX> cur = load_desc<L, E, IDX>(a, tile, n_tiles, grp, gl);
+    const TopicDescT<IDX> cur = load_desc_uniform<L, E, IDX>(a, tile, n_tiles, grp, gl);
     // every topic of this wavefront fills its tile exactly: the form without clamps, validity selects and sentinels
     // (the single-launch form of small batches keeps to the general one: it carries the wide code already)
     if constexpr (!INLINE_WIDE) {
