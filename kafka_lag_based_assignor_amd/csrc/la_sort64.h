@@ -357,23 +357,157 @@ __device__ __forceinline__ uint64_t p64_of_next_lane(const P64& r) {
     return ((uint64_t)hi << 32) | lo;
 }
 
-// every group of the wavefront ascending already?  (wavefront-uniform answer)
-__device__ __forceinline__ bool lanes_in_order_p64(const P64& r, int gl) {
-    // The shift is a cross-lane operation: EVERY lane executes it, before any lane-dependent condition.  (Written as
-    // `gl > 0 && p64_of_prev_lane(r) > ...` the DPP moves run only in lanes with gl > 0, and a lane whose source -- the
-    // first lane of a group -- is masked off reads `old` = 0: "in order" whatever the bins are.  Fifty-two parity tests
-    // said so.)
-    const uint64_t prev = p64_of_prev_lane(r);
-    const bool bad = (gl > 0) & (prev > p64_value(r));
-    return __builtin_amdgcn_ballot_w64(bad) == 0;
-}
-
 // One record per lane (consumer bins), ascending over each group of L lanes.
 template <int L, bool VO = false>
 __device__ __forceinline__ void bitonic_sort_lanes_p64(P64& rec) {
     P64 r1[1] = {rec};
     merge_p64<L, 1, 2, true, VO>(r1);
     rec = r1[0];
+}
+
+// ---- bins that are NEARLY in order: neighbour exchanges instead of the network ------------------------------------------
+// From the third round on the bins are (ascending totals) + (descending lags) with a heavy-tailed lag list: a few bins a
+// few places from home (the 256 x 32 Zipf target: 1-4 descents, displacement <= 4 in rounds 3-7).  An odd-even
+// transposition pass moves a bin one place for 4 (even pairs) or 6 (odd pairs) VALU and ONE hop through VCC; the 32-lane
+// network is 60 VALU and 15 hops whatever its input.  All of it is wave-uniform, written like the steps above; the
+// counts and the A/B are in profiles/tile_settle_rounds.txt, the replay that predicts them is tools/settle_model.py.
+
+// lane masks over groups of L lanes: every lane but the last of its group / the odd lanes but the last of their group
+constexpr uint64_t first_lanes_of_groups(int l) {
+    uint64_t m = 0;
+    for (int i = 0; i < 64; i += l) m |= 1ull << i;
+    return m;
+}
+template <int L>
+struct GroupLanes {
+    static_assert(L == 2 || L == 4 || L == 8 || L == 16 || L == 32 || L == 64, "bad group width");
+    static constexpr uint64_t kNotLast = ~(first_lanes_of_groups(L) << (L - 1));
+    static constexpr uint64_t kOddNotLast = 0xAAAAAAAAAAAAAAAAull & ~(first_lanes_of_groups(L) << (L - 1));
+};
+
+// The descents of every group as a lane mask (wavefront-uniform): bit i set = lane i's record is above lane i+1's, same
+// group.  Zero = every group ascending already.  The shift is a cross-lane operation: EVERY lane executes it, and the
+// group's last lane is taken out afterwards, in the SALU.  (Written as `gl > 0 && p64_of_prev_lane(r) > ...` the DPP
+// moves run only in lanes with gl > 0, and a lane whose source -- the first lane of a group -- is masked off reads
+// `old` = 0: "in order" whatever the bins are.  Fifty-two parity tests said so.)  The records may come straight from
+// compiler-written code: two wait states first.  The compare is next - mine through v_sub_co_u32_dpp: the *rev
+// subtracts do not turn a DPP operand into the subtrahend -- v_subrev_co_u32_dpp D, vcc, A, B gave A[shifted] - B on the
+// chip, as v_sub does (tools/dpp_lab.hip), and "mine - prev" written with it called descending bins ordered.
+template <int L>
+__device__ __forceinline__ uint64_t lane_descents_p64(const P64& r) {
+    uint32_t t;
+    uint64_t m;
+    asm volatile(LA_PAD2
+                 "v_sub_co_u32_dpp %1, vcc, %2, %2 wave_shl:1" LA_DPP_TAIL " bound_ctrl:0\n\t"          // lo[lane+1] - lo
+                 "v_subb_co_u32_dpp %1, vcc, %3, %3, vcc wave_shl:1" LA_DPP_TAIL " bound_ctrl:0\n\t"    // vcc = next < mine
+                 "s_and_b64 %0, vcc, %4"
+                 : "=&s"(m), "=&v"(t)
+                 : "v"(r.lo), "v"(r.hi), "s"(GroupLanes<L>::kNotLast)
+                 : "vcc", "scc");
+    return m;
+}
+
+// The passes are separate statements, and between two statements the compiler may copy the record to other registers
+// (it does, where the branches of the stop test meet): every pass starts with the two wait states its first DPP read needs
+// after such a copy.  (One wait state is not enough exactly where a wave shift crosses a 16-lane row: lanes 15, 31 and 47
+// read the old value; tools/check_dpp_hazards.py checks the generated code.)
+
+// Even pass: pairs (2k, 2k+1) -- the step of cmpx_same_xor<1> -- and whether any pair exchanged (unique keys: the lower
+// lane of a pair took its partner's record; a pair of equal sentinels exchanges nothing).
+__device__ __forceinline__ bool settle_even_pass_p64(P64& r) {
+    uint32_t t;
+    uint64_t swapped;
+    asm volatile(LA_PAD2
+                 "v_sub_co_u32_dpp %2, vcc, %0, %0 quad_perm:[1,0,3,2]" LA_DPP_TAIL "\n\t"
+                 "v_subb_co_u32_dpp %2, vcc, %1, %1, vcc quad_perm:[1,0,3,2]" LA_DPP_TAIL "\n\t"
+                 "s_xor_b64 vcc, vcc, %4\n\t"
+                 "v_cndmask_b32_dpp %0, %0, %0, vcc quad_perm:[1,0,3,2]" LA_DPP_TAIL "\n\t"
+                 "v_cndmask_b32_dpp %1, %1, %1, vcc quad_perm:[1,0,3,2]" LA_DPP_TAIL "\n\t"
+                 "s_andn2_b64 %3, %4, vcc"
+                 : "+v"(r.lo), "+v"(r.hi), "=&v"(t), "=&s"(swapped)
+                 : "s"(KeepMin<1>::value)
+                 : "vcc", "scc");
+    return swapped != 0;
+}
+
+// Odd pass: pairs (2k+1, 2k+2) inside each group of L lanes, partners through the wave shifts of p64_of_next_lane /
+// p64_of_prev_lane (they cross the 16-lane rows; EXEC is full, every lane executes them).  ONE compare serves both lanes
+// of a pair: "next < mine" on the odd lane i is "mine < prev" on lane i+1, so the even lanes' mask is the odd lanes'
+// shifted by one lane in the SALU.  The odd-lane mask leaves out the last lane of every group (and its shift therefore
+// the first): no record crosses a group boundary.  Both selects read the neighbours' ORIGINAL records: the result is
+// built in other registers (n) and `r` is only read.  Returns whether any pair exchanged.
+template <int L>
+__device__ __forceinline__ bool settle_odd_pass_p64(P64& r) {
+    uint32_t t;
+    P64 n;
+    uint64_t swapped;
+    asm volatile(LA_PAD2
+                 "v_sub_co_u32_dpp %0, vcc, %4, %4 wave_shl:1" LA_DPP_TAIL " bound_ctrl:0\n\t"           // lo[lane+1] - lo
+                 "v_subb_co_u32_dpp %0, vcc, %5, %5, vcc wave_shl:1" LA_DPP_TAIL " bound_ctrl:0\n\t"     // vcc = next < mine
+                 "s_and_b64 %3, vcc, %6\n\t"                                                            // odd lanes that take next
+                 "s_not_b64 vcc, %3\n\t"
+                 "v_cndmask_b32_dpp %1, %4, %4, vcc wave_shl:1" LA_DPP_TAIL " bound_ctrl:0\n\t"          // n = vcc ? mine : next
+                 "v_cndmask_b32_dpp %2, %5, %5, vcc wave_shl:1" LA_DPP_TAIL " bound_ctrl:0\n\t"
+                 "s_lshl_b64 vcc, %3, 1\n\t"                                                            // even lanes that take prev
+                 "s_not_b64 vcc, vcc\n\t"
+                 "v_cndmask_b32_dpp %1, %4, %1, vcc wave_shr:1" LA_DPP_TAIL " bound_ctrl:0\n\t"          // n = vcc ? n : prev
+                 "v_cndmask_b32_dpp %2, %5, %2, vcc wave_shr:1" LA_DPP_TAIL " bound_ctrl:0"
+                 : "=&v"(t), "=&v"(n.lo), "=&v"(n.hi), "=&s"(swapped)
+                 : "v"(r.lo), "v"(r.hi), "s"(GroupLanes<L>::kOddNotLast)
+                 : "vcc", "scc");
+    r = n;
+    return swapped != 0;
+}
+
+// Settle thresholds (repeated in tools/settle_model.py and tests/test_tile_settle_gpu.py): try when no group has more than
+// kSettleMaxDescents descents, give up after kSettleMaxPairs (even, odd) pairs.  -DLA_SETTLE_ROUNDS=0: the network always.
+#ifndef LA_SETTLE_ROUNDS
+#define LA_SETTLE_ROUNDS 1
+#endif
+#ifndef LA_SETTLE_D
+#define LA_SETTLE_D 4
+#endif
+#ifndef LA_SETTLE_K
+#define LA_SETTLE_K 4
+#endif
+constexpr bool kSettleRounds = LA_SETTLE_ROUNDS != 0;
+constexpr int kSettleMaxDescents = LA_SETTLE_D;
+constexpr int kSettleMaxPairs = LA_SETTLE_K;
+
+// the largest number of descents any group of L lanes has
+template <int L>
+__device__ __forceinline__ int max_group_descents(uint64_t desc) {
+    int most = 0;
+    if constexpr (L == 64) {
+        most = __builtin_popcountll(desc);
+    } else {
+#pragma unroll
+        for (int g = 0; g < 64; g += L) {
+            const int n = __builtin_popcountll((desc >> g) & ((1ull << L) - 1));
+            most = n > most ? n : most;
+        }
+    }
+    return most;
+}
+
+// Bins with the descents `desc` (lane_descents_p64) ascending over each group of L lanes, LC of them live: the order the
+// network gives, bit for bit (live keys are unique, sentinels equal and behind every live bin).  A pass that exchanges
+// nothing after a pass of the other parity has run leaves every neighbour pair in order: sorted, stop.  (`desc` is zero
+// only in a build without kSkipSortedRounds: one pair runs and finds nothing to do.)
+template <int L, int LC>
+__device__ __forceinline__ void settle_lanes_p64(P64& bin, uint64_t desc) {
+    if constexpr (kSettleRounds && LC >= 32) {
+        if (max_group_descents<L>(desc) <= kSettleMaxDescents) {
+            (void)settle_even_pass_p64(bin);
+            if (!settle_odd_pass_p64<L>(bin)) return;
+#pragma unroll
+            for (int p = 1; p < kSettleMaxPairs; ++p) {
+                if (!settle_even_pass_p64(bin)) return;
+                if (!settle_odd_pass_p64<L>(bin)) return;
+            }
+        }
+    }
+    bitonic_sort_lanes_p64<LC>(bin);
 }
 
 // ---- (d) one greedy round of a one-wavefront topic, as ONE statement ---------------------------------------------------

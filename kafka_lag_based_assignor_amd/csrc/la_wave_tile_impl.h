@@ -394,15 +394,17 @@ __device__ __forceinline__ void sort_into_slice(uint64_t* slice, int gl, P64 (&r
 // LC = lanes the bins' network spans: the group width L, or less when every topic of the wavefront has at most LC
 // consumers (a 1 000-partition topic with 3 consumers sits in a 64-lane group; its 334 rounds then sort 4 lanes,
 // 3 steps, instead of 64 lanes, 21 steps).  Lanes >= C hold the all-ones sentinel, so any LC >= C sorts the same.
-// Rounds whose bins are in ascending order already skip their sort (lanes_in_order_p64, la_sort64.h: one DPP wave shift
-// per dword and one 64-bit compare): all-zero lags, a Zipf tail (the second round of the 100 000 x 256 x 32 target),
-// topics with few consumers or few distinct lags.
+// Rounds whose bins are in ascending order already skip their sort (lane_descents_p64, la_sort64.h: one 64-bit subtract
+// through a DPP wave shift): all-zero lags, a Zipf tail (the second round of the 100 000 x 256 x 32 target), topics with
+// few consumers or few distinct lags.  From the third round on, bins with only a few descents are settled by neighbour
+// exchanges instead of the network (settle_lanes_p64: rounds 3-7 of the target).
 template <int L, int LC>
 __device__ __forceinline__ void greedy_rounds_tile(P64& bin, uint64_t* slice, int P, int C, int gl, int sh,
                                                    uint64_t lag_max, uint32_t pid_mask, int max_rounds) {
     for (int q = 0; q < max_rounds; ++q) {
         // round 0 starts sorted: all totals 0, indices ascending
-        if (q >= 1 && kSkipSortedRounds && lanes_in_order_p64(bin, gl)) {
+        const uint64_t desc = q >= 1 ? lane_descents_p64<L>(bin) : 0;   // (wavefront-uniform)
+        if (q >= 1 && kSkipSortedRounds && desc == 0) {
             // nothing to sort
         } else if (q == 1) {
             // After round 0 consumer k holds the k-th largest lag: if those lags are STRICTLY descending over
@@ -421,7 +423,7 @@ __device__ __forceinline__ void greedy_rounds_tile(P64& bin, uint64_t* slice, in
             }
             if (!mirrored) bitonic_sort_lanes_p64<LC>(bin);
         } else if (q > 1) {
-            bitonic_sort_lanes_p64<LC>(bin);
+            settle_lanes_p64<L, LC>(bin, desc);
         }
         const int s = q * C + gl;
         if (gl < C && s < P) {
