@@ -260,6 +260,7 @@ const char *la_last_error(const la_ctx *ctx);
  *                la_assignment_moves_device / la_assignment_moves_device_on (who moved between two rebalances);
  *                la_verify_assignment_device / la_verify_assignment_device_on (certify an assignment);
  *                la_cooperative_adjust_device (the cooperative form of a rebalance);
+ *                la_cooperative_round_device / la_cooperative_round (that form and every member's list of it in one call);
  *                a shim detects them by symbol lookup (dlsym / getattr) instead of by version */
 #define LA_VERSION 500
 int la_version(void);
@@ -807,6 +808,53 @@ typedef struct la_coop_args {
     int64_t *d_summary;               /* [6] or NULL */
 } la_coop_args;
 int la_cooperative_adjust_device(la_ctx *ctx, const la_coop_args *args, void *stream);
+
+/* The cooperative round in one call: la_cooperative_adjust_device AND the lists a cooperative assignor hands back -- every
+ * member's list of the ADJUSTED assignment.
+ *   adjust             exactly as for la_cooperative_adjust_device: the same inputs, the same eight outputs, bit for bit what
+ *                      that call writes, every one of them still optional -- here all eight may be NULL, the lists are outputs
+ *                      too.  adjust.struct_size is not looked at (the outer struct_size covers the whole struct).
+ *   member_off, grouped_topic, grouped_partition
+ *                      what la_group_by_member_device writes for (d_part_off, d_out_partition, the adjusted ranks, M): member
+ *                      r's list is [member_off[r], member_off[r+1]); the withheld entries and those of topics without consumers
+ *                      sit before member_off[0].  So the lists of round n can be the owned arrays of round n + 1 as they lie.
+ *                      The lists do not need adjust.d_coop_member_rank: they are the same when it is NULL.  N < 2^31.
+ * Errors and hostile input as for la_cooperative_adjust_device: the same conditions are LA_EINVAL / LA_ESHAPE from la_sync,
+ * nothing is read through an offset, a bad entry is never stored through; the lists of a call that ends in such an error are
+ * unspecified but stay inside the arrays.  Buffer contract as everywhere in this header.  Both calls run on shard 0.
+ * Two forms, the same results:
+ *   ONE WORKGROUP  N <= 2048, n_owned <= 2048, M <= 2046 and T <= 2048 -- what a real rebalance is.  EXACTLY ONE kernel launch
+ *                  (la_last_launches == 1), whatever is NULL or empty: the (topic, id) table, every counter and the lists live
+ *                  in that workgroup's LDS, which writes every counting output in full.  No memset, no allocation, no table in
+ *                  device memory, no scratch of any kind: the call can be captured into a graph, needs no ordering against
+ *                  other cooperative calls, and the results kept for la_group_last_by_member stay valid.
+ *   GENERAL        any limit exceeded, or LA_COOP_FORCE_TABLE: la_cooperative_adjust_device followed by
+ *                  la_group_by_member_device on the adjusted ranks (a buffer of the shard's own when d_coop_member_rank is
+ *                  NULL, grown before anything is enqueued: LA_ENOMEM then).  la_last_launches is the sum of the two: at most 2
+ *                  plus the launches of that grouping (one up to 2 560 entries, two or a radix sort's beyond).  Everything said
+ *                  of the table above holds: the call may allocate, must not be captured, and the cooperative calls of a shard
+ *                  must be ordered among themselves.  The grouping runs in the scratch la_group_by_member_device uses, which is
+ *                  the one la_group_last_by_member itself sorts in and holds no kept result: kept results stay valid here too.
+ * struct_size: sizeof(la_coop_round_args) of the caller's header; less than this library's is LA_EINVAL.  flags: LA_COOP_*, any
+ * other bit is LA_EINVAL.  member_off NULL, or grouped_partition NULL with N > 0, is LA_EINVAL.
+ *
+ * la_cooperative_round takes HOST memory for every pointer of the struct (the d_ prefix of `adjust` notwithstanding): what the
+ * Java host and the C++ mirror have.  The inputs are packed into a staging buffer of shard 0's own -- pinned host memory and
+ * device memory, grown before anything is enqueued (LA_ENOMEM then leaves nothing enqueued), never the assign scratch -- and
+ * travel as ONE H2D copy; the device call above runs on la_stream(ctx); the outputs come back as ONE D2H copy; the call waits and
+ * returns what la_sync would return (on an error the caller's outputs are left as they were).  A pending la_hint_next_call
+ * survives it, and so do the results kept for la_group_last_by_member, in both forms (see above). */
+#define LA_COOP_FORCE_TABLE 1   /* test hook / A-B: never the one-workgroup form; results identical */
+typedef struct la_coop_round_args {
+    int32_t struct_size;          /* sizeof(la_coop_round_args) of the caller's header */
+    int32_t flags;                /* LA_COOP_* */
+    la_coop_args adjust;          /* as for la_cooperative_adjust_device, every output optional */
+    int64_t *member_off;          /* [M+1]  required */
+    int32_t *grouped_topic;       /* [N] or NULL */
+    int32_t *grouped_partition;   /* [N]  required when N > 0 */
+} la_coop_round_args;
+int la_cooperative_round_device(la_ctx *ctx, const la_coop_round_args *args, void *stream);
+int la_cooperative_round(la_ctx *ctx, const la_coop_round_args *args);   /* every pointer is HOST memory */
 
 #ifdef __cplusplus
 }

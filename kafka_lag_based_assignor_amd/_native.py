@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import numpy as np
 
@@ -53,6 +53,14 @@ VERIFY_MAX_LAUNCHES = 7
 # la_cooperative_adjust_device: insert the owned entries, look the target up (kCoopLaunches of csrc/la_coop.h); its per-member
 # counts are LDS bins up to MOVES_LDS_MAX_MEMBERS members, as the moves call's
 COOP_MAX_LAUNCHES = 2
+# la_cooperative_round[_device]: a call within ALL four limits (entries N, owned entries, members M, topics T) is one launch of one
+# workgroup; any other, or one with LA_COOP_FORCE_TABLE, the table form plus the grouping (kCoopSmall* of csrc/la_coop.h; results
+# are the same, tests run both sides)
+COOP_SMALL_ENTRIES = 2048
+COOP_SMALL_OWNED = 2048
+COOP_SMALL_MEMBERS = 2046
+COOP_SMALL_TOPICS = 2048
+LA_COOP_FORCE_TABLE = 1
 
 EXPORTED_SYMBOLS = (
     "la_create", "la_destroy", "la_last_error", "la_version", "la_compute_lag",
@@ -69,6 +77,7 @@ EXPORTED_SYMBOLS = (
     "la_assignment_moves_device", "la_assignment_moves_device_on",
     "la_verify_assignment_device", "la_verify_assignment_device_on",
     "la_cooperative_adjust_device",
+    "la_cooperative_round_device", "la_cooperative_round",
 )
 
 _i64p = ctypes.POINTER(ctypes.c_int64)
@@ -149,6 +158,30 @@ class CoopArgs(ctypes.Structure):
         ("d_member_kept", ctypes.c_void_p), ("d_member_fresh", ctypes.c_void_p), ("d_member_pending", ctypes.c_void_p),
         ("d_member_release", ctypes.c_void_p), ("d_topic_withheld", ctypes.c_void_p), ("d_summary", ctypes.c_void_p),
     ]
+
+
+class CoopRoundArgs(ctypes.Structure):
+    """struct la_coop_round_args (addresses as ints, None / 0 = NULL; struct_size is filled in by cooperative_round_device).
+    `adjust` is the CoopArgs of cooperative_adjust_device; for la_cooperative_round every address is host memory."""
+    _fields_ = [
+        ("struct_size", ctypes.c_int32), ("flags", ctypes.c_int32), ("adjust", CoopArgs),
+        ("member_off", ctypes.c_void_p), ("grouped_topic", ctypes.c_void_p), ("grouped_partition", ctypes.c_void_p),
+    ]
+
+
+class CoopRound(NamedTuple):
+    """What Context.cooperative_round returns: the eight outputs of the adjusted assignment, then every member's list of it."""
+    prev_owner: np.ndarray
+    coop_member_rank: np.ndarray
+    kept: np.ndarray
+    fresh: np.ndarray
+    pending: np.ndarray
+    release: np.ndarray
+    topic_withheld: np.ndarray
+    summary: np.ndarray
+    member_off: np.ndarray
+    grouped_topic: np.ndarray
+    grouped_partition: np.ndarray
 
 
 class PhaseTimes(ctypes.Structure):
@@ -298,6 +331,11 @@ def load() -> ctypes.CDLL:
     if hasattr(L, "la_cooperative_adjust_device"):
         L.la_cooperative_adjust_device.restype = ctypes.c_int
         L.la_cooperative_adjust_device.argtypes = [ctypes.c_void_p, ctypes.POINTER(CoopArgs), ctypes.c_void_p]
+    if hasattr(L, "la_cooperative_round_device"):
+        L.la_cooperative_round_device.restype = ctypes.c_int
+        L.la_cooperative_round_device.argtypes = [ctypes.c_void_p, ctypes.POINTER(CoopRoundArgs), ctypes.c_void_p]
+        L.la_cooperative_round.restype = ctypes.c_int
+        L.la_cooperative_round.argtypes = [ctypes.c_void_p, ctypes.POINTER(CoopRoundArgs)]
     _lib = L
     return L
 
@@ -752,6 +790,63 @@ class Context:
         if not args.struct_size:
             args.struct_size = ctypes.sizeof(CoopArgs)
         self._check(fn(self._h, ctypes.byref(args), ctypes.c_void_p(stream)))
+
+    def cooperative_round_device(self, args: CoopRoundArgs, stream: int = 0) -> None:
+        """la_cooperative_round_device (shard 0 of the context): cooperative_adjust_device on args.adjust -- every one of its
+        outputs optional -- and every member's list of the adjusted assignment (member_off int64[M+1], grouped_topic int32[N] or
+        0, grouped_partition int32[N]): what group_by_member_device writes for the adjusted ranks, whether args.adjust wants
+        them or not, so the lists of one round can be the owned arrays of the next as they lie.  Within COOP_SMALL_ENTRIES /
+        _OWNED / _MEMBERS / _TOPICS it is ONE kernel launch without memset, allocation or scratch; otherwise, or with
+        args.flags = LA_COOP_FORCE_TABLE, the table form followed by the grouping.  Errors as for cooperative_adjust_device.
+        sharding.cooperative_round_numpy is the same on the host."""
+        fn = getattr(self._lib, "la_cooperative_round_device", None)
+        if fn is None:
+            raise LagAssignError(LA_EINVAL, "this liblagassign.so has no la_cooperative_round_device")
+        if not args.struct_size:
+            args.struct_size = ctypes.sizeof(CoopRoundArgs)
+        self._check(fn(self._h, ctypes.byref(args), ctypes.c_void_p(stream)))
+
+    def cooperative_round(self, part_off, out_partition, out_member_rank, n_members: int, owned_off, owned_topic, owned_partition,
+                          force_table: bool = False) -> CoopRound:
+        """la_cooperative_round: the cooperative round on host arrays (numpy in, a CoopRound of numpy arrays out) -- the target
+        (part_off, out_partition, out_member_rank) against every member's owned list (owned_off int64[M+1], owned_topic /
+        owned_partition; all three None when nobody owns anything).  One copy each way, waited for; raises what sync() would.
+        sharding.cooperative_round_numpy is the same on the host."""
+        fn = getattr(self._lib, "la_cooperative_round", None)
+        if fn is None:
+            raise LagAssignError(LA_EINVAL, "this liblagassign.so has no la_cooperative_round")
+        part_off, out_partition, out_member_rank = _a64(part_off), _a32(out_partition), _a32(out_member_rank)
+        m, t, n = int(n_members), part_off.size - 1, out_partition.size
+        if t < 0 or out_member_rank.size != n:
+            raise ValueError("part_off is empty, or out_partition and out_member_rank differ in length")
+        owned_topic = _a32(owned_topic if owned_topic is not None else [])
+        owned_partition = _a32(owned_partition if owned_partition is not None else [])
+        if owned_partition.size != owned_topic.size:
+            raise ValueError("owned_topic and owned_partition differ in length")
+        if owned_off is None:
+            if owned_topic.size:
+                raise ValueError("owned entries without owned_off")
+        else:
+            owned_off = _a64(owned_off)
+            if owned_off.size != m + 1:
+                raise ValueError("owned_off must hold n_members + 1 offsets")
+        out = CoopRound(np.empty(n, np.int32), np.empty(n, np.int32), np.empty(m, np.int64), np.empty(m, np.int64),
+                        np.empty(m, np.int64), np.empty(m, np.int64), np.empty(t, np.int64), np.empty(6, np.int64),
+                        np.empty(m + 1, np.int64), np.empty(n, np.int32), np.empty(n, np.int32))
+        p = lambda a: a.ctypes.data if a is not None and a.size else None
+        r = CoopRoundArgs()
+        r.struct_size, r.flags = ctypes.sizeof(CoopRoundArgs), LA_COOP_FORCE_TABLE if force_table else 0
+        a = r.adjust
+        a.struct_size = ctypes.sizeof(CoopArgs)
+        a.n_topics, a.n_partitions, a.n_members, a.n_owned = t, n, m, owned_topic.size
+        a.d_part_off, a.d_out_partition, a.d_out_member_rank = part_off.ctypes.data, p(out_partition), p(out_member_rank)
+        a.d_owned_member_off, a.d_owned_topic, a.d_owned_partition = p(owned_off), p(owned_topic), p(owned_partition)
+        a.d_prev_owner, a.d_coop_member_rank = p(out.prev_owner), p(out.coop_member_rank)
+        a.d_member_kept, a.d_member_fresh, a.d_member_pending = p(out.kept), p(out.fresh), p(out.pending)
+        a.d_member_release, a.d_topic_withheld, a.d_summary = p(out.release), p(out.topic_withheld), out.summary.ctypes.data
+        r.member_off, r.grouped_topic, r.grouped_partition = out.member_off.ctypes.data, p(out.grouped_topic), p(out.grouped_partition)
+        self._check(fn(self._h, ctypes.byref(r)))
+        return out
 
     # -- device-resident entry point ------------------------------------------------
     def assign_batch_device(self, batch: DeviceBatch, stream: int = 0, shard: int = 0) -> None:

@@ -1112,6 +1112,42 @@ LA_API int la_verify_assignment_device_on(la_ctx* ctx, int shard, const la_devic
     });
 }
 
+// What la_cooperative_adjust_device and the two round calls check of a la_coop_args, and the validated call.  need_output: the
+// eight outputs are all a call has (the round calls have the lists beside them).
+static int coop_call_of(la_ctx* ctx, const la_coop_args& g, bool need_output, la::CoopCall* out) {
+    if (g.n_topics < 0 || g.n_partitions < 0 || g.n_members < 0 || g.n_owned < 0) return fail(ctx, LA_EINVAL, "negative size");
+    if (g.reserved != 0) return fail(ctx, LA_EINVAL, "la_coop_args.reserved must be 0");
+    if (g.n_members > la::kMovesMaxMembers) return fail(ctx, LA_EINVAL, "n_members must be below 2^30");
+    if (need_output && !g.d_prev_owner && !g.d_coop_member_rank && !g.d_member_kept && !g.d_member_fresh && !g.d_member_pending &&
+        !g.d_member_release && !g.d_topic_withheld && !g.d_summary)
+        return fail(ctx, LA_EINVAL, "every output is NULL");
+    if (g.n_topics == 0 && g.n_partitions != 0) return fail(ctx, LA_EINVAL, "partitions without topics");
+    if (g.n_partitions > 0 && (!g.d_part_off || !g.d_out_partition || !g.d_out_member_rank)) return fail(ctx, LA_EINVAL, "null buffer");
+    if (g.n_owned > 0 && (!g.d_owned_member_off || !g.d_owned_topic || !g.d_owned_partition))
+        return fail(ctx, LA_EINVAL, "null owned buffer");
+    la::CoopCall c{};
+    c.n_topics = g.n_topics;
+    c.n_members = g.n_members;
+    c.n_partitions = g.n_partitions;
+    c.n_owned = g.n_owned;
+    c.part_off = g.d_part_off;
+    c.out_partition = g.d_out_partition;
+    c.out_member_rank = g.d_out_member_rank;
+    c.owned_off = g.d_owned_member_off;
+    c.owned_topic = g.d_owned_topic;
+    c.owned_partition = g.d_owned_partition;
+    c.prev_owner = g.d_prev_owner;
+    c.coop_rank = g.d_coop_member_rank;
+    c.member_kept = g.d_member_kept;
+    c.member_fresh = g.d_member_fresh;
+    c.member_pending = g.d_member_pending;
+    c.member_release = g.d_member_release;
+    c.topic_withheld = g.d_topic_withheld;
+    c.summary = g.d_summary;
+    *out = c;
+    return LA_OK;
+}
+
 // The cooperative form of a rebalance (la_coop.hip), on shard 0.  The table is the shard's own buffer, not the assign scratch:
 // the results kept for la_group_last_by_member stay as they are.
 LA_API int la_cooperative_adjust_device(la_ctx* ctx, const la_coop_args* args, void* stream) {
@@ -1119,38 +1155,138 @@ LA_API int la_cooperative_adjust_device(la_ctx* ctx, const la_coop_args* args, v
         if (!args) return fail(ctx, LA_EINVAL, "args is NULL");
         if (args->struct_size < (int32_t)sizeof(la_coop_args))
             return fail(ctx, LA_EINVAL, "la_coop_args.struct_size is %d, this library takes %d and above", (int)args->struct_size, (int)sizeof(la_coop_args));
-        const la_coop_args& g = *args;
-        if (g.n_topics < 0 || g.n_partitions < 0 || g.n_members < 0 || g.n_owned < 0) return fail(ctx, LA_EINVAL, "negative size");
-        if (g.reserved != 0) return fail(ctx, LA_EINVAL, "la_coop_args.reserved must be 0");
-        if (g.n_members > la::kMovesMaxMembers) return fail(ctx, LA_EINVAL, "n_members must be below 2^30");
-        if (!g.d_prev_owner && !g.d_coop_member_rank && !g.d_member_kept && !g.d_member_fresh && !g.d_member_pending &&
-            !g.d_member_release && !g.d_topic_withheld && !g.d_summary)
-            return fail(ctx, LA_EINVAL, "every output is NULL");
-        if (g.n_topics == 0 && g.n_partitions != 0) return fail(ctx, LA_EINVAL, "partitions without topics");
-        if (g.n_partitions > 0 && (!g.d_part_off || !g.d_out_partition || !g.d_out_member_rank)) return fail(ctx, LA_EINVAL, "null buffer");
-        if (g.n_owned > 0 && (!g.d_owned_member_off || !g.d_owned_topic || !g.d_owned_partition))
-            return fail(ctx, LA_EINVAL, "null owned buffer");
         la::CoopCall c{};
-        c.n_topics = g.n_topics;
-        c.n_members = g.n_members;
-        c.n_partitions = g.n_partitions;
-        c.n_owned = g.n_owned;
-        c.part_off = g.d_part_off;
-        c.out_partition = g.d_out_partition;
-        c.out_member_rank = g.d_out_member_rank;
-        c.owned_off = g.d_owned_member_off;
-        c.owned_topic = g.d_owned_topic;
-        c.owned_partition = g.d_owned_partition;
-        c.prev_owner = g.d_prev_owner;
-        c.coop_rank = g.d_coop_member_rank;
-        c.member_kept = g.d_member_kept;
-        c.member_fresh = g.d_member_fresh;
-        c.member_pending = g.d_member_pending;
-        c.member_release = g.d_member_release;
-        c.topic_withheld = g.d_topic_withheld;
-        c.summary = g.d_summary;
+        if (int rc = coop_call_of(ctx, *args, true, &c)) return rc;
         hipError_t e = la::cooperative_adjust_launch(sh.coop, c, sh.lanes[0].d_status, (hipStream_t)stream);
         return e != hipSuccess ? hip_fail(ctx, e, "cooperative_adjust: %s") : LA_OK;
+    });
+}
+
+static_assert(LA_COOP_FORCE_TABLE == 1, "lagassign.h");
+
+// a la_coop_round_args, checked: the adjust part as above, the lists' own pointers, the flags
+static int coop_round_call_of(la_ctx* ctx, const la_coop_round_args* args, la::CoopRoundCall* out) {
+    if (!args) return fail(ctx, LA_EINVAL, "args is NULL");
+    if (args->struct_size < (int32_t)sizeof(la_coop_round_args))
+        return fail(ctx, LA_EINVAL, "la_coop_round_args.struct_size is %d, this library takes %d and above", (int)args->struct_size, (int)sizeof(la_coop_round_args));
+    if (args->flags & ~LA_COOP_FORCE_TABLE) return fail(ctx, LA_EINVAL, "la_coop_round_args.flags holds a bit this library does not know");
+    la::CoopRoundCall r{};
+    if (int rc = coop_call_of(ctx, args->adjust, false, &r.c)) return rc;
+    if (!args->member_off) return fail(ctx, LA_EINVAL, "member_off is NULL");
+    if (r.c.n_partitions > 0 && !args->grouped_partition) return fail(ctx, LA_EINVAL, "grouped_partition is NULL");
+    if (r.c.n_partitions > 0x7FFFFFFF) return fail(ctx, LA_ESHAPE, "at most 2^31-1 entries are supported");
+    r.member_off = args->member_off;
+    r.grouped_topic = args->grouped_topic;
+    r.grouped_partition = args->grouped_partition;
+    *out = r;
+    return LA_OK;
+}
+
+// The cooperative round in one call (la_coop_small.hip), on shard 0: one launch of one workgroup within the limits of la_coop.h,
+// otherwise the table form and the grouping behind it.  Neither touches the assign scratch or a kept result.
+LA_API int la_cooperative_round_device(la_ctx* ctx, const la_coop_round_args* args, void* stream) {
+    return shard_entry<true>(ctx, 0, "exception in la_cooperative_round_device", [&](Shard& sh) -> int {
+        la::CoopRoundCall r{};
+        if (int rc = coop_round_call_of(ctx, args, &r)) return rc;
+        hipError_t e = la::cooperative_round_launch(sh.coop, sh.lanes[0].large, r, (args->flags & LA_COOP_FORCE_TABLE) != 0,
+                                                    sh.lanes[0].d_status, (hipStream_t)stream);
+        return e != hipSuccess ? hip_fail(ctx, e, "cooperative_round: %s") : LA_OK;
+    });
+}
+
+// The same on host buffers: the inputs packed into the shard's own staging buffer (pinned + device, both grown before anything
+// is enqueued), ONE copy in, the device call on lane 0's stream, ONE copy out, one wait.  8-byte arrays first, so every array
+// is aligned for its element.  It neither takes nor spends a pending la_hint_next_call.
+LA_API int la_cooperative_round(la_ctx* ctx, const la_coop_round_args* args) {
+    return shard_entry<true>(ctx, 0, "exception in la_cooperative_round", [&](Shard& sh) -> int {
+        la::CoopRoundCall host{};
+        if (int rc = coop_round_call_of(ctx, args, &host)) return rc;
+        const la::CoopCall& h = host.c;
+        const size_t N = (size_t)h.n_partitions, n = (size_t)h.n_owned, M = (size_t)h.n_members, T = (size_t)h.n_topics;
+        const bool use_part_off = N > 0, use_owned = n > 0;
+        size_t at = 0;
+        auto take = [&](size_t bytes) { const size_t o = at; at += (bytes + 7) & ~(size_t)7; return o; };
+        // inputs
+        const size_t i_part_off = take(use_part_off ? (T + 1) * 8 : 0), i_owned_off = take(use_owned ? (M + 1) * 8 : 0);
+        const size_t i_pid = take(N * 4), i_rank = take(N * 4), i_otopic = take(n * 4), i_opid = take(n * 4);
+        const size_t in_bytes = at;
+        // outputs: the wanted ones, side by side
+        const size_t o_member_off = take((M + 1) * 8);
+        int64_t* const h_count[4] = {h.member_kept, h.member_fresh, h.member_pending, h.member_release};
+        size_t o_count[4];
+        for (int w = 0; w < 4; ++w) o_count[w] = take(h_count[w] ? M * 8 : 0);
+        const size_t o_withheld = take(h.topic_withheld ? T * 8 : 0), o_summary = take(h.summary ? 6 * 8 : 0);
+        const size_t o_prev = take(h.prev_owner ? N * 4 : 0), o_coop = take(h.coop_rank ? N * 4 : 0);
+        const size_t o_gtopic = take(host.grouped_topic ? N * 4 : 0), o_gpart = take(N * 4);
+        const size_t total = at, out_bytes = total - in_bytes;
+        // both halves of the staging buffer before anything is enqueued
+        la::CoopScratch& s = sh.coop;
+        if (total > s.stage_h_cap) {
+            if (s.stage_h) { (void)hipHostFree(s.stage_h); s.stage_h = nullptr; s.stage_h_cap = 0; }
+            const size_t want = total + total / 4 + 256;
+            const hipError_t e = hipHostMalloc(&s.stage_h, want, hipHostMallocDefault);
+            if (e != hipSuccess) { s.stage_h = nullptr; return hip_fail(ctx, e, "cooperative_round staging (host): %s"); }
+            s.stage_h_cap = want;
+        }
+        if (total > s.stage_d_cap) {
+            if (s.stage_d) { (void)hipFree(s.stage_d); s.stage_d = nullptr; s.stage_d_cap = 0; }
+            const size_t want = total + total / 4 + 256;
+            const hipError_t e = hipMalloc(&s.stage_d, want);
+            if (e != hipSuccess) { s.stage_d = nullptr; return hip_fail(ctx, e, "cooperative_round staging (device): %s"); }
+            s.stage_d_cap = want;
+        }
+        char* const hp = static_cast<char*>(s.stage_h);
+        char* const dp = static_cast<char*>(s.stage_d);
+        if (use_part_off) memcpy(hp + i_part_off, h.part_off, (T + 1) * 8);
+        if (use_owned) memcpy(hp + i_owned_off, h.owned_off, (M + 1) * 8);
+        if (N) {
+            memcpy(hp + i_pid, h.out_partition, N * 4);
+            memcpy(hp + i_rank, h.out_member_rank, N * 4);
+        }
+        if (n) {
+            memcpy(hp + i_otopic, h.owned_topic, n * 4);
+            memcpy(hp + i_opid, h.owned_partition, n * 4);
+        }
+        la::CoopRoundCall d = host;
+        d.c.part_off = use_part_off ? (const int64_t*)(dp + i_part_off) : nullptr;
+        d.c.owned_off = use_owned ? (const int64_t*)(dp + i_owned_off) : nullptr;
+        d.c.out_partition = N ? (const int32_t*)(dp + i_pid) : nullptr;
+        d.c.out_member_rank = N ? (const int32_t*)(dp + i_rank) : nullptr;
+        d.c.owned_topic = n ? (const int32_t*)(dp + i_otopic) : nullptr;
+        d.c.owned_partition = n ? (const int32_t*)(dp + i_opid) : nullptr;
+        d.member_off = (int64_t*)(dp + o_member_off);
+        d.c.member_kept = h_count[0] ? (int64_t*)(dp + o_count[0]) : nullptr;
+        d.c.member_fresh = h_count[1] ? (int64_t*)(dp + o_count[1]) : nullptr;
+        d.c.member_pending = h_count[2] ? (int64_t*)(dp + o_count[2]) : nullptr;
+        d.c.member_release = h_count[3] ? (int64_t*)(dp + o_count[3]) : nullptr;
+        d.c.topic_withheld = h.topic_withheld ? (int64_t*)(dp + o_withheld) : nullptr;
+        d.c.summary = h.summary ? (int64_t*)(dp + o_summary) : nullptr;
+        d.c.prev_owner = h.prev_owner ? (int32_t*)(dp + o_prev) : nullptr;
+        d.c.coop_rank = h.coop_rank ? (int32_t*)(dp + o_coop) : nullptr;
+        d.grouped_topic = host.grouped_topic ? (int32_t*)(dp + o_gtopic) : nullptr;
+        d.grouped_partition = (int32_t*)(dp + o_gpart);
+        Lane& ln = sh.lanes[0];
+        hipStream_t st = ln.stream;
+        if (in_bytes) LA_HIP(ctx, hipMemcpyAsync(dp, hp, in_bytes, hipMemcpyHostToDevice, st));
+        hipError_t e = la::cooperative_round_launch(s, ln.large, d, (args->flags & LA_COOP_FORCE_TABLE) != 0, ln.d_status, st);
+        if (e != hipSuccess) {
+            (void)hipStreamSynchronize(st);
+            return hip_fail(ctx, e, "cooperative_round: %s");
+        }
+        LA_HIP(ctx, hipMemcpyAsync(hp + in_bytes, dp + in_bytes, out_bytes, hipMemcpyDeviceToHost, st));
+        if (int rc = sync_status(ctx, ln, st)) return rc;
+        memcpy(host.member_off, hp + o_member_off, (M + 1) * 8);
+        for (int w = 0; w < 4; ++w)
+            if (h_count[w] && M) memcpy(h_count[w], hp + o_count[w], M * 8);
+        if (h.topic_withheld && T) memcpy(h.topic_withheld, hp + o_withheld, T * 8);
+        if (h.summary) memcpy(h.summary, hp + o_summary, 6 * 8);
+        if (N) {
+            if (h.prev_owner) memcpy(h.prev_owner, hp + o_prev, N * 4);
+            if (h.coop_rank) memcpy(h.coop_rank, hp + o_coop, N * 4);
+            if (host.grouped_topic) memcpy(host.grouped_topic, hp + o_gtopic, N * 4);
+            memcpy(host.grouped_partition, hp + o_gpart, N * 4);
+        }
+        return LA_OK;
     });
 }
 

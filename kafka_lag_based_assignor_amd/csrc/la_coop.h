@@ -1,7 +1,9 @@
-// la_coop.h -- host-visible declarations of la_cooperative_adjust_device (la_coop.hip): its scratch, its call struct, its launcher
-// (its status bit, kStatusCoop, stands with the others in la_kernels.h).
+// la_coop.h -- host-visible declarations of la_cooperative_adjust_device (la_coop.hip) and of la_cooperative_round[_device]
+// (la_coop_small.hip): the scratch, the call structs, the launchers (the status bit, kStatusCoop, stands with the others in
+// la_kernels.h).
 #pragma once
 #include "la_kernels.h"
+#include "la_group_small.h"
 
 namespace la {
 
@@ -12,9 +14,43 @@ namespace la {
 constexpr int kCoopLaunches = 2;            // insert | lookup: what la_last_launches reports at most (lagassign.h)
 constexpr int64_t kCoopMaxOwned = 1ll << 40;      // beyond it the table is not even asked for (hipErrorOutOfMemory)
 
+// ---- device code both compile units share: the key, its first slot, a wavefront sum, the bisection of an offset array ----------
+__device__ __forceinline__ uint64_t coop_key(int32_t topic, int32_t id) {
+    return ((uint64_t)(uint32_t)(topic + 1) << 32) | (uint32_t)id;
+}
+
+__device__ __forceinline__ uint64_t coop_first_slot(uint64_t key, int bits) {       // Fibonacci hashing over both halves of the key
+    return (key * 0x9E3779B97F4A7C15ull) >> (64 - bits);
+}
+
+__device__ __forceinline__ uint64_t wave_sum_u64(uint64_t v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, d), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), d);
+        v += ((uint64_t)hi << 32) | lo;
+    }
+    return v;
+}
+
+// largest r in [lo, hi) with off[r] <= x, for lo < hi; with offsets that do not ascend some r of that range all the same
+__device__ __forceinline__ int64_t last_not_above(const int64_t* off, int64_t lo, int64_t hi, int64_t x) {
+    while (hi - lo > 1) {
+        const int64_t mid = lo + ((hi - lo) >> 1);
+        if (off[mid] <= x) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
 struct CoopScratch {            // of one shard, grown lazily: never the assign scratch (results kept on the device stay valid)
     void* table = nullptr;      // keys, then payloads
     size_t table_cap = 0;
+    void* ranks = nullptr;      // la_cooperative_round_device, general form, without d_coop_member_rank: the adjusted ranks
+    size_t ranks_cap = 0;
+    void* stage_h = nullptr;    // la_cooperative_round (host buffers): inputs and outputs of a call, pinned ...
+    size_t stage_h_cap = 0;
+    void* stage_d = nullptr;    // ... and on the device: one copy each way
+    size_t stage_d_cap = 0;
 };
 
 struct CoopCall {               // la_coop_args (lagassign.h), validated
@@ -33,5 +69,33 @@ struct CoopCall {               // la_coop_args (lagassign.h), validated
 // be had.  Sets kStatusCoop / kStatusShape / kStatusInternal.
 hipError_t cooperative_adjust_launch(CoopScratch& s, const CoopCall& c, uint32_t* status, hipStream_t stream);
 void coop_scratch_release(CoopScratch& s);
+
+// ---- the round in one call: the adjusted assignment AND every member's list of it (la_coop_small.hip) ---------------------------
+// A call within ALL four limits is ONE launch of ONE workgroup that holds the (topic, id) table, the counters and the lists in
+// its LDS (coop_round_small_kernel: no memset, no allocation, nothing in device memory beside the caller's arrays).  Any other
+// call, or one with LA_COOP_FORCE_TABLE, is cooperative_adjust_launch followed by group_by_member_launch on the adjusted ranks.
+// The LDS budget of every phase is proved by the static_asserts of la_coop_small.hip.
+constexpr int kCoopSmallEntries = 2048;                 // N: the staged target (ids, ranks, topics) and the lists' seven arrays
+constexpr int kCoopSmallOwned = 2048;                   // n_owned: 2 x this many slots of 12 B are the table
+constexpr int kCoopSmallMembers = kTailGroupM - 2;      // M: the groups of the list builder are the members, "nobody" and the clamp
+constexpr int kCoopSmallTopics = 2048;                  // T: T + 1 part offsets and T withheld counters
+constexpr int kCoopSmallThreads = 1024;
+
+struct CoopRoundCall {          // la_coop_round_args (lagassign.h), validated
+    CoopCall c;
+    int64_t* member_off;        // [M + 1]
+    int32_t *grouped_topic, *grouped_partition;      // [N]; grouped_topic may be null
+};
+
+inline bool coop_round_is_small(const CoopCall& c) {
+    return c.n_partitions <= kCoopSmallEntries && c.n_owned <= kCoopSmallOwned && c.n_members <= kCoopSmallMembers &&
+           c.n_topics <= kCoopSmallTopics;
+}
+
+// The one-workgroup form (coop_round_is_small) unless force_table; otherwise at most kCoopLaunches launches and then those of
+// group_by_member_launch on `large`, the adjusted ranks in s.ranks when the caller wants none (grown, like the table, before
+// anything is enqueued: hipErrorOutOfMemory then).  Sets kStatusCoop / kStatusShape / kStatusInternal.
+hipError_t cooperative_round_launch(CoopScratch& s, LargeScratch& large, const CoopRoundCall& r, bool force_table, uint32_t* status,
+                                    hipStream_t stream);
 
 }  // namespace la

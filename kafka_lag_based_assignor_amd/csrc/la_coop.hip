@@ -46,33 +46,6 @@ struct CoopArgs {
     int64_t n_chunks;           // workgroup steps of the launch
 };
 
-__device__ __forceinline__ uint64_t coop_key(int32_t topic, int32_t id) {
-    return ((uint64_t)(uint32_t)(topic + 1) << 32) | (uint32_t)id;
-}
-
-__device__ __forceinline__ uint64_t coop_first_slot(uint64_t key, int bits) {       // Fibonacci hashing over both halves of the key
-    return (key * 0x9E3779B97F4A7C15ull) >> (64 - bits);
-}
-
-__device__ __forceinline__ uint64_t wave_sum_u64(uint64_t v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, d), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), d);
-        v += ((uint64_t)hi << 32) | lo;
-    }
-    return v;
-}
-
-// largest r in [lo, hi) with off[r] <= x, for lo < hi; with offsets that do not ascend some r of that range all the same
-__device__ __forceinline__ int64_t last_not_above(const int64_t* off, int64_t lo, int64_t hi, int64_t x) {
-    while (hi - lo > 1) {
-        const int64_t mid = lo + ((hi - lo) >> 1);
-        if (off[mid] <= x) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
-
 // LDS (LDS_OFF): the owned offsets, M + 1 words
 template <bool LDS_OFF>
 __global__ __launch_bounds__(kMovesThreads) void coop_insert_kernel(CoopArgs a) {
@@ -258,6 +231,9 @@ __global__ __launch_bounds__(kMovesThreads) void coop_lookup_kernel(CoopArgs a) 
 
 void coop_scratch_release(CoopScratch& s) {
     if (s.table) (void)hipFree(s.table);
+    if (s.ranks) (void)hipFree(s.ranks);
+    if (s.stage_d) (void)hipFree(s.stage_d);
+    if (s.stage_h) (void)hipHostFree(s.stage_h);
     s = CoopScratch{};
 }
 

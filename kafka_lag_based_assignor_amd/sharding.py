@@ -510,6 +510,15 @@ def owned_after_round(part_off, out_partition, coop_member_rank, n_members: int)
     return group_by_member_numpy(part_off, out_partition, coop_member_rank, n_members)
 
 
+def cooperative_round_numpy(part_off, out_partition, out_member_rank, n_members: int, owned_off, owned_topic, owned_partition):
+    """la_cooperative_round[_device] restated on the host: cooperative_adjust_numpy, then owned_after_round on its adjusted ranks
+    -> the eight outputs of the former followed by (member_off int64[M+1], grouped_topic int32[N], grouped_partition int32[N]).
+    The withheld entries and those of topics without consumers sit before member_off[0]; the three lists are the owned arrays
+    of the next round as they are.  ValueError as cooperative_adjust_numpy.  The yardstick of tests/test_coop_round_gpu.py."""
+    adjusted = cooperative_adjust_numpy(part_off, out_partition, out_member_rank, n_members, owned_off, owned_topic, owned_partition)
+    return adjusted + owned_after_round(part_off, out_partition, adjusted[1], n_members)
+
+
 def reduce_member_loads(partitions, lag, unassigned, group=None):
     """Partial roll-ups of the ranks' shards -> the group-wide roll-up on every rank: ONE all_reduce(SUM) over a single int64
     tensor of 2 * M + 1 entries (shards are disjoint topic ranges, so the sum of the partial roll-ups IS the roll-up; int64
