@@ -20,6 +20,8 @@
  *   la_group_by_member      building every member's List<TopicPartition>      Main.java:171-174, :264
  *   la_assign_batch_grouped la_assign_batch + la_group_last_by_member in one call: the body of
  *                           assign(Cluster, GroupSubscription) between the offset RPCs and the wrapping  Main.java:147-156
+ *   la_assign_batch_cooperative  nothing in the reference, whose protocol is eager: the same body for a COOPERATIVE host --
+ *                           the assignment, the owned lists joined against it and every member's adjusted list in one call
  *   la_create_multi         the per-topic loop, sharded over the GPUs of a node Main.java:177-184
  *   la_assign_batch_device_on  the same loop for a caller whose data already lives on every GPU
  *   la_plan_shards          (which topics of that loop each shard takes)
@@ -261,6 +263,7 @@ const char *la_last_error(const la_ctx *ctx);
  *                la_verify_assignment_device / la_verify_assignment_device_on (certify an assignment);
  *                la_cooperative_adjust_device (the cooperative form of a rebalance);
  *                la_cooperative_round_device / la_cooperative_round (that form and every member's list of it in one call);
+ *                la_assign_batch_cooperative (a cooperative rebalance from host buffers in one call);
  *                a shim detects them by symbol lookup (dlsym / getattr) instead of by version */
 #define LA_VERSION 500
 int la_version(void);
@@ -855,6 +858,63 @@ typedef struct la_coop_round_args {
 } la_coop_round_args;
 int la_cooperative_round_device(la_ctx *ctx, const la_coop_round_args *args, void *stream);
 int la_cooperative_round(la_ctx *ctx, const la_coop_round_args *args);   /* every pointer is HOST memory */
+
+/* A COOPERATIVE rebalance in one host call: la_assign_batch / _sparse / _lags AND la_cooperative_round on its result.  It replaces
+ * no line of Main.java (the reference is eager); it is to a cooperative host what la_assign_batch_grouped is to the eager one:
+ * offsets, subscriptions and what every member owns go in, the lists to hand back come out.  Every pointer is HOST memory.
+ *   the rebalance     exactly the inputs of the assign calls: `lag` non-NULL is la_assign_batch_lags (the four offset fields are
+ *                     not looked at); otherwise begin_off non-NULL is la_assign_batch and begin_off NULL is la_assign_batch_sparse
+ *                     with (n_none, none_index, none_begin) -- LA_RESET_LATEST reads neither.  The TARGET is what that call
+ *                     returns for these inputs, bit for bit, and every error condition of that call applies.
+ *   the owned lists   n_owned, owned_member_off, owned_topic, owned_partition as la_coop_args has them; n_members is M.
+ *   outputs           member_off, grouped_topic, grouped_partition and the eight adjust outputs: what la_cooperative_round writes
+ *                     for that target and these owned lists, with the same LA_EINVAL / LA_ESHAPE conditions.  out_total_lag,
+ *                     out_partition / out_member_rank (both or neither) describe the TARGET.  member_off is required,
+ *                     grouped_partition when N > 0; everything else may be NULL.
+ * On any error the caller's outputs are left as they were.  A pending la_hint_next_call is consumed, as by every host-buffer
+ * assign call.  Afterwards the target stays kept on the device, exactly as after la_assign_batch_grouped: la_group_last_by_member
+ * yields the target's EAGER lists.  Buffer contract as everywhere in this header.  The call runs on the whole context like
+ * la_assign_batch; the round itself on shard 0.
+ * Two forms, the same results:
+ *   FUSED    the call is one a zero-copy staged call serves (one shard, staging layout within the zero-copy size), within the
+ *            four ONE WORKGROUP limits above, without LA_COOP_FORCE_TABLE.  The owned arrays ride in the staging buffer the
+ *            assignment kernels read in place; the target stays in device memory; ONE launch of the round's workgroup behind
+ *            them reads it, writes every output into the staging buffer and stores the completion word the calling thread
+ *            spins on.  No copy, no memset, no stream synchronize.  la_last_pipeline is LA_PIPELINE_ZERO_COPY; la_last_launches
+ *            is what la_assign_batch reports for the same inputs and hints (the round takes the place of its finishing launch):
+ *            2 for a one-tile batch with bounds hints.
+ *   GENERAL  everything else: the assign call into buffers of the context's own, then la_cooperative_round; la_last_launches is
+ *            the sum of the two.
+ * struct_size: sizeof(la_assign_coop_args) of the caller's header; less than this library's is LA_EINVAL.  flags: LA_COOP_*, any
+ * other bit is LA_EINVAL.  reserved must be 0. */
+typedef struct la_assign_coop_args {
+    int32_t struct_size;            /* sizeof(la_assign_coop_args) of the caller's header */
+    int32_t flags;                  /* LA_COOP_* */
+    int32_t n_topics, reset_mode;
+    const int64_t *part_off;        /* [T+1] */
+    const int32_t *partition_id;    /* [N] */
+    const int64_t *lag;             /* [N] or NULL */
+    const int64_t *begin_off;       /* [N] dense, or NULL: the sparse list */
+    const int64_t *end_off, *committed_off;
+    int64_t n_none;
+    const int64_t *none_index, *none_begin;
+    const int64_t *cons_off;        /* [T+1] */
+    const int32_t *cons_rank;       /* [K] */
+    int32_t n_members, reserved;    /* M; 0 */
+    int64_t n_owned;
+    const int64_t *owned_member_off;/* [M+1] */
+    const int32_t *owned_topic, *owned_partition;   /* [n_owned] */
+    int64_t *member_off;            /* [M+1]  required */
+    int32_t *grouped_topic;         /* [N] or NULL */
+    int32_t *grouped_partition;     /* [N]  required when N > 0 */
+    int64_t *out_total_lag;         /* [K] or NULL: the target's totals */
+    int32_t *out_partition, *out_member_rank;       /* [N] or both NULL: the target */
+    int32_t *prev_owner, *coop_member_rank;         /* [N] or NULL */
+    int64_t *member_kept, *member_fresh, *member_pending, *member_release;   /* [M] or NULL */
+    int64_t *topic_withheld;        /* [T] or NULL */
+    int64_t *summary;               /* [6] or NULL */
+} la_assign_coop_args;
+int la_assign_batch_cooperative(la_ctx *ctx, const la_assign_coop_args *args);
 
 #ifdef __cplusplus
 }

@@ -78,6 +78,7 @@ EXPORTED_SYMBOLS = (
     "la_verify_assignment_device", "la_verify_assignment_device_on",
     "la_cooperative_adjust_device",
     "la_cooperative_round_device", "la_cooperative_round",
+    "la_assign_batch_cooperative",
 )
 
 _i64p = ctypes.POINTER(ctypes.c_int64)
@@ -181,6 +182,44 @@ class CoopRound(NamedTuple):
     summary: np.ndarray
     member_off: np.ndarray
     grouped_topic: np.ndarray
+    grouped_partition: np.ndarray
+
+
+class AssignCoopArgs(ctypes.Structure):
+    """struct la_assign_coop_args (host addresses as ints, None / 0 = NULL)"""
+    _fields_ = [
+        ("struct_size", ctypes.c_int32), ("flags", ctypes.c_int32), ("n_topics", ctypes.c_int32), ("reset_mode", ctypes.c_int32),
+        ("part_off", ctypes.c_void_p), ("partition_id", ctypes.c_void_p), ("lag", ctypes.c_void_p),
+        ("begin_off", ctypes.c_void_p), ("end_off", ctypes.c_void_p), ("committed_off", ctypes.c_void_p),
+        ("n_none", ctypes.c_int64), ("none_index", ctypes.c_void_p), ("none_begin", ctypes.c_void_p),
+        ("cons_off", ctypes.c_void_p), ("cons_rank", ctypes.c_void_p),
+        ("n_members", ctypes.c_int32), ("reserved", ctypes.c_int32),
+        ("n_owned", ctypes.c_int64), ("owned_member_off", ctypes.c_void_p), ("owned_topic", ctypes.c_void_p),
+        ("owned_partition", ctypes.c_void_p),
+        ("member_off", ctypes.c_void_p), ("grouped_topic", ctypes.c_void_p), ("grouped_partition", ctypes.c_void_p),
+        ("out_total_lag", ctypes.c_void_p), ("out_partition", ctypes.c_void_p), ("out_member_rank", ctypes.c_void_p),
+        ("prev_owner", ctypes.c_void_p), ("coop_member_rank", ctypes.c_void_p),
+        ("member_kept", ctypes.c_void_p), ("member_fresh", ctypes.c_void_p), ("member_pending", ctypes.c_void_p),
+        ("member_release", ctypes.c_void_p), ("topic_withheld", ctypes.c_void_p), ("summary", ctypes.c_void_p),
+    ]
+
+
+class AssignCoop(NamedTuple):
+    """What Context.assign_batch_cooperative returns (and takes as `out`): the TARGET (what the assign call returns) and its
+    totals, the eight outputs of the adjusted assignment, then every member's list of it.  A None entry was not asked for."""
+    out_partition: Optional[np.ndarray]
+    out_member_rank: Optional[np.ndarray]
+    totals: Optional[np.ndarray]
+    prev_owner: Optional[np.ndarray]
+    coop_member_rank: Optional[np.ndarray]
+    kept: Optional[np.ndarray]
+    fresh: Optional[np.ndarray]
+    pending: Optional[np.ndarray]
+    release: Optional[np.ndarray]
+    topic_withheld: Optional[np.ndarray]
+    summary: Optional[np.ndarray]
+    member_off: np.ndarray
+    grouped_topic: Optional[np.ndarray]
     grouped_partition: np.ndarray
 
 
@@ -336,6 +375,9 @@ def load() -> ctypes.CDLL:
         L.la_cooperative_round_device.argtypes = [ctypes.c_void_p, ctypes.POINTER(CoopRoundArgs), ctypes.c_void_p]
         L.la_cooperative_round.restype = ctypes.c_int
         L.la_cooperative_round.argtypes = [ctypes.c_void_p, ctypes.POINTER(CoopRoundArgs)]
+    if hasattr(L, "la_assign_batch_cooperative"):
+        L.la_assign_batch_cooperative.restype = ctypes.c_int
+        L.la_assign_batch_cooperative.argtypes = [ctypes.c_void_p, ctypes.POINTER(AssignCoopArgs)]
     _lib = L
     return L
 
@@ -390,6 +432,25 @@ def _check_out_grouped(out, m: int, n: int, k: int):
     if not (ok(off, np.int64, m + 1) and ok(g_t, np.int32, n, True) and ok(g_p, np.int32, n) and ok(out_t, np.int64, k, True)):
         raise ValueError("out buffers must be contiguous int64[M+1], int32[N] or None, int32[N], int64[K] or None")
     return off, g_t, g_p, out_t
+
+
+def _check_out_coop(out: AssignCoop, m: int, n: int, k: int, t: int) -> AssignCoop:
+    """Caller-owned buffers of assign_batch_cooperative: contiguous, of the right type and size, as for _check_out_grouped.
+    member_off and grouped_partition are required, the target's two arrays come together, every other entry may be None."""
+    def ok(a, dtype, size, optional=True):
+        if a is None:
+            return optional
+        return isinstance(a, np.ndarray) and a.dtype == dtype and a.size == size and a.flags.c_contiguous
+
+    if not (isinstance(out, AssignCoop) and (out.out_partition is None) == (out.out_member_rank is None) and
+            ok(out.out_partition, np.int32, n) and ok(out.out_member_rank, np.int32, n) and ok(out.totals, np.int64, k) and
+            ok(out.prev_owner, np.int32, n) and ok(out.coop_member_rank, np.int32, n) and ok(out.kept, np.int64, m) and
+            ok(out.fresh, np.int64, m) and ok(out.pending, np.int64, m) and ok(out.release, np.int64, m) and
+            ok(out.topic_withheld, np.int64, t) and ok(out.summary, np.int64, 6) and ok(out.member_off, np.int64, m + 1, False) and
+            ok(out.grouped_topic, np.int32, n) and ok(out.grouped_partition, np.int32, n, False)):
+        raise ValueError("out must be an AssignCoop of contiguous arrays: int32[N] x2 (both or neither), int64[K], int32[N] x2, "
+                         "int64[M] x4, int64[T], int64[6], int64[M+1] (required), int32[N], int32[N] (required); None = not wanted")
+    return out
 
 
 def plan_shards(part_off, n_shards: int) -> np.ndarray:
@@ -846,6 +907,68 @@ class Context:
         a.d_member_release, a.d_topic_withheld, a.d_summary = p(out.release), p(out.topic_withheld), out.summary.ctypes.data
         r.member_off, r.grouped_topic, r.grouped_partition = out.member_off.ctypes.data, p(out.grouped_topic), p(out.grouped_partition)
         self._check(fn(self._h, ctypes.byref(r)))
+        return out
+
+    def assign_batch_cooperative(self, part_off, partition_id, cons_off, cons_rank, n_members: int, owned_off, owned_topic,
+                                 owned_partition, *, lag=None, begin=None, end=None, committed=None, reset_mode: int = 0,
+                                 none_index=None, none_begin=None, force_table: bool = False,
+                                 out: Optional[AssignCoop] = None) -> AssignCoop:
+        """la_assign_batch_cooperative: a COOPERATIVE rebalance in one call -- the assign call (`lag`: assign_batch_lags; `begin`:
+        assign_batch; neither: assign_batch_sparse with none_index / none_begin) and cooperative_round on its result against
+        every member's owned list (owned_off int64[M+1], owned_topic / owned_partition; all three None when nobody owns
+        anything).  Returns an AssignCoop; `out` = caller-owned buffers in that shape, None entries are not computed.  A small
+        call is zero-copy with the round as its last launch; the target stays on the device for group_last_by_member().
+        sharding.assign_cooperative_numpy is the same on the host."""
+        fn = getattr(self._lib, "la_assign_batch_cooperative", None)
+        if fn is None:
+            raise LagAssignError(LA_EINVAL, "this liblagassign.so has no la_assign_batch_cooperative")
+        part_off, cons_off = _a64(part_off), _a64(cons_off)
+        partition_id, cons_rank = _a32(partition_id), _a32(cons_rank)
+        m, t, n, k = int(n_members), part_off.size - 1, partition_id.size, cons_rank.size
+        if t < 0 or cons_off.size != t + 1:
+            raise ValueError("part_off is empty, or part_off and cons_off differ in length")
+        lag, begin = (None if lag is None else _a64(lag)), (None if begin is None else _a64(begin))
+        end, committed = (None if end is None else _a64(end)), (None if committed is None else _a64(committed))
+        none_index = None if none_index is None else _a64(none_index)
+        none_begin = None if none_begin is None else _a64(none_begin)
+        owned_topic = _a32(owned_topic if owned_topic is not None else [])
+        owned_partition = _a32(owned_partition if owned_partition is not None else [])
+        if owned_partition.size != owned_topic.size:
+            raise ValueError("owned_topic and owned_partition differ in length")
+        if owned_off is None:
+            if owned_topic.size:
+                raise ValueError("owned entries without owned_off")
+        else:
+            owned_off = _a64(owned_off)
+            if owned_off.size != m + 1:
+                raise ValueError("owned_off must hold n_members + 1 offsets")
+        if out is not None:
+            out = _check_out_coop(out, m, n, k, t)
+        else:
+            out = AssignCoop(np.empty(n, np.int32), np.empty(n, np.int32), np.zeros(k, np.int64),
+                             np.empty(n, np.int32), np.empty(n, np.int32), np.empty(m, np.int64), np.empty(m, np.int64),
+                             np.empty(m, np.int64), np.empty(m, np.int64), np.empty(t, np.int64), np.empty(6, np.int64),
+                             np.empty(m + 1, np.int64), np.empty(n, np.int32), np.empty(n, np.int32))
+        p = lambda a: a.ctypes.data if a is not None and a.size else None
+        g = AssignCoopArgs()
+        g.struct_size, g.flags = ctypes.sizeof(AssignCoopArgs), LA_COOP_FORCE_TABLE if force_table else 0
+        g.n_topics, g.reset_mode = t, reset_mode
+        g.part_off, g.partition_id, g.lag = part_off.ctypes.data, p(partition_id), p(lag)
+        if lag is not None and not lag.size:
+            g.lag = lag.ctypes.data                    # (lags mode is chosen by the pointer, also for an empty batch)
+        g.begin_off, g.end_off, g.committed_off = p(begin), p(end), p(committed)
+        g.n_none = 0 if none_index is None else none_index.size
+        g.none_index, g.none_begin = p(none_index), p(none_begin)
+        g.cons_off, g.cons_rank = cons_off.ctypes.data, p(cons_rank)
+        g.n_members, g.n_owned = m, owned_topic.size
+        g.owned_member_off, g.owned_topic, g.owned_partition = p(owned_off), p(owned_topic), p(owned_partition)
+        g.member_off, g.grouped_topic, g.grouped_partition = out.member_off.ctypes.data, p(out.grouped_topic), p(out.grouped_partition)
+        g.out_total_lag, g.out_partition, g.out_member_rank = p(out.totals), p(out.out_partition), p(out.out_member_rank)
+        g.prev_owner, g.coop_member_rank = p(out.prev_owner), p(out.coop_member_rank)
+        g.member_kept, g.member_fresh, g.member_pending = p(out.kept), p(out.fresh), p(out.pending)
+        g.member_release, g.topic_withheld = p(out.release), p(out.topic_withheld)
+        g.summary = None if out.summary is None else out.summary.ctypes.data
+        self._check(fn(self._h, ctypes.byref(g)))
         return out
 
     # -- device-resident entry point ------------------------------------------------

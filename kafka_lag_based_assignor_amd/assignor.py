@@ -64,6 +64,35 @@ class LagBasedPartitionAssignor:
                                 [(m, list(ts)) for m, ts in subscriptions.items()], offsets)
         return {m: [TopicPartition(*tp) for tp in tps] for m, tps in out.items()}
 
+    # -- the cooperative protocol (nothing in the reference, which is eager) ------------------
+    @staticmethod
+    def supported_protocols() -> List[str]:
+        """ConsumerPartitionAssignor.supportedProtocols(): ["COOPERATIVE", "EAGER"] -- cooperative first, eager kept so a
+        group with an eager member still finds a common protocol."""
+        return list(_host().LagBasedPartitionAssignor.supported_protocols())
+
+    def assign_cooperative(self, metadata: Mapping[str, Sequence[int]], subscriptions: Mapping[str, Sequence[str]],
+                           owned: Mapping[str, Iterable[Tuple[str, int]]], offsets) -> Dict[str, List[TopicPartition]]:
+        """assign() for a group that speaks the COOPERATIVE protocol.  ``owned``: memberId -> the (topic, partition) pairs that
+        member consumes right now (its ownedPartitions(); members that are absent own nothing).  Returns the ADJUSTED
+        assignment: a partition that changes hands between two live members is in nobody's list this round -- its owner
+        revokes it, and the follow-up rebalance (``last_cooperative_round()["followup"]``) hands it over.  With nothing owned
+        it is ``assign()``.  One native call.  ValueError when a partition is claimed twice."""
+        subs = [(m, list(ts), [(str(t), int(p)) for t, p in owned.get(m, ())]) for m, ts in subscriptions.items()]
+        out = self._impl.assign_cooperative({t: list(p) for t, p in metadata.items()}, subs, offsets)
+        return {m: [TopicPartition(*tp) for tp in tps] for m, tps in out.items()}
+
+    @staticmethod
+    def last_cooperative_round() -> Dict[str, object]:
+        """What the last assign_cooperative() on this thread did: ``per_member`` memberId -> (kept, fresh, pending, release),
+        ``topic_withheld`` topic -> count, the totals ``kept`` / ``fresh`` / ``withheld`` / ``dropped`` / ``stale`` and
+        ``followup`` (another rebalance is needed).  last_topic_totals / last_member_loads / last_native_call describe the
+        TARGET of that call, as after assign()."""
+        d = dict(_host().LagBasedPartitionAssignor.last_cooperative_round())
+        d["per_member"] = {m: tuple(int(x) for x in v) for m, v in d["per_member"].items()}
+        d["topic_withheld"] = {t: int(v) for t, v in d["topic_withheld"].items()}
+        return d
+
     def metadata_consumer_props(self) -> Dict[str, str]:
         return dict(self._impl.metadata_consumer_props())
 

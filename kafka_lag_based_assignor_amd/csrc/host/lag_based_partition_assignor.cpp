@@ -37,6 +37,7 @@ la_ctx* shared_ctx_locked() {
 thread_local bool t_last_order_exact = true;
 thread_local LagBasedPartitionAssignor::NativeCallStats t_last_native;
 thread_local LagBasedPartitionAssignor::MemberLoads t_last_loads;
+thread_local LagBasedPartitionAssignor::CooperativeRound t_last_coop;
 
 void check(la_ctx* ctx, int rc) {
     if (rc == LA_OK) return;
@@ -156,7 +157,7 @@ void hint_bounds(la_ctx* ctx, const Flat& f) {
 
 Assignment run_native(const Plan& plan, const std::vector<const TopicData*>& data, bool offsets_mode,
                       int32_t reset_mode, std::map<std::string, std::map<std::string, int64_t>>* totals_out,
-                      const std::function<void(const std::string&)>* debug = nullptr) {
+                      const std::function<void(const std::string&)>* debug = nullptr, const OwnedArrays* owned = nullptr) {
     Flat f;
     for (size_t t = 0; t < plan.topics.size(); ++t) {
         const TopicData* d = data[t];
@@ -191,7 +192,62 @@ Assignment run_native(const Plan& plan, const std::vector<const TopicData*>& dat
     const int32_t n_members = (int32_t)plan.members.size();
     std::vector<int64_t> member_off((size_t)n_members + 1, 0);
     std::vector<int32_t> grouped_topic(n), grouped_pid(n);
-    if (!plan.topics.empty()) {
+    // assignCooperative: the lists above are those of the ADJUSTED assignment; the target itself (for the roll-up) and, with the
+    // debug hook set, its eager lists (for the summary) come beside them
+    std::vector<int32_t> target_pid(owned ? n : 0), target_rank(owned ? n : 0), eager_topic, eager_pid;
+    std::vector<int64_t> eager_off;
+    if (owned) t_last_coop = LagBasedPartitionAssignor::CooperativeRound{};
+    if (owned && !plan.topics.empty()) {
+        const size_t M = (size_t)n_members, T = plan.topics.size();
+        std::vector<int64_t> counts(4 * M), withheld(T), summary(6);
+        std::lock_guard<std::mutex> lock(g_ctx_mutex);
+        la_ctx* ctx = shared_ctx_locked();
+        hint_bounds(ctx, f);
+        la_assign_coop_args a{};
+        a.struct_size = (int32_t)sizeof a;
+        a.n_topics = (int32_t)T;
+        a.reset_mode = reset_mode;
+        a.part_off = f.part_off.data();
+        a.partition_id = f.pid.data();
+        a.end_off = f.end.data();                                // begin_off stays NULL: the sparse list
+        a.committed_off = f.committed.data();
+        a.n_none = (int64_t)f.none_index.size();
+        a.none_index = f.none_index.data();
+        a.none_begin = f.none_begin.data();
+        a.cons_off = f.cons_off.data();
+        a.cons_rank = f.cons_rank.data();
+        a.n_members = n_members;
+        a.n_owned = (int64_t)owned->topic.size();
+        a.owned_member_off = owned->member_off.data();
+        a.owned_topic = owned->topic.data();
+        a.owned_partition = owned->partition.data();
+        a.member_off = member_off.data();
+        a.grouped_topic = grouped_topic.data();
+        a.grouped_partition = grouped_pid.data();
+        a.out_total_lag = out_total.data();
+        a.out_partition = target_pid.data();
+        a.out_member_rank = target_rank.data();
+        a.member_kept = counts.data();
+        a.member_fresh = counts.data() + M;
+        a.member_pending = counts.data() + 2 * M;
+        a.member_release = counts.data() + 3 * M;
+        a.topic_withheld = withheld.data();
+        a.summary = summary.data();
+        check(ctx, la_assign_batch_cooperative(ctx, &a));
+        t_last_native.pipeline = la_last_pipeline(ctx);
+        t_last_native.launches = la_last_launches(ctx);
+        if (debug && *debug) {                                   // (only then: the target's eager lists, still on the device)
+            eager_off.assign(M + 1, 0);
+            eager_topic.resize(n);
+            eager_pid.resize(n);
+            if (n > 0) check(ctx, la_group_last_by_member(ctx, n_members, eager_off.data(), eager_topic.data(), eager_pid.data()));
+        }
+        for (size_t r = 0; r < M; ++r)
+            t_last_coop.per_member[plan.members[plan.member_of_rank[r]]] = {counts[r], counts[M + r], counts[2 * M + r], counts[3 * M + r]};
+        for (size_t t = 0; t < T; ++t) t_last_coop.topic_withheld[plan.topics[t]] = withheld[t];
+        t_last_coop.kept = summary[0]; t_last_coop.fresh = summary[1]; t_last_coop.withheld = summary[2];
+        t_last_coop.dropped = summary[3]; t_last_coop.stale = summary[4]; t_last_coop.followup = summary[5] != 0;
+    } else if (!plan.topics.empty()) {
         std::lock_guard<std::mutex> lock(g_ctx_mutex);       // one lock over both calls: the second reads the first's results
         la_ctx* ctx = shared_ctx_locked();
         hint_bounds(ctx, f);
@@ -221,9 +277,14 @@ Assignment run_native(const Plan& plan, const std::vector<const TopicData*>& dat
         LagBasedPartitionAssignor::MemberLoads loads;
         std::vector<uint64_t> lag_of((size_t)n_members, 0);
         for (size_t c = 0; c < k; ++c) lag_of[(size_t)f.cons_rank[c]] += (uint64_t)out_total[c];
+        std::vector<int64_t> held((size_t)n_members + 1, 0);     // [0]: nobody's.  Of the TARGET: from its ranks where the lists are adjusted ones
+        if (owned)
+            for (size_t i = 0; i < n; ++i) ++held[(size_t)(target_rank[i] + 1)];
+        else
+            for (int32_t r = 0; r <= n_members; ++r) held[(size_t)r] = r == 0 ? member_off[0] : member_off[r] - member_off[r - 1];
         for (int32_t r = 0; r < n_members; ++r)
-            loads.per_member[plan.members[plan.member_of_rank[r]]] = {member_off[r + 1] - member_off[r], (int64_t)lag_of[(size_t)r]};
-        loads.unassigned = member_off[0];
+            loads.per_member[plan.members[plan.member_of_rank[r]]] = {held[(size_t)r + 1], (int64_t)lag_of[(size_t)r]};
+        loads.unassigned = held[0];
         t_last_loads = std::move(loads);
     }
     // partition id -> the element's own topic string (normally the map key), per topic
@@ -237,8 +298,11 @@ Assignment run_native(const Plan& plan, const std::vector<const TopicData*>& dat
         for (int64_t j = member_off[r]; j < member_off[r + 1]; ++j)
             list.push_back(TopicPartition{*topic_of[grouped_topic[j]].at(grouped_pid[j]), grouped_pid[j]});   // :264
     }
-    if (debug && *debug) {
+    if (debug && *debug && (!owned || !eager_off.empty())) {
         // Main.java:279-306.  consumerTotalLags is a HashMap filled with put() in consumers-list order (:216-225).
+        // (after assignCooperative the message describes the target: its eager lists)
+        const std::vector<int64_t>& d_off = owned ? eager_off : member_off;
+        const std::vector<int32_t>&d_topic = owned ? eager_topic : grouped_topic, &d_pid = owned ? eager_pid : grouped_pid;
         for (size_t t = 0; t < plan.topics.size(); ++t) {
             JavaHashMapOrder order(plan.topic_members[t].size());          // new HashMap<>(consumers.size()), :216
             std::vector<int> uniq;
@@ -255,10 +319,10 @@ Assignment run_native(const Plan& plan, const std::vector<const TopicData*>& dat
                 for (int64_t c = f.cons_off[t]; c < f.cons_off[t + 1]; ++c)
                     if (f.cons_rank[c] == r) total = out_total[c];
                 summary += "\t" + plan.members[m] + " (total_lag=" + std::to_string(total) + ")\n";
-                for (int64_t j = member_off[r]; j < member_off[r + 1]; ++j) {
-                    if ((size_t)grouped_topic[j] > t) break;               // the map as it stood after this topic
-                    summary += "\t\t" + *topic_of[grouped_topic[j]].at(grouped_pid[j]) + "-" +
-                               std::to_string(grouped_pid[j]) + "\n";    // TopicPartition.toString()
+                for (int64_t j = d_off[r]; j < d_off[r + 1]; ++j) {
+                    if ((size_t)d_topic[j] > t) break;                     // the map as it stood after this topic
+                    summary += "\t\t" + *topic_of[d_topic[j]].at(d_pid[j]) + "-" +
+                               std::to_string(d_pid[j]) + "\n";          // TopicPartition.toString()
                 }
             }
             (*debug)("Assignment for " + plan.topics[t] + ":\n" + summary);
@@ -346,8 +410,47 @@ Assignment LagBasedPartitionAssignor::assign(const OrderedMap<std::vector<TopicP
     return run_native(plan, data, false, LA_RESET_LATEST, nullptr);
 }
 
+LagBasedPartitionAssignor::CooperativeRound LagBasedPartitionAssignor::lastCooperativeRound() { return t_last_coop; }
+
+OwnedArrays cooperativeOwnedArrays(const std::vector<std::string>& memberIds, const std::vector<std::string>& topics,
+                                   const std::vector<std::vector<TopicPartition>>& ownedPerMember) {
+    if (ownedPerMember.size() != memberIds.size()) throw std::invalid_argument("one owned list per member");
+    std::unordered_map<std::string, int32_t> topic_index;
+    for (size_t t = 0; t < topics.size(); ++t) topic_index.emplace(topics[t], (int32_t)t);
+    const std::vector<int32_t> rank = rankMembers(memberIds);
+    std::vector<size_t> member_of_rank(memberIds.size());
+    for (size_t i = 0; i < memberIds.size(); ++i) member_of_rank[(size_t)rank[i]] = i;
+    OwnedArrays o;
+    o.member_off.push_back(0);
+    for (size_t r = 0; r < memberIds.size(); ++r) {              // in rank order: the layout la_group_by_member writes
+        for (const TopicPartition& tp : ownedPerMember[member_of_rank[r]]) {
+            auto it = topic_index.find(tp.topic);
+            o.topic.push_back(it == topic_index.end() ? -1 : it->second);    // not in this rebalance: a stale claim
+            o.partition.push_back(tp.partition);
+        }
+        o.member_off.push_back((int64_t)o.topic.size());
+    }
+    return o;
+}
+
 Assignment LagBasedPartitionAssignor::assign(const Cluster& metadata, const GroupSubscription& subscriptions,
                                              OffsetSource& offsets) {
+    return assignImpl(metadata, subscriptions, offsets, nullptr);
+}
+
+Assignment LagBasedPartitionAssignor::assignCooperative(const Cluster& metadata, const CooperativeSubscription& subscriptions,
+                                                        OffsetSource& offsets) {
+    GroupSubscription topics;
+    OrderedMap<std::vector<TopicPartition>> owned;
+    for (const auto& kv : subscriptions) {
+        topics.emplace_back(kv.first, kv.second.topics);
+        owned.emplace_back(kv.first, kv.second.ownedPartitions);
+    }
+    return assignImpl(metadata, topics, offsets, &owned);
+}
+
+Assignment LagBasedPartitionAssignor::assignImpl(const Cluster& metadata, const GroupSubscription& subscriptions,
+                                                 OffsetSource& offsets, const OrderedMap<std::vector<TopicPartition>>* owned) {
     // Everything is cold when a rebalance comes (Kafka calls the leader's assign() minutes apart): la_wake runs a one-partition
     // rebalance through the real path NOW (~95 us, cold) -- the three broker round trips below (Main.java:147 -> :317-365)
     // take milliseconds before there is an offset to hand over, and the call that matters then runs warm (at the C ABI a
@@ -425,6 +528,15 @@ Assignment LagBasedPartitionAssignor::assign(const Cluster& metadata, const Grou
         data.push_back(it == by_topic.end() ? nullptr : &it->second);
     }
     last_totals_.clear();
+    if (owned) {
+        // what every member owns, in the plan's member order (a Map has unique keys: the last entry of a member wins, as above)
+        std::unordered_map<std::string, const std::vector<TopicPartition>*> of;
+        for (const auto& kv : *owned) of[kv.first] = &kv.second;
+        std::vector<std::vector<TopicPartition>> per_member;
+        for (const std::string& m : plan.members) per_member.push_back(*of.at(m));
+        const OwnedArrays arrays = cooperativeOwnedArrays(plan.members, plan.topics, per_member);
+        return run_native(plan, data, true, reset, &last_totals_, &debug, &arrays);
+    }
     return run_native(plan, data, true, reset, &last_totals_, &debug);           // wrap: :152-156
 }
 

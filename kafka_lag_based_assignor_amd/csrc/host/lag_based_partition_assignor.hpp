@@ -20,6 +20,7 @@
 // Everything string- or container-shaped happens here; every number is computed by the HIP
 // kernels behind the C ABI (there is no host arithmetic fallback).
 #pragma once
+#include <array>
 #include <cstdint>
 #include <functional>
 #include <map>
@@ -73,6 +74,13 @@ using Cluster = std::map<std::string, std::vector<int32_t>>;
 using GroupSubscription = OrderedMap<std::vector<std::string>>;
 // GroupAssignment / the static assign's result: memberId -> partitions in the reference's list order.
 using Assignment = std::map<std::string, std::vector<TopicPartition>>;
+// What a member sends when the group speaks the COOPERATIVE protocol (ConsumerPartitionAssignor.Subscription): its topics
+// and ownedPartitions() -- what it consumes right now.  Nothing in the reference, whose protocol is eager.
+struct MemberSubscription {
+    std::vector<std::string> topics;
+    std::vector<TopicPartition> ownedPartitions;
+};
+using CooperativeSubscription = OrderedMap<MemberSubscription>;
 
 class LagBasedPartitionAssignor {
  public:
@@ -86,6 +94,29 @@ class LagBasedPartitionAssignor {
     // Main.java:137-157.  `offsets` plays the metadata consumer.
     Assignment assign(const Cluster& metadata, const GroupSubscription& subscriptions, OffsetSource& offsets);
 
+    // ConsumerPartitionAssignor.supportedProtocols(): cooperative first -- the group picks the first protocol every member
+    // supports, so a group of these assignors rebalances cooperatively and one with an eager member still finds EAGER
+    // (INTEGRATION.md 3.1, step 1).
+    static std::vector<std::string> supportedProtocols() { return {"COOPERATIVE", "EAGER"}; }
+
+    // The cooperative form of assign(Cluster, GroupSubscription): the same plan, offsets and lags, ONE native call
+    // (la_assign_batch_cooperative) that also joins every member's ownedPartitions against the new assignment.  Returned is
+    // the ADJUSTED assignment -- a partition that changes hands between two live members is in nobody's list this round; its
+    // owner revokes it and a follow-up rebalance (lastCooperativeRound().followup) hands it over.  A list for every member.
+    // With nothing owned anywhere it is assign().  std::invalid_argument when two members (or one, twice) claim a partition.
+    Assignment assignCooperative(const Cluster& metadata, const CooperativeSubscription& subscriptions, OffsetSource& offsets);
+
+    // What the last assignCooperative on the calling thread did.  per_member: memberId -> {kept, fresh, pending, release}
+    // (pending: what the follow-up will bring; release: what the member revokes now); topic_withheld: withheld per topic;
+    // then the call's totals (stale: owned partitions the new assignment does not have) and whether a follow-up is needed.
+    struct CooperativeRound {
+        std::map<std::string, std::array<int64_t, 4>> per_member;
+        std::map<std::string, int64_t> topic_withheld;
+        int64_t kept = 0, fresh = 0, withheld = 0, dropped = 0, stale = 0;
+        bool followup = false;
+    };
+    static CooperativeRound lastCooperativeRound();
+
     // Main.java:166-188 (package-private static in the reference; the seam its tests use).
     static Assignment assign(const OrderedMap<std::vector<TopicPartitionLag>>& partitionLagPerTopic,
                              const GroupSubscription& subscriptions);
@@ -98,6 +129,7 @@ class LagBasedPartitionAssignor {
     // Properties the side consumer would get (Main.java:116-120), for inspection/tests.
     const std::map<std::string, std::string>& metadataConsumerProps() const { return metadata_consumer_props_; }
 
+    // The accessors below describe the TARGET (the eager assignment) after assignCooperative, exactly as after assign().
     // Per-topic consumer totals of the last instance-level assign (the debug summary's
     // numbers, Main.java:279-306): topic -> (memberId -> total lag).
     const std::map<std::string, std::map<std::string, int64_t>>& lastTopicTotals() const { return last_totals_; }
@@ -143,6 +175,8 @@ class LagBasedPartitionAssignor {
     std::function<void(const std::string&)> debug;
 
  private:
+    Assignment assignImpl(const Cluster& metadata, const GroupSubscription& subscriptions, OffsetSource& offsets,
+                          const OrderedMap<std::vector<TopicPartition>>* owned);
     std::map<std::string, std::string> consumer_group_props_;
     std::map<std::string, std::string> metadata_consumer_props_;
     std::map<std::string, std::map<std::string, int64_t>> last_totals_;
@@ -152,5 +186,14 @@ class LagBasedPartitionAssignor {
 // Exposed for tests of the host-side string logic (no GPU involved).
 std::vector<int32_t> rankMembers(const std::vector<std::string>& memberIds);
 std::vector<std::string> consumersPerTopicOrder(const GroupSubscription& subscriptions);
+// The owned lists as la_assign_batch_cooperative takes them.  memberIds[i] owns ownedPerMember[i]; members are walked in
+// String.compareTo rank order (member_off[r] = entries of the ranks below r); topic[j] is the index of the owned topic in
+// `topics` (this rebalance's list), or -1 when it is not there: deleted, without metadata or subscriber -- a stale claim.
+struct OwnedArrays {
+    std::vector<int64_t> member_off;
+    std::vector<int32_t> topic, partition;
+};
+OwnedArrays cooperativeOwnedArrays(const std::vector<std::string>& memberIds, const std::vector<std::string>& topics,
+                                   const std::vector<std::vector<TopicPartition>>& ownedPerMember);
 
 }  // namespace kafka_lag

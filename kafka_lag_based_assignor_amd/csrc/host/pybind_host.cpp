@@ -81,6 +81,16 @@ PYBIND11_MODULE(_host, m) {
     m.def("equals_ignore_case_latest", &equals_ignore_case_latest);
     m.def("rank_members", &rankMembers);
     m.def("consumers_per_topic_order", &consumersPerTopicOrder);
+    m.def("cooperative_owned_arrays", [](const std::vector<std::string>& member_ids, const std::vector<std::string>& topics,
+                                         const std::vector<std::vector<PyTp>>& owned) {
+        std::vector<std::vector<TopicPartition>> per;
+        for (const auto& l : owned) {
+            per.emplace_back();
+            for (const auto& tp : l) per.back().push_back(TopicPartition{tp.first, tp.second});
+        }
+        const OwnedArrays o = cooperativeOwnedArrays(member_ids, topics, per);
+        return py::make_tuple(o.member_off, o.topic, o.partition);
+    }, py::arg("member_ids"), py::arg("topics"), py::arg("owned"));
     m.def("hashmap_put_order", [](const std::vector<std::string>& keys, py::object initial_capacity) {
         JavaHashMapOrder o = initial_capacity.is_none() ? JavaHashMapOrder()
                                                         : JavaHashMapOrder(initial_capacity.cast<size_t>());
@@ -124,6 +134,33 @@ PYBIND11_MODULE(_host, m) {
                  PyOffsetSource src(std::move(offsets));
                  return to_py(self.assign(metadata, subs, src));
              })
+        .def_static("supported_protocols", &LagBasedPartitionAssignor::supportedProtocols)
+        .def("assign_cooperative",
+             [](LagBasedPartitionAssignor& self, const Cluster& metadata,
+                const std::vector<std::tuple<std::string, std::vector<std::string>, std::vector<PyTp>>>& subs, py::object offsets) {
+                 CooperativeSubscription cs;
+                 for (const auto& e : subs) {
+                     MemberSubscription ms;
+                     ms.topics = std::get<1>(e);
+                     for (const auto& tp : std::get<2>(e)) ms.ownedPartitions.push_back(TopicPartition{tp.first, tp.second});
+                     cs.emplace_back(std::get<0>(e), std::move(ms));
+                 }
+                 PyOffsetSource src(std::move(offsets));
+                 return to_py(self.assignCooperative(metadata, cs, src));
+             })
+        .def_static("last_cooperative_round", [] {
+            const auto c = LagBasedPartitionAssignor::lastCooperativeRound();
+            py::dict d;
+            d["per_member"] = c.per_member;
+            d["topic_withheld"] = c.topic_withheld;
+            d["kept"] = c.kept;
+            d["fresh"] = c.fresh;
+            d["withheld"] = c.withheld;
+            d["dropped"] = c.dropped;
+            d["stale"] = c.stale;
+            d["followup"] = c.followup;
+            return d;
+        })
         .def_static("assign_static",
                     [](const std::vector<std::pair<std::string, std::vector<PyTpl>>>& lags, const GroupSubscription& subs) {
                         return to_py(LagBasedPartitionAssignor::assign(lags_from_py(lags), subs));

@@ -1197,8 +1197,8 @@ LA_API int la_cooperative_round_device(la_ctx* ctx, const la_coop_round_args* ar
 // The same on host buffers: the inputs packed into the shard's own staging buffer (pinned + device, both grown before anything
 // is enqueued), ONE copy in, the device call on lane 0's stream, ONE copy out, one wait.  8-byte arrays first, so every array
 // is aligned for its element.  It neither takes nor spends a pending la_hint_next_call.
-LA_API int la_cooperative_round(la_ctx* ctx, const la_coop_round_args* args) {
-    return shard_entry<true>(ctx, 0, "exception in la_cooperative_round", [&](Shard& sh) -> int {
+static int coop_round_host(la_ctx* ctx, Shard& sh, const la_coop_round_args* args) {
+    {
         la::CoopRoundCall host{};
         if (int rc = coop_round_call_of(ctx, args, &host)) return rc;
         const la::CoopCall& h = host.c;
@@ -1287,7 +1287,108 @@ LA_API int la_cooperative_round(la_ctx* ctx, const la_coop_round_args* args) {
             memcpy(host.grouped_partition, hp + o_gpart, N * 4);
         }
         return LA_OK;
-    });
+    }
+}
+
+LA_API int la_cooperative_round(la_ctx* ctx, const la_coop_round_args* args) {
+    return shard_entry<true>(ctx, 0, "exception in la_cooperative_round", [&](Shard& sh) -> int { return coop_round_host(ctx, sh, args); });
+}
+
+// A cooperative rebalance from host buffers in one call: an assign call and the round on its result.  FUSED (la_host.hip,
+// assign_small_zc): the round kernel is the zero-copy call's last launch.  GENERAL: the assign call into the context's own host
+// buffers, then the body of la_cooperative_round on them; the caller's arrays are written only after both have succeeded.
+LA_API int la_assign_batch_cooperative(la_ctx* ctx, const la_assign_coop_args* g) {
+    DeviceGuard restore_device;
+    LaunchSpan span(ctx);
+    HintSpender spend_hints(ctx);
+    if (!ctx) return LA_EINVAL;
+    try {
+        if (!g) return fail(ctx, LA_EINVAL, "args is NULL");
+        if (g->struct_size < (int32_t)sizeof(la_assign_coop_args))
+            return fail(ctx, LA_EINVAL, "la_assign_coop_args.struct_size is %d, this library takes %d and above", (int)g->struct_size, (int)sizeof(la_assign_coop_args));
+        if (g->flags & ~LA_COOP_FORCE_TABLE) return fail(ctx, LA_EINVAL, "la_assign_coop_args.flags holds a bit this library does not know");
+        if (g->reserved != 0) return fail(ctx, LA_EINVAL, "la_assign_coop_args.reserved must be 0");
+        if (g->n_topics < 0 || g->n_members < 0 || g->n_owned < 0) return fail(ctx, LA_EINVAL, "negative size");
+        if (g->n_members > la::kMovesMaxMembers) return fail(ctx, LA_EINVAL, "n_members must be below 2^30");
+        if (g->n_owned > 0 && (!g->owned_member_off || !g->owned_topic || !g->owned_partition))
+            return fail(ctx, LA_EINVAL, "null owned buffer");
+        if (!g->member_off) return fail(ctx, LA_EINVAL, "member_off is NULL");
+        const int32_t T = g->n_topics;
+        if (T > 0 && g->part_off && g->part_off[T] > 0 && !g->grouped_partition) return fail(ctx, LA_EINVAL, "grouped_partition is NULL");
+        la::CoopRoundCall q{};
+        q.c.n_topics = T;
+        q.c.n_members = g->n_members;
+        q.c.n_owned = g->n_owned;
+        q.c.owned_off = g->owned_member_off;
+        q.c.owned_topic = g->owned_topic;
+        q.c.owned_partition = g->owned_partition;
+        q.c.prev_owner = g->prev_owner;
+        q.c.coop_rank = g->coop_member_rank;
+        q.c.member_kept = g->member_kept;
+        q.c.member_fresh = g->member_fresh;
+        q.c.member_pending = g->member_pending;
+        q.c.member_release = g->member_release;
+        q.c.topic_withheld = g->topic_withheld;
+        q.c.summary = g->summary;
+        q.member_off = g->member_off;
+        q.grouped_topic = g->grouped_topic;
+        q.grouped_partition = g->grouped_partition;
+        bool done = false;
+        HostCall c;
+        c.T = T; c.part_off = g->part_off; c.pid = g->partition_id; c.cons_off = g->cons_off; c.cons_rank = g->cons_rank;
+        c.out_pid = g->out_partition; c.out_rank = g->out_member_rank; c.out_total = g->out_total_lag;
+        if (g->lag) {                                            // la_assign_batch_lags
+            c.reset_mode = LA_RESET_LATEST;
+            c.lag = g->lag;
+        } else {                                                 // la_assign_batch, or la_assign_batch_sparse without a dense begin
+            c.reset_mode = g->reset_mode; c.end = g->end_off; c.committed = g->committed_off; c.begin = g->begin_off;
+            if (!g->begin_off) { c.sparse = true; c.n_none = g->n_none; c.none_index = g->none_index; c.none_begin = g->none_begin; }
+        }
+        c.coop = &q; c.coop_force_table = (g->flags & LA_COOP_FORCE_TABLE) != 0; c.coop_done = &done;
+        if (int rc = assign_host(ctx, c)) return rc;
+        if (done) return LA_OK;
+        // the general form: the target lies in ctx->coop_target (totals | ids | ranks) -- or there is none (no topics)
+        const int64_t N = T > 0 ? g->part_off[T] : 0, K = T > 0 ? g->cons_off[T] : 0;
+        int64_t* const t_total = T > 0 ? ctx->coop_target.data() : nullptr;
+        int32_t* const t_pid = T > 0 ? (int32_t*)(t_total + K) : nullptr;
+        int32_t* const t_rank = T > 0 ? t_pid + N : nullptr;
+        la_coop_round_args ra{};
+        ra.struct_size = (int32_t)sizeof ra;
+        ra.flags = g->flags;
+        ra.adjust.struct_size = (int32_t)sizeof ra.adjust;
+        ra.adjust.n_topics = T;
+        ra.adjust.n_partitions = N;
+        ra.adjust.d_part_off = g->part_off;
+        ra.adjust.d_out_partition = t_pid;
+        ra.adjust.d_out_member_rank = t_rank;
+        ra.adjust.n_members = g->n_members;
+        ra.adjust.n_owned = g->n_owned;
+        ra.adjust.d_owned_member_off = g->owned_member_off;
+        ra.adjust.d_owned_topic = g->owned_topic;
+        ra.adjust.d_owned_partition = g->owned_partition;
+        ra.adjust.d_prev_owner = g->prev_owner;
+        ra.adjust.d_coop_member_rank = g->coop_member_rank;
+        ra.adjust.d_member_kept = g->member_kept;
+        ra.adjust.d_member_fresh = g->member_fresh;
+        ra.adjust.d_member_pending = g->member_pending;
+        ra.adjust.d_member_release = g->member_release;
+        ra.adjust.d_topic_withheld = g->topic_withheld;
+        ra.adjust.d_summary = g->summary;
+        ra.member_off = g->member_off;
+        ra.grouped_topic = g->grouped_topic;
+        ra.grouped_partition = g->grouped_partition;
+        Shard& sh = ctx->shards[0];
+        LA_HIP(ctx, hipSetDevice(sh.device));
+        if (int rc = coop_round_host(ctx, sh, &ra)) return rc;
+        if (g->out_total_lag && K > 0) memcpy(g->out_total_lag, t_total, (size_t)K * 8);
+        if (g->out_partition && N > 0) {
+            memcpy(g->out_partition, t_pid, (size_t)N * 4);
+            memcpy(g->out_member_rank, t_rank, (size_t)N * 4);
+        }
+        return LA_OK;
+    } catch (...) {
+        return fail(ctx, LA_ENOMEM, "exception in la_assign_batch_cooperative");
+    }
 }
 
 LA_API int la_group_by_member(la_ctx* ctx, int32_t n_topics, const int64_t* part_off, const int32_t* out_partition,

@@ -98,4 +98,13 @@ inline bool coop_round_is_small(const CoopCall& c) {
 hipError_t cooperative_round_launch(CoopScratch& s, LargeScratch& large, const CoopRoundCall& r, bool force_table, uint32_t* status,
                                     hipStream_t stream);
 
+// The round as the LAST launch of a zero-copy host call (la_assign_batch_cooperative, fused form): the one-workgroup kernel in its
+// finishing form.  `r` must be within coop_round_is_small; r.c.out_partition / out_member_rank are the target in DEVICE memory,
+// every other pointer of `r`, target_partition / target_rank (both or neither: the target as the caller wants it) and fin_flag lie
+// in the call's mapped staging buffer.  The kernel reads `status` (the lane's device word, where the assignment kernels left their
+// bits), adds the round's own, puts the word back to zero and stores `0x80000000 | bits` into fin_flag after everything else.
+// Exactly one launch; hipErrorInvalidValue, with nothing enqueued, for a call outside the limits.
+hipError_t cooperative_round_finish_launch(const CoopRoundCall& r, int32_t* target_partition, int32_t* target_rank,
+                                           uint32_t* status, uint32_t* fin_flag, hipStream_t stream);
+
 }  // namespace la

@@ -24,8 +24,15 @@
 //            one it has: chunks in order by in-order returning LDS atomics, no spin, no wait on another thread.
 //
 // Any other call -- or one with LA_COOP_FORCE_TABLE -- is cooperative_adjust_launch followed by group_by_member_launch.
+//
+// The kernel has a second, FINISHING form (kFinish: la_assign_batch_cooperative, fused): the last launch of a
+// zero-copy host call.  The target comes from device memory, the offsets, the owned arrays and every output lie in the call's
+// mapped staging buffer, the target is handed on to the host from the stage phase where it is wanted, and the launch ends with
+// `done | status` in the word the calling thread spins on.  kFinish == false is the kernel as it was.
 #include "la_moves_shared.h"
 #include "la_coop.h"
+
+#include <type_traits>
 
 namespace la {
 
@@ -72,7 +79,16 @@ struct CoopSmallArgs {
     int32_t bits;               // the table has 1 << bits slots (n_owned > 0)
 };
 
-__global__ __launch_bounds__(NT) void coop_round_small_kernel(CoopSmallArgs a) {
+// The finishing form (la_assign_batch_cooperative, fused: la_host.hip, assign_small_zc).  The target lies in device memory, the
+// part offsets, the owned arrays and EVERY output in the call's staging buffer -- coherent host memory mapped into the device,
+// read and written in place over the link -- and the launch is the call's last: it ends with `done | status` in fin_flag.
+struct CoopSmallFinishArgs : CoopSmallArgs {
+    int32_t *target_partition, *target_rank;      // [N] in the staging buffer, or both null: the target as the caller wants it
+    uint32_t* fin_flag;                            // host word the calling thread spins on
+};
+
+template <bool kFinish>
+__global__ __launch_bounds__(NT) void coop_round_small_kernel(std::conditional_t<kFinish, CoopSmallFinishArgs, CoopSmallArgs> a) {
     extern __shared__ uint64_t coop_small_lds[];
     char* const lds = reinterpret_cast<char*>(coop_small_lds);
     int64_t* const l_part_off = reinterpret_cast<int64_t*>(lds + kOffPartOff);
@@ -100,9 +116,23 @@ __global__ __launch_bounds__(NT) void coop_round_small_kernel(CoopSmallArgs a) {
     for (int k = tid; k < T; k += NT) held[k] = 0;
     for (int k = tid; k < N; k += NT) e_topic[k] = 0;
     if (tid < 8) misc[tid] = 0;
-    for (int i = tid; i < N; i += NT) {
-        e_pid[i] = c.out_partition[i];
-        e_rank[i] = c.out_member_rank[i];
+    if constexpr (!kFinish) {
+        for (int i = tid; i < N; i += NT) {
+            e_pid[i] = c.out_partition[i];
+            e_rank[i] = c.out_member_rank[i];
+        }
+    } else {
+        // the target on its way from device memory to LDS: where the caller wants it, it goes to the staging buffer from here,
+        // while the thread holds both words (afterwards the adjusted rank overwrites the LDS copy) -- no trip of its own
+        for (int i = tid; i < N; i += NT) {
+            const int32_t id = c.out_partition[i], rank = c.out_member_rank[i];
+            e_pid[i] = id;
+            e_rank[i] = rank;
+            if (a.target_partition) {
+                a.target_partition[i] = id;
+                a.target_rank[i] = rank;
+            }
+        }
     }
     if (Tn > 0)
         for (int t = tid; t <= Tn; t += NT) l_part_off[t] = c.part_off[t];
@@ -265,7 +295,8 @@ __global__ __launch_bounds__(NT) void coop_round_small_kernel(CoopSmallArgs a) {
                 c.summary[4] = (int64_t)misc[kSumClaimed] - (k + w + d);      // claimed - hits = stale
                 c.summary[5] = w + d > 0 ? 1 : 0;
             }
-            if (misc[kSumBad]) atomicOr(a.status, misc[kSumBad]);
+            if constexpr (!kFinish)
+                if (misc[kSumBad]) atomicOr(a.status, misc[kSumBad]);
         }
     }
     __syncthreads();                                                 // (the table and the counters are done with: the lists take their LDS)
@@ -277,6 +308,21 @@ __global__ __launch_bounds__(NT) void coop_round_small_kernel(CoopSmallArgs a) {
                                              a.r.grouped_partition, nullptr, reinterpret_cast<uint32_t*>(lds + kOffStart),
                                              misc + kWsum, misc + kTurn, l, l + E, l + 2 * E, l + 3 * E, l + 4 * E,
                                              reinterpret_cast<uint32_t*>(l + 5 * E), reinterpret_cast<uint32_t*>(l + 6 * E));
+    if constexpr (kFinish) {
+        // The call ends here, in the order of the finishing form of group_small_kernel (la_large.hip): every thread releases
+        // what it stored into the host's memory, the workgroup meets, ONE thread stores `done | status` where the calling thread
+        // spins.  The status is what the assignment kernels left in the lane's device word plus this round's own bits (kept in
+        // LDS: the list builder leaves the misc words below kWsum alone but for its turn counter); the device word goes back to
+        // zero HERE, so a call that ends in an error leaves nothing behind for the next one.  The host copies the outputs out
+        // of the staging buffer only when the status is zero: that alone leaves the caller's arrays untouched on an error.
+        __threadfence_system();
+        __syncthreads();
+        if (tid == 0) {
+            uint32_t st = __hip_atomic_load(a.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) | misc[kSumBad];
+            if (st) __hip_atomic_store(a.status, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(a.fin_flag, 0x80000000u | st, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+    }
 }
 
 }  // namespace
@@ -291,11 +337,11 @@ hipError_t cooperative_round_launch(CoopScratch& s, LargeScratch& large, const C
         a.bits = r.c.n_owned > 0 ? ceil_log2(2 * r.c.n_owned) : 1;
         static PerDeviceOnce lds_opt_in;
         if ((e = lds_opt_in.run([] {
-                 return hipFuncSetAttribute((const void*)coop_round_small_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                 return hipFuncSetAttribute((const void*)coop_round_small_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                             (int)kCoopSmallLdsBytes);
              })) != hipSuccess)
             return e;
-        LA_LAUNCH(coop_round_small_kernel, dim3(1), dim3(NT), kCoopSmallLdsBytes, stream, a);
+        LA_LAUNCH(coop_round_small_kernel<false>, dim3(1), dim3(NT), kCoopSmallLdsBytes, stream, a);
         return hipGetLastError();
     }
     // the general form: the table in device memory, then the grouping of the adjusted ranks
@@ -308,6 +354,28 @@ hipError_t cooperative_round_launch(CoopScratch& s, LargeScratch& large, const C
     if ((e = cooperative_adjust_launch(s, c, status, stream)) != hipSuccess) return e;
     return group_by_member_launch(large, c.n_partitions, c.n_members, c.n_topics, c.part_off, c.out_partition, c.coop_rank,
                                   r.member_off, r.grouped_topic, r.grouped_partition, nullptr, status, stream);
+}
+
+// The finishing form: `r` within coop_round_is_small, the target in device memory, everything else (and fin_flag) in the mapped
+// staging buffer of a zero-copy call.  Exactly one launch, nothing else enqueued.
+hipError_t cooperative_round_finish_launch(const CoopRoundCall& r, int32_t* target_partition, int32_t* target_rank,
+                                           uint32_t* status, uint32_t* fin_flag, hipStream_t stream) {
+    if (!coop_round_is_small(r.c) || !fin_flag || (target_partition == nullptr) != (target_rank == nullptr)) return hipErrorInvalidValue;
+    CoopSmallFinishArgs a{};
+    a.r = r;
+    a.status = status;
+    a.bits = r.c.n_owned > 0 ? ceil_log2(2 * r.c.n_owned) : 1;
+    a.target_partition = target_partition;
+    a.target_rank = target_rank;
+    a.fin_flag = fin_flag;
+    static PerDeviceOnce lds_opt_in;
+    const hipError_t e = lds_opt_in.run([] {
+        return hipFuncSetAttribute((const void*)coop_round_small_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   (int)kCoopSmallLdsBytes);
+    });
+    if (e != hipSuccess) return e;
+    LA_LAUNCH(coop_round_small_kernel<true>, dim3(1), dim3(NT), kCoopSmallLdsBytes, stream, a);
+    return hipGetLastError();
 }
 
 }  // namespace la

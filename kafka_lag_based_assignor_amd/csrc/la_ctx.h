@@ -229,6 +229,7 @@ struct la_ctx {
     la_call_hints hints{};               // la_hint_next_call: what the caller knows about its next host-buffer assign call
     bool hints_set = false;              // (one-shot: assign_host takes them and clears the flag)
     int64_t last_launches = 0;           // kernel launches of the last call (la_last_launches)
+    std::vector<int64_t> coop_target;    // la_assign_batch_cooperative, general form: the target (ids, ranks, totals) before the round
 };
 
 // Kernel launches between construction and destruction, left in the context for la_last_launches (the outermost span of a
@@ -416,6 +417,13 @@ struct HostCall {
     // la_hint_next_call: the caller's bounds on every lag and partition id of the call (LA_FLAG_BOUNDS of every chunk's batch)
     bool bounded = false;
     int64_t max_lag = 0, max_id = 0;
+    // la_assign_batch_cooperative: the owned lists and the round's outputs, all HOST memory (coop->c.part_off / out_partition /
+    // out_member_rank and n_partitions are not looked at: they are this call's).  A zero-copy staged call within the limits of
+    // la_coop.h ends in the round kernel's finishing form and sets *coop_done; any other call is a plain assign call that leaves
+    // *coop_done alone -- the entry point then runs the round on its results.
+    const la::CoopRoundCall* coop = nullptr;
+    bool coop_force_table = false;
+    bool* coop_done = nullptr;
 };
 
 void plan_ranges(const int64_t* po, int32_t t_begin, int32_t t_end, int parts, int32_t* bounds);

@@ -489,6 +489,9 @@ constexpr size_t kSmallHostCheck = 16384;      // consumer entries up to which t
 
 struct SmallLayout {
     size_t po, co, pid, end, com, beg, cr, status, ot, goff, gt, gp, op, orank, total;
+    // la_assign_batch_cooperative, fused form (carved for such a call only: every other call's layout is what it was): the owned
+    // arrays on the upload side of the status word, the round's counting outputs and per-entry outputs on the download side
+    size_t oo, otp, opp, cnt[4], held, sum, prev, coop;
 };
 
 SmallLayout small_layout(const HostCall& c) {
@@ -503,12 +506,32 @@ SmallLayout small_layout(const HostCall& c) {
     L.com = carve(c.lag ? 0 : n * 8);
     L.beg = carve(c.use_begin ? n * 8 : 0);
     L.cr = carve(k * 4);
+    const la::CoopRoundCall* q = c.coop;
+    if (q) {
+        const size_t no = (size_t)q->c.n_owned;
+        L.oo = carve(no ? ((size_t)q->c.n_members + 1) * 8 : 0);
+        L.otp = carve(no * 4);
+        L.opp = carve(no * 4);
+    }
     L.status = carve(256);                                    // last word of the upload, first of the download
     L.ot = carve(k * 8);
     const bool grouped = c.g_members >= 0;                    // la_assign_batch_grouped: the CSR rides in the same download
-    L.goff = carve(grouped ? ((size_t)c.g_members + 1) * 8 : 0);
-    L.gt = carve(grouped && c.g_topic ? n * 4 : 0);
-    L.gp = carve(grouped ? n * 4 : 0);
+    if (q) {                                                  // the lists of the ADJUSTED assignment take the CSR's place
+        const size_t M = (size_t)q->c.n_members;
+        L.goff = carve((M + 1) * 8);
+        L.gt = carve(q->grouped_topic ? n * 4 : 0);
+        L.gp = carve(n * 4);
+        int64_t* const want[4] = {q->c.member_kept, q->c.member_fresh, q->c.member_pending, q->c.member_release};
+        for (int w = 0; w < 4; ++w) L.cnt[w] = carve(want[w] ? M * 8 : 0);
+        L.held = carve(q->c.topic_withheld ? T * 8 : 0);
+        L.sum = carve(q->c.summary ? 6 * 8 : 0);
+        L.prev = carve(q->c.prev_owner ? n * 4 : 0);
+        L.coop = carve(q->c.coop_rank ? n * 4 : 0);
+    } else {
+        L.goff = carve(grouped ? ((size_t)c.g_members + 1) * 8 : 0);
+        L.gt = carve(grouped && c.g_topic ? n * 4 : 0);
+        L.gp = carve(grouped ? n * 4 : 0);
+    }
     L.op = carve(n * 4);
     L.orank = carve(n * 4);
     L.total = off;
@@ -598,6 +621,12 @@ int small_fill_inputs(la_ctx* ctx, const HostCall& c, const SmallLayout& L, char
         }
     }
     if (k) memcpy(h + L.cr, c.cons_rank, k * 4);
+    if (c.coop && c.coop->c.n_owned > 0) {
+        const la::CoopCall& q = c.coop->c;
+        memcpy(h + L.oo, q.owned_off, ((size_t)q.n_members + 1) * 8);
+        memcpy(h + L.otp, q.owned_topic, (size_t)q.n_owned * 4);
+        memcpy(h + L.opp, q.owned_partition, (size_t)q.n_owned * 4);
+    }
     if (k && k <= kSmallHostCheck) {
         // a topic's member ranks must be strictly ascending (the kernels compare ranks, never strings).  A few thousand
         // entries are checked here in less time than the ~5 us a dependent launch of the check kernel puts in front of
@@ -666,6 +695,53 @@ hipError_t small_group_launch(const HostCall& c, Lane& ln, const SmallLayout& L,
                                       status, st, fin_flag, finished);
 }
 
+// la_assign_batch_cooperative, fused form: the round of a zero-copy call as its last launch.  The target at d (device memory),
+// the part offsets and the owned arrays at m (the device's view of the staging buffer), every output to m, the completion word
+// where the calling thread spins.
+hipError_t small_coop_launch(const HostCall& c, Lane& ln, const SmallLayout& L, char* m, const char* d, hipStream_t st) {
+    const la::CoopRoundCall& q = *c.coop;
+    la::CoopRoundCall r = q;
+    r.c.n_topics = c.T;
+    r.c.n_partitions = c.shape.n;
+    r.c.part_off = (const int64_t*)(m + L.po);
+    r.c.out_partition = (const int32_t*)(d + L.op);
+    r.c.out_member_rank = (const int32_t*)(d + L.orank);
+    const bool owned = q.c.n_owned > 0;
+    r.c.owned_off = owned ? (const int64_t*)(m + L.oo) : nullptr;
+    r.c.owned_topic = owned ? (const int32_t*)(m + L.otp) : nullptr;
+    r.c.owned_partition = owned ? (const int32_t*)(m + L.opp) : nullptr;
+    r.c.member_kept = q.c.member_kept ? (int64_t*)(m + L.cnt[0]) : nullptr;
+    r.c.member_fresh = q.c.member_fresh ? (int64_t*)(m + L.cnt[1]) : nullptr;
+    r.c.member_pending = q.c.member_pending ? (int64_t*)(m + L.cnt[2]) : nullptr;
+    r.c.member_release = q.c.member_release ? (int64_t*)(m + L.cnt[3]) : nullptr;
+    r.c.topic_withheld = q.c.topic_withheld ? (int64_t*)(m + L.held) : nullptr;
+    r.c.summary = q.c.summary ? (int64_t*)(m + L.sum) : nullptr;
+    r.c.prev_owner = q.c.prev_owner ? (int32_t*)(m + L.prev) : nullptr;
+    r.c.coop_rank = q.c.coop_rank ? (int32_t*)(m + L.coop) : nullptr;
+    r.member_off = (int64_t*)(m + L.goff);
+    r.grouped_topic = q.grouped_topic ? (int32_t*)(m + L.gt) : nullptr;
+    r.grouped_partition = (int32_t*)(m + L.gp);
+    return la::cooperative_round_finish_launch(r, c.out_pid ? (int32_t*)(m + L.op) : nullptr, c.out_pid ? (int32_t*)(m + L.orank) : nullptr,
+                                               ln.d_status, (uint32_t*)(m + L.status), st);
+}
+
+// ... and its outputs, from the host side of the staging buffer into the caller's arrays (only ever after a status of zero)
+void small_coop_unpack(const HostCall& c, const SmallLayout& L, const char* h) {
+    const la::CoopRoundCall& q = *c.coop;
+    const size_t n = (size_t)c.shape.n, M = (size_t)q.c.n_members, T = (size_t)c.T;
+    memcpy(q.member_off, h + L.goff, (M + 1) * 8);
+    memcpy(q.grouped_partition, h + L.gp, n * 4);
+    if (q.grouped_topic) memcpy(q.grouped_topic, h + L.gt, n * 4);
+    int64_t* const want[4] = {q.c.member_kept, q.c.member_fresh, q.c.member_pending, q.c.member_release};
+    for (int w = 0; w < 4; ++w)
+        if (want[w] && M) memcpy(want[w], h + L.cnt[w], M * 8);
+    if (q.c.topic_withheld && T) memcpy(q.c.topic_withheld, h + L.held, T * 8);
+    if (q.c.summary) memcpy(q.c.summary, h + L.sum, 6 * 8);
+    if (q.c.prev_owner) memcpy(q.c.prev_owner, h + L.prev, n * 4);
+    if (q.c.coop_rank) memcpy(q.c.coop_rank, h + L.coop, n * 4);
+    *c.coop_done = true;
+}
+
 int assign_small_zc(la_ctx* ctx, const HostCall& c, Shard& sh, const SmallLayout& L) {
     LA_HIP(ctx, hipSetDevice(sh.device));
     Lane& ln = sh.lanes[0];
@@ -687,7 +763,8 @@ int assign_small_zc(la_ctx* ctx, const HostCall& c, Shard& sh, const SmallLayout
     const bool grouped = c.g_members >= 0;
     // results the caller reads go to the host's memory; those only the grouping reads stay on the device.  The totals: only
     // when the caller wants them
-    char* res = (c.out_pid && !grouped) ? m : d;
+    // (a cooperative call: the round reads the target on the device and hands it on to the host itself where it is wanted)
+    char* res = (c.out_pid && !grouped && !c.coop) ? m : d;
     const la_device_batch b = small_batch(c, L, m, res, c.out_total ? m : nullptr);
     // ONE launch for the whole rebalance where the batch is one resident tile launch: its last workgroup builds the lists and
     // stores the completion word -- otherwise the grouping / finishing launches below.  Where that pays was measured at the C
@@ -703,7 +780,7 @@ int assign_small_zc(la_ctx* ctx, const HostCall& c, Shard& sh, const SmallLayout
                                          (int64_t)c.g_members + 2 <= la::kTailGroupM)
                                       : tail_all;
     ln.tail_done = false;
-    ln.tail_wanted = one_wg_lists && !no_tail && k <= kSmallHostCheck;
+    ln.tail_wanted = one_wg_lists && !no_tail && k <= kSmallHostCheck && !c.coop;      // (the round is its own 1 024-thread launch)
     if (ln.tail_wanted) {
         ln.tail = la::TileTail{};
         ln.tail.enabled = 1;
@@ -726,6 +803,11 @@ int assign_small_zc(la_ctx* ctx, const HostCall& c, Shard& sh, const SmallLayout
     if (rc == LA_OK && grouped && !finished) {
         const hipError_t e = small_group_launch(c, ln, L, m, d, m, ln.d_status, st, (uint32_t*)(m + L.status), &finished);
         if (e != hipSuccess) rc = hip_fail(ctx, e, "group_by_member: %s");
+    }
+    if (rc == LA_OK && c.coop) {
+        const hipError_t e = small_coop_launch(c, ln, L, m, d, st);
+        if (e != hipSuccess) rc = hip_fail(ctx, e, "cooperative_round: %s");
+        finished = true;
     }
     if (rc == LA_OK && !finished) {
         const hipError_t e = la::finish_status_launch(ln.d_status, (uint32_t*)(m + L.status), st);
@@ -776,6 +858,7 @@ int assign_small_zc(la_ctx* ctx, const HostCall& c, Shard& sh, const SmallLayout
     }
     // what la_group_last_by_member would read: valid only where the results stayed on the device
     small_unpack(ctx, c, sh, L, h, /*pieces=*/true, m, res);
+    if (c.coop) small_coop_unpack(c, L, h);
     return LA_OK;
 }
 
@@ -924,7 +1007,24 @@ int assign_host(la_ctx* ctx, HostCall& c) {
     if (S > T) S = T;
     plan_ranges(part_off, 0, T, S, ctx->last_bounds);
     ctx->last_shards = S;
-    if (S == 1 && !ctx->split_always && s.n > 0) {
+    const bool may_stage = S == 1 && !ctx->split_always && s.n > 0;
+    // la_assign_batch_cooperative.  FUSED: a zero-copy staged call within the round kernel's limits.  Anything else is the
+    // GENERAL form: this call is then a plain assign call into buffers of the context's own (totals | ids | ranks), and the entry
+    // point runs the round on them -- the caller's arrays see nothing before both have succeeded.
+    auto coop_general = [&] {
+        ctx->coop_target.resize((size_t)s.k + (size_t)s.n + 1);
+        c.out_total = ctx->coop_target.data();
+        c.out_pid = (int32_t*)(ctx->coop_target.data() + s.k);
+        c.out_rank = c.out_pid + s.n;
+        c.coop = nullptr;
+    };
+    if (c.coop) {
+        la::CoopCall probe = c.coop->c;
+        probe.n_topics = T;
+        probe.n_partitions = s.n;
+        if (!may_stage || c.coop_force_table || !la::coop_round_is_small(probe)) coop_general();
+    }
+    if (may_stage) {
         SmallLayout L = small_layout(c);
         // How large a layout still travels through ONE staging buffer.  Pageable caller arrays: ctx->small_bytes (12 MB) -- beyond,
         // packing the inputs costs as much as the lanes' overlapped copies.  Caller arrays that are pinned
@@ -942,6 +1042,11 @@ int assign_host(la_ctx* ctx, HostCall& c) {
             return upto;
         };
         size_t upto = staged_upto(c.g_members >= 0);
+        if (c.coop && (L.total > upto || L.total > ctx->zero_copy_bytes)) {
+            coop_general();
+            L = small_layout(c);
+            upto = staged_upto(false);
+        }
         if (L.total > upto && c.g_members >= 0) {            // too large with the lists aboard: they take their own round trip
             c.g_members = -1;
             L = small_layout(c);

@@ -519,6 +519,17 @@ def cooperative_round_numpy(part_off, out_partition, out_member_rank, n_members:
     return adjusted + owned_after_round(part_off, out_partition, adjusted[1], n_members)
 
 
+def assign_cooperative_numpy(part_off, partition_id, lag, cons_off, cons_rank, n_members: int, owned_off, owned_topic,
+                             owned_partition, *, assign):
+    """la_assign_batch_cooperative restated on the host: cooperative_round_numpy over the target that
+    assign(part_off, partition_id, lag, cons_off, cons_rank) -> (out_partition, out_member_rank, totals) produced -> those three
+    followed by the eleven outputs of cooperative_round_numpy.  `assign` is the caller's restatement of the assign call (the
+    tests pass the reference oracle's); ValueError as cooperative_adjust_numpy.  The yardstick of tests/test_assign_coop_gpu.py."""
+    out_partition, out_member_rank, totals = assign(part_off, partition_id, lag, cons_off, cons_rank)
+    return (out_partition, out_member_rank, totals) + cooperative_round_numpy(
+        part_off, out_partition, out_member_rank, n_members, owned_off, owned_topic, owned_partition)
+
+
 def reduce_member_loads(partitions, lag, unassigned, group=None):
     """Partial roll-ups of the ranks' shards -> the group-wide roll-up on every rank: ONE all_reduce(SUM) over a single int64
     tensor of 2 * M + 1 entries (shards are disjoint topic ranges, so the sum of the partial roll-ups IS the roll-up; int64
