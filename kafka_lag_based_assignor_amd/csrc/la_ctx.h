@@ -296,12 +296,14 @@ inline void release(DevBuf& b) {
 inline int status_error(la_ctx* ctx, uint32_t st) {
     if (st & la::kStatusInternal)
         return fail(ctx, LA_EHIP, "internal error: a radix-sort look-back gave up waiting for an earlier tile, or a hash-table walk found neither its key nor an empty slot");
+    // (before kStatusOrder: the bounds decide which radix passes are launched at all, so a partition outside them whose lag or
+    // id reaches into a digit that was ruled out leaves the sort out of order as well -- the caller's error, not an internal one)
+    if (st & la::kStatusBounds)
+        return fail(ctx, LA_EINVAL, "a lag or a partition id lies outside the bounds the caller gave (la_hint_next_call / LA_FLAG_BOUNDS)");
     if (st & la::kStatusOrder)
         return fail(ctx, LA_EHIP, "internal error: a device radix sort left its result out of order");
     if (st & la::kStatusUnsorted)
         return fail(ctx, LA_EINVAL, "a topic's cons_rank segment is not strictly ascending");
-    if (st & la::kStatusBounds)
-        return fail(ctx, LA_EINVAL, "a lag or a partition id lies outside the bounds the caller gave (la_hint_next_call / LA_FLAG_BOUNDS)");
     if (st & la::kStatusSparse)
         return fail(ctx, LA_EINVAL, "none_index must hold ascending positions inside the batch");
     if (st & la::kStatusWire)
