@@ -12,10 +12,9 @@
 //   1. count the entries of every group (group = member rank + 1; 0 = topics without consumers), exclusive scan -> cursors;
 //   2. chunks of 64 consecutive entries, chunk c to wavefront c % (NT / 64): inside a chunk every lane finds its peers (the lanes
 //      with the same group: one ballot per group-id bit) -- its rank among them and, for the first of them, their number;
-//   3. the chunks take their places IN ORDER: wavefront-ordered hand-over -- a wavefront's turn waits until `turn` says its
-//      predecessor has advanced the cursors, its group leaders advance them by their peers' counts (one LDS atomic per chunk,
-//      back to back), it passes the turn on.  Turn t - 1 belongs to another wavefront of the same workgroup that waits for
-//      nothing later: no deadlock; the ordered section is a few atomic instructions per chunk.
+//   3. the chunks take their places IN ORDER: every wavefront walks all chunks for its own share of the groups and advances
+//      their cursors by the chunk's counts; an entry's place is its group's cursor at its chunk's turn + its rank among its peers
+//      (steps B and C of group_small_body_staged).  No wavefront waits for another.
 // Stable by construction (chunk order, then lane order), no reliance on how colliding lanes of an atomic are served.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -51,133 +50,13 @@ constexpr int kSmallGroupBits = 13;      // bits of a group id
 constexpr int kTailMaxEntries = 1024;    // entries up to which a zero-copy call fuses its lists into the tile kernel (la_host.hip, assign_small_zc)
 constexpr int kTailGroupM = 2048;        // groups (members + 2) the tile kernel's tail holds (8 KB of LDS beside the tiles' slices)
 
-// A TURN is kSub consecutive chunks of one wavefront: their ranks are found first, side by side; inside the turn the wavefront's
-// cursor atomics go out back to back (LDS executes one wavefront's operations in order), so the ordered hand-over -- ~0.4 us per
-// turn -- is paid once per kSub * 64 entries.  kSub = 1 is what runs (every wavefront gets work); 4 was measured 2-3 us slower at
-// every size the kernel is used for (lab builds with -DLA_GROUP_SUB=4).
-// topic_of (may be null): the topic of every entry, already worked out (LDS); otherwise a binary search over part_off per entry.
-template <int kSub, int NT>
-__device__ __forceinline__ void group_small_place(int n, uint32_t G, int64_t n_topics, const int64_t* part_off, const int32_t* out_partition,
-                                                  const int32_t* member_rank, int32_t* grouped_topic, int32_t* grouped_partition,
-                                                  int32_t* grouped_entry, uint32_t* start, uint32_t* turn_p, int lane, int wave,
-                                                  const int32_t* topic_of = nullptr) {
-    uint32_t& turn = *turn_p;
-    const uint64_t below = ((uint64_t)1 << lane) - 1;
-    const int n_turns = (n + kSub * kWave - 1) / (kSub * kWave);
-    for (int turn_i = wave; turn_i < n_turns; turn_i += NT / kWave) {
-        uint32_t gi[kSub], rank[kSub], cnt[kSub], first[kSub];
-        int leader[kSub];
-        int32_t part[kSub], topic[kSub];
-        bool valid[kSub];
-#pragma unroll
-        for (int u = 0; u < kSub; ++u) {
-            const int i = (turn_i * kSub + u) * kWave + lane;
-            valid[u] = i < n;
-            gi[u] = 0;
-            part[u] = 0;
-            if (valid[u]) {
-                gi[u] = (uint32_t)(member_rank[i] + 1);
-                gi[u] = gi[u] < G ? gi[u] : G;
-                part[u] = out_partition ? out_partition[i] : 0;
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < kSub; ++u) {
-            uint64_t peers = __ballot(valid[u]);
-#pragma unroll
-            for (int bit = 0; bit < kSmallGroupBits + 1; ++bit) {       // (G itself may need one bit more than G - 1)
-                const bool one = (gi[u] >> bit) & 1u;
-                const uint64_t bal = __ballot(one);
-                peers &= one ? bal : ~bal;
-            }
-            rank[u] = (uint32_t)__popcll(peers & below);
-            cnt[u] = (uint32_t)__popcll(peers);
-            leader[u] = __ffsll((unsigned long long)peers) - 1;
-            topic[u] = 0;
-            if (valid[u] && grouped_topic && topic_of) {
-                topic[u] = topic_of[(turn_i * kSub + u) * kWave + lane];
-            } else if (valid[u] && grouped_topic) {
-                const int64_t i = (int64_t)(turn_i * kSub + u) * kWave + lane;
-                int64_t lo = 0, hi = n_topics;                         // largest t with part_off[t] <= i
-                while (hi - lo > 1) {
-                    const int64_t mid = (lo + hi) >> 1;
-                    if (part_off[mid] <= i) lo = mid; else hi = mid;
-                }
-                topic[u] = (int32_t)lo;
-            }
-        }
-        // the ordered section: wait for the turn before this one, advance the cursors, pass the turn on
-        while (__hip_atomic_load(&turn, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) != (uint32_t)turn_i) __builtin_amdgcn_s_sleep(1);
-#pragma unroll
-        for (int u = 0; u < kSub; ++u) {
-            first[u] = 0;
-            if (valid[u] && lane == leader[u]) first[u] = atomicAdd(&start[gi[u]], cnt[u]);
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        if (lane == 0) __hip_atomic_store(&turn, (uint32_t)turn_i + 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-#pragma unroll
-        for (int u = 0; u < kSub; ++u) {
-            const uint32_t f = (uint32_t)__shfl((int)first[u], leader[u] < 0 ? 0 : leader[u]);
-            if (valid[u]) {
-                const int i = (turn_i * kSub + u) * kWave + lane;
-                const uint32_t pos = f + rank[u];
-                if (grouped_entry) grouped_entry[pos] = i;
-                if (grouped_partition) grouped_partition[pos] = part[u];
-                if (grouped_topic) grouped_topic[pos] = topic[u];
-            }
-        }
-    }
-}
-
 // The whole grouping by one workgroup of NT threads (every thread of it calls this).  start: [M] words of LDS, wsum: [NT / 64],
-// turn: one word.  Needs n_members + 2 <= M and n_members + 1 < 2^(kSmallGroupBits + 1).
-template <int NT, int M, int kSub = 1>
-__device__ __forceinline__ void group_small_body(int n, int32_t n_members, int64_t n_topics, const int64_t* part_off,
-                                                 const int32_t* out_partition, const int32_t* member_rank, int64_t* member_off,
-                                                 int32_t* grouped_topic, int32_t* grouped_partition, int32_t* grouped_entry,
-                                                 uint32_t* start, uint32_t* wsum, uint32_t* turn) {
-    static_assert(M % NT == 0 && NT % kWave == 0, "M counters over NT threads");
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const uint32_t G = (uint32_t)n_members + 1;                      // a rank >= n_members (out of contract) sorts behind every
-                                                                       // member, as in member_emit_kernel: member_off[n_members]
-    for (int k = tid; k < M; k += NT) start[k] = 0;                   // is then where such entries start
-    if (tid == 0) *turn = 0;
-    __syncthreads();
-    for (int i = tid; i < n; i += NT) {
-        uint32_t gi = (uint32_t)(member_rank[i] + 1);
-        gi = gi < G ? gi : G;
-        atomicAdd(&start[gi], 1u);
-    }
-    __syncthreads();
-    // exclusive scan over the M counts: M / NT per thread, a wavefront scan, the wavefronts' sums
-    constexpr int PER = M / NT;
-    uint32_t c[PER], run = 0;
-#pragma unroll
-    for (int r = 0; r < PER; ++r) { c[r] = start[PER * tid + r]; run += c[r]; }
-    uint32_t incl = run;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t y = __shfl_up(incl, o);
-        if (lane >= o) incl += y;
-    }
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    uint32_t base = incl - run;
-    for (int w = 0; w < wave; ++w) base += wsum[w];
-#pragma unroll
-    for (int r = 0; r < PER; ++r) { start[PER * tid + r] = base; base += c[r]; }
-    __syncthreads();
-    // member r's list starts where the groups 0 .. r end; positions before member_off[0] belong to topics without consumers
-    for (int k = tid; k <= n_members; k += NT) member_off[k] = (int64_t)start[k + 1];
-    __syncthreads();                                                    // (the cursors move from here on)
-    group_small_place<kSub, NT>(n, G, n_topics, part_off, out_partition, member_rank, grouped_topic, grouped_partition, grouped_entry,
-                                start, turn, lane, wave);
-}
-
-// ---- the same with the inputs staged in LDS first ---------------------------------------------------------------------------
-// The chunks of the placement above are DEPENDENT round trips per wavefront: the loads of a chunk's ranks and partition ids
-// (one trip to HBM each) and a binary search over part_off per entry -- log2(T) trips, to HOST memory over PCIe (~1.5 us each)
-// in a zero-copy call -- eight chunks deep per wavefront in the 256-thread tail: 20 us for 2 000 entries.  Here every global
+// turn: one word.  Needs n_members + 2 <= M and n_members + 1 < 2^(kSmallGroupBits + 1).  A rank >= n_members (out of contract)
+// sorts behind every member, as in member_emit_kernel: member_off[n_members] is then where such entries start.
+// The inputs are staged in LDS first.  Placing chunk by chunk straight from global memory is a chain of DEPENDENT round trips
+// per wavefront: the loads of a chunk's ranks and partition ids (one trip to HBM each) and a binary search over part_off per
+// entry -- log2(T) trips, to HOST memory over PCIe (~1.5 us each) in a zero-copy call -- eight chunks deep per wavefront in
+// the 256-thread tail: 20 us for 2 000 entries.  Here every global
 // input is read ONCE, coalesced, all loads of a thread issued back to back: ranks and ids into LDS, and the topic of every
 // entry from ONE pass over part_off -- +1 at every topic's first position, an inclusive scan (topic of entry i = the number of
 // topic starts at or before i, minus one: the largest t with part_off[t] <= i, empty topics included).  The placement then
@@ -288,8 +167,8 @@ __device__ __forceinline__ void group_small_body_staged(int n, int32_t n_members
     for (int k = tid; k <= n_members; k += NT) member_off[k] = (int64_t)start[k + 1];
     __syncthreads();                                                    // (the cursors move from here on)
     // Places.  An entry's place is (its group's cursor when its chunk's turn comes) + (its rank among the chunk's entries of that
-    // group, found in A).  The form above passes the turn from chunk to chunk through a spin on an LDS word: ~0.4 us per chunk,
-    // one after another.  Here the serial part is cut down to what is serial:
+    // group, found in A).  Passing a turn from chunk to chunk through a spin on an LDS word costs ~0.4 us per chunk, one after
+    // another.  Here the serial part is cut down to what is serial:
     //   B (every wavefront walks ALL chunks in order, for the groups g with g % wavefronts == its number): cursor read, cursor +
     //     count in one returning LDS atomic, the old cursor left in first[chunk][lane] (NOT in lead: the other wavefronts, which
     //     may be chunks behind or ahead, still read this chunk's (group, count) words).  Groups of different wavefronts are disjoint,

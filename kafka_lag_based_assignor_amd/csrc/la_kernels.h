@@ -85,7 +85,7 @@ constexpr int64_t kLargeMaxConsumers = 8192;   // large path: 8 bins per thread 
 
 // The tail of a small rebalance's ONE launch (tile kernel, single-launch form: the whole batch resident at once).  Every
 // workgroup counts itself done on `counter`; the last one builds every member's list from the results the others wrote
-// (group_small_body, la_group_small.h; skipped when member_off is null: an ungrouped call) and stores `done | status` where the
+// (group_small_body_staged, la_group_small.h; skipped when member_off is null: an ungrouped call) and stores `done | status` where the
 // calling thread is spinning -- assignment, lists and completion in one launch instead of three (Main.java:147-156).
 struct TileTail {
     int32_t enabled;            // 0: no tail (every launch but a zero-copy small call's)

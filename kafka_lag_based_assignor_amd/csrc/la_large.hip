@@ -1,27 +1,40 @@
-// la_large.hip -- topics that do not fit one wave tile (> 1024 partitions or > 64 consumers).
+// la_large.hip -- topics that do not fit one wave tile (> 1024 partitions or > 64 consumers), and the grouping by member.
+// Everything runs on the device, no host round trip between the launches of a call.  In file order:
 //
-// Three phases per topic, all on the device, no host round trip in between:
+//   keys and plan     build_keys_kernel: lag from offsets (Main.java:376-404), 64-bit sort key + 32-bit id, the 12 digit
+//                     histograms of the 96-bit composite and a sample of the lags in one read; sample_scan_kernel: is some lag
+//                     frequent?; plan_kernel: a pass whose digit is constant over the topic is skipped (lags < 2^40 with ids
+//                     < 2^24 cost 8 passes, not 12; ids already ascending skip the 4 id passes), and whether the sort goes
+//                     keys first.  The sort is an LSD radix sort, 8 bits per pass, stable, over (key64, id32): id digits, then
+//                     key digits -> (lag desc, id asc), the comparator of Main.java:228-235.
+//   two pass forms    four kernels per pass (tile_count, two scans, tile_scatter): n >= 2^30 and a test hook; ONE kernel per
+//                     pass (onesweep_pass_kernel): stable scatter with decoupled look-back, ranks from returning LDS atomics
+//                     where the device serves colliding lanes in lane order (lds_atomic_order_test_kernel), else by matching.
+//   keys first        large topics with shuffled ids and no frequent lag sort by the key digits alone; tie_scan_kernel and
+//                     tie_repair_kernel then put every run of equal lags in id order (they follow the rounds kernel in the
+//                     file).  A run too long for one workgroup makes replan_kernel arm the redo slots: the same digits
+//                     again, all in one launch (onesweep_redo_kernel); no-ops otherwise.
+//   ids and greedy    emit_ids_kernel writes the sorted ids and checks the order.  greedy_rounds_kernel: ONE workgroup per
+//                     topic (the chain of rounds is serial), consumer bins in registers, each round orders the bins by
+//                     (total lag, member) and hands the round's C partitions out in that order -- ceil(P/C) rounds instead
+//                     of P argmins.  Packed 64-bit bins are ordered by a full sort (bitonic through DPP and LDS, or a sample
+//                     sort), by merging a few ascending runs, or by sorting only the bins that moved; bins that do not pack
+//                     keep the 96-bit form.  map_ranks_kernel turns consumer indices into member ranks.  greedy_argmin_kernel
+//                     (LA_ALGO_ARGMIN) is the literal form: bins in LDS, one argmin per partition.
+//   host: one topic   sort layout and scratch, the pass launches (sort_passes), the whole sort (sort_launch),
+//                     large_topic_launch.
+//   host: a batch     large_topics_launch: several large topics in the same launches, a LargeItem each, one set of pass
+//                     launches per tile class and one rounds launch per rounds class; a single topic takes the serial form.
+//   huge path         huge_topic_launch, more than kLargeMaxConsumers consumers: bins in HBM, one radix sort of the bins and
+//                     one huge_round_kernel per round.
+//   grouping          group_by_member_launch, the members' lists in three size classes: one workgroup (group_small_kernel),
+//                     a counting sort over several workgroups (group_mid_*, la_group_small.h), and the radix passes above
+//                     between member_keys_kernel and member_emit_kernel.
+//   read-outs         the lab builds' instrumentation arrays (la_debug_*), large_profile_read.
 //
-//   kernel 1  build_keys     lag from offsets (Main.java:376-404), 64-bit sort key + 32-bit id,
-//                            and the 12 digit histograms of the 96-bit composite in one read.
-//   kernel 2  radix sort     LSD, 8 bits per pass, stable, over (key64, id32):
-//                            id digits first, then key digits -> (lag desc, id asc), the
-//                            comparator of Main.java:228-235.  A pass whose digit is constant
-//                            over the whole topic is skipped on the device (plan kernel), so
-//                            lags < 2^40 with ids < 2^24 cost 8 passes, not 12; input that is
-//                            already in id order skips the 4 id passes.
-//                            per pass ONE kernel: stable scatter with decoupled look-back (every tile
-//                            publishes its digit counts as {tag, count} granules and walks back over its
-//                            predecessors'); ranks from returning LDS atomics.  The four-kernel form (tile
-//                            digit counts -> per-digit scan over tiles -> scatter) stays as a test hook.
-//   kernel 3  greedy         ONE workgroup (the chain of rounds is serial): consumer bins live in
-//                            registers, E per thread; each round bitonic-sorts the bins by
-//                            (total lag, member) -- in registers, across lanes with DPP, across
-//                            waves through LDS -- and hands the round's C partitions out in
-//                            that order.  ceil(P/C) rounds instead of P argmins.  A round whose bins are a
-//                            few ascending runs (flat tails of lags) merges the runs instead of sorting.
-//                            LA_ALGO_ARGMIN keeps the literal form: bins (count, total) in LDS,
-//                            one wavefront-argmin + LDS combine per partition.
+// Environment hooks.  Read at every call (tests set them around live contexts): LA_SORT_KEYS_FIRST, LA_SORT_MULTIKERNEL,
+// LA_SWEEP_THREADS (sort_layout), LA_NO_SMALL_GROUP, LA_NO_MID_GROUP (group_by_member_launch).  Read once per process:
+// LA_SORT_RANK (large_init_device, per device), LA_KEYS_GRID (keys_grid).
 #include "la_kernels.h"
 #include "la_device.h"
 #include "la_sort64.h"
@@ -37,40 +50,21 @@ namespace la {
 namespace {
 
 // Arrays that a kernel reads ONCE (the caller's inputs in build_keys_kernel, a pass's source buffers) as non-temporal loads
-// (round 6, after the tile kernel's A/B: profiles/r06_ab_nt_loads.txt).  -DLA_LARGE_NT_LOADS=0: plain loads.
-#ifndef LA_LARGE_NT_LOADS
-#define LA_LARGE_NT_LOADS 1
-#endif
+// (profiles/r06_ab_nt_loads.txt, profiles/r06_ad_nt_loads_large.txt).
 template <typename T>
 __device__ __forceinline__ T stream_load(const T* p) {
-#if LA_LARGE_NT_LOADS
     return __builtin_nontemporal_load(p);
-#else
-    return *p;
-#endif
 }
 
-// Round 1 of the greedy turns the bins around instead of sorting them from scratch (greedy_rounds_packed).  -DLA_ROUND1_REVERSE=0: round 5's form.
-#ifndef LA_ROUND1_REVERSE
-#define LA_ROUND1_REVERSE 1
-#endif
-// The moved-bins sort takes up to twice its narrow capacity in a wide form (moved_sort_bins).  -DLA_WIDE_MOVED=0: narrow only.
-// LA_WIDE_MOVED_LIMIT x (bins per thread of the round) = the most bins the wide form is tried on (512 = all that fit).
-#ifndef LA_WIDE_MOVED
-#define LA_WIDE_MOVED 1
-#endif
-// The rounds kernel's lags as 32-bit words and its results as 16-bit consumer indices where they fit (rounds_io).  -DLA_ROUNDS_NARROW_IO=0: off.
-#ifndef LA_ROUNDS_NARROW_IO
-#define LA_ROUNDS_NARROW_IO 1
-#endif
-#ifndef LA_ROUNDS_NARROW_EC
-#define LA_ROUNDS_NARROW_EC 8          // from how many bins per thread on (8: more than 4 096 consumers; at 4 bins per thread it lost 3 %)
-#endif
-#ifndef LA_WIDE_MOVED_LIMIT
-#define LA_WIDE_MOVED_LIMIT 512
-#endif
+// The rounds kernel's lags as 32-bit words and its results as 16-bit consumer indices where they fit (rounds_io): from how many
+// bins per thread on (8: more than 4 096 consumers; at 4 bins per thread it lost 3 %)
+constexpr int kRoundsNarrowEc = 8;
+// x (bins per thread of the round) = the most bins the wide form of the moved-bins sort is tried on (moved_sort_bins; 512 = all
+// that fit)
+constexpr int kWideMovedLimit = 512;
 
 constexpr int kDigits = 12;            // 4 id digits + 8 key digits
+constexpr uint32_t kAllPasses = (1u << kDigits) - 1;       // pass mask (bit p = digit p) of a sort whose caller knows no bounds
 constexpr int kRadix = 256;
 constexpr int kSortThreads = 256;
 constexpr int kSortWaves = kSortThreads / kWave;
@@ -193,6 +187,12 @@ static int keys_grid(int64_t n) {
     const int64_t coarse = (n + 2047) / 2048;
     const int64_t g = coarse > cap ? cap : coarse;
     return (int)(g < 512 ? 512 : g);
+}
+
+// grid of the grid-stride kernels of 256 threads: a thread per element, up to `cap` workgroups
+static int grid_256(int64_t n, int cap = 2048) {
+    const int64_t g = (n + 255) / 256;
+    return (int)(g > cap ? cap : g);
 }
 
 // ---- kernel 1: keys + all digit histograms ---------------------------------------------------
@@ -713,9 +713,6 @@ __global__ __launch_bounds__(kSortThreads) void tile_scatter_kernel(SortBufs b, 
 // (a bounded spin turns anything unforeseen into kStatusInternal instead of a hung device).  Tried and measured without
 // effect on this kernel (profiles/archive/r03_sort_*): giving every XCD 4-32 consecutive tiles at a time (arrival- or
 // blockIdx-based) -- what made the four-kernel scatter 20 % faster -- and polling 4, 8 or 16 predecessors per hop.
-#ifndef LA_LOOK_WINDOW
-#define LA_LOOK_WINDOW 2
-#endif
 #ifdef LA_LOOKBACK_STATS   // development build: how far the walks go (tools/lookback_probe.py)
 __device__ unsigned long long g_lookback_stats[8];      // walks, hops, polls that found nothing, longest walk, cycles in walks
 #endif
@@ -735,11 +732,11 @@ __device__ unsigned long long g_sweep_clocks[12];
 #define LA_SCLK_START do {} while (0)
 #endif
 constexpr uint32_t kStateAggregate = 1u, kStateInclusive = 2u;
-constexpr int kLookWindow = LA_LOOK_WINDOW;           // predecessors a walk polls at once
+constexpr int kLookWindow = 2;           // predecessors a walk polls at once
 constexpr uint32_t kLookbackSpinLimit = 1u << 22;     // polls of one granule (~1 us each with the sleep) before giving up
 
 // One tile of one pass: the body of onesweep_pass_kernel (one tile per workgroup, taken by arrival) and of onesweep_redo_kernel
-// (round 6: workgroups that loop over tickets and passes).  s_ticket: the tile's number, written by thread 0 of the caller BEFORE
+// (workgroups that loop over tickets and passes).  s_ticket: the tile's number, written by thread 0 of the caller BEFORE
 // the call and read here after the first barrier.
 template <bool ATOMIC_RANK, int THREADS>
 __device__ __forceinline__ void onesweep_tile(const SortBufs& b, const int slot, uint32_t* status, const uint32_t* s_ticket) {
@@ -955,7 +952,7 @@ __global__ __launch_bounds__(THREADS, 4) void onesweep_pass_kernel(SortBufs b0, 
     onesweep_tile<ATOMIC_RANK, THREADS>(b, slot, status, &s_ticket);
 }
 
-// ---- the redo slots of a keys-first sort as ONE launch (round 6) ---------------------------------------------------------------
+// ---- the redo slots of a keys-first sort as ONE launch -------------------------------------------------------------------------
 // A keys-first sort whose tie repair met a run of equal lags longer than a workgroup holds (ctl->redo: the sample said there
 // was none, or a test forced keys first) is sorted again in full, ids first.  Rounds 4-5 kept a second set of pass launches
 // for that -- up to twelve kernels that return at once in every ordinary sort, 4.4 us apiece: 50 us of a 1.15 ms sort of 33.5 M
@@ -1002,7 +999,7 @@ __global__ __launch_bounds__(THREADS, 4) void onesweep_redo_kernel(SortBufs b0, 
 // (one returning LDS atomic per element) is stable only because colliding lanes are served in lane order -- a property of
 // the hardware checked once at la_create on an idle device, not a promise of the ISA.  A violation under load would scramble
 // the order silently; here it raises kStatusOrder (LA_EHIP at the next sync) for 8 B more read per element.
-// ---- what the rounds kernel reads and writes per round (round 6) ---------------------------------------------------------------
+// ---- what the rounds kernel reads and writes per round -------------------------------------------------------------------------
 // greedy_rounds_kernel is ONE workgroup on one compute unit, and every round of a topic of C consumers used to pull C sorted 64-bit
 // keys in and push C 32-bit consumer indices out through that unit's address path -- 96 KB per round at 8 192 consumers, in 16-byte
 // pieces that each touch every cache line of a wavefront's stretch: measured with the stores left out and with half the loads
@@ -1026,7 +1023,7 @@ __device__ __forceinline__ RoundsIo rounds_io(const LargeArgs& a, const uint64_t
     if (P <= 0 || C <= 0) return io;
     int ec = 1, threads = 64;
     rounds_class(C, &ec, &threads);
-    if (only_narrow && !(LA_ROUNDS_NARROW_IO != 0 && a.rounds_follow != 0 && ec >= LA_ROUNDS_NARROW_EC && P >= 8)) return io;   // (no key is read)
+    if (only_narrow && !(a.rounds_follow != 0 && ec >= kRoundsNarrowEc && P >= 8)) return io;   // (no key is read)
     const int n = ec * threads;
     const int64_t rounds = (P + C - 1) / C;
     const int64_t lmax = (int64_t)(key[0] ^ kLagKeyFlip), lmin = (int64_t)(key[P - 1] ^ kLagKeyFlip);
@@ -1036,7 +1033,7 @@ __device__ __forceinline__ RoundsIo rounds_io(const LargeArgs& a, const uint64_t
     if (lmin >= 0 && lag_bits + round_bits + idx_bits <= 62) io.idx_bits = idx_bits;
     io.zero_tail = lmin == 0;
     // (the last element written is P - 1 + 7 (rounds - 1) < 2 P: both buffers hold twice as many narrow elements as partitions)
-    io.narrow = LA_ROUNDS_NARROW_IO != 0 && a.rounds_follow != 0 && io.idx_bits != 0 && ec >= LA_ROUNDS_NARROW_EC && lag_bits <= 32 && P >= 8;
+    io.narrow = a.rounds_follow != 0 && io.idx_bits != 0 && ec >= kRoundsNarrowEc && lag_bits <= 32 && P >= 8;
     return io;
 }
 
@@ -1386,10 +1383,7 @@ __device__ __forceinline__ bool sample_sort_bins(P64 (&rec)[EC], const SampleLds
 // where a sample-sorted round costs ~350 LDS operations and 16 barriers.
 // Returns false (and leaves rec alone) when there are more than kMaxRuns runs: the caller sorts as before.  *runs_out = the
 // number of runs found, so that the caller can decide when to look again.
-#ifndef LA_MAX_RUNS
-#define LA_MAX_RUNS 32
-#endif
-constexpr int kMaxRuns = LA_MAX_RUNS;
+constexpr int kMaxRuns = 32;
 
 template <int EC>
 __device__ __forceinline__ bool merge_runs_bins(P64 (&rec)[EC], const SampleLds& L, int tid, int* runs_out) {
@@ -1691,7 +1685,7 @@ __device__ __forceinline__ bool moved_sort_bins(P64 (&rec)[EC], const SampleLds&
     constexpr int NT = kSampleThreads;
     constexpr int CPT = EC >= 8 ? 2 : 1;                         // bins of the small sort per thread
     constexpr int kCapN = 256 * EC;                              // its capacity (a quarter of the round's bins) in the narrow form
-    constexpr bool kWide = LA_WIDE_MOVED != 0 && EC >= 4;        // the wide form: twice the capacity, twice the bins per thread, 128 buckets
+    constexpr bool kWide = EC >= 4;        // the wide form: twice the capacity, twice the bins per thread, 128 buckets
     constexpr int kCap = kWide ? 2 * kCapN : kCapN;              // what the side-by-side array holds
     static_assert(kCapN <= CPT * NT && NT == 1024, "capacity");
     const int lane = tid & 63;
@@ -1845,7 +1839,7 @@ __device__ __forceinline__ bool moved_sort_bins(P64 (&rec)[EC], const SampleLds&
             // per thread and 128 buckets -- a round of 27 - 33 k cycles where the sample sort over all bins takes 51 k and the run
             // merge 55 - 59 k.  Decided per round from what the round's bins say (round 6's first wide form was chosen by the
             // host from the number of rounds, kept 64 buckets, and lost wherever ~4 000 bins moved).
-            if (m > LA_WIDE_MOVED_LIMIT * EC) return false;
+            if (m > kWideMovedLimit * EC) return false;
             if (!moved_small_sort<2 * CPT, 128>(comp, stage2, sup, sup1, cnt2, m, tid, bucket_limit LA_CLK_ARG)) return false;
         } else {
             return false;
@@ -1879,9 +1873,9 @@ __device__ void greedy_rounds_packed(const LargeArgs& a, const uint64_t* key, in
     // issued back to back: a branch around a load makes hipcc wait for it before issuing the next one -- eight
     // serialized memory round trips per round here, 6k of a round's 52k cycles; the select happens at the use, a
     // whole round of sorting later.
-    // lag[]: the lags themselves (since round 6: the keys' flip is undone when they arrive, not when they are added).  narrow: the
+    // lag[]: the lags themselves (the keys' flip is undone when they arrive, not when they are added).  narrow: the
     // 32-bit lags emit_ids_kernel left, a round's stretch `cpad` elements after the one before (rounds_io).
-    const bool narrow = EC >= LA_ROUNDS_NARROW_EC && EC >= 4 && lag32 != nullptr;     // (workgroup-uniform; never for fewer bins per thread)
+    const bool narrow = EC >= kRoundsNarrowEc && EC >= 4 && lag32 != nullptr;     // (workgroup-uniform; never for fewer bins per thread)
     const int64_t cap8 = (2 * P - 8) & ~(int64_t)3;                              // the last aligned place a 8-element read may start
     uint64_t lag[EC];
 #pragma unroll
@@ -1935,7 +1929,6 @@ __device__ void greedy_rounds_packed(const LargeArgs& a, const uint64_t* key, in
         [[maybe_unused]] int path_ = 0, moved_ = 0;
         if (q > 0 && q <= first_zero_round) {
             bool sorted = false;
-#if LA_ROUND1_REVERSE
             if constexpr (EC >= 2) {
                 // Round 0 handed the DESCENDING lags to the bins in index order (all totals were 0): where the lags differ the
                 // bins stand in exactly the reverse of the order round 1 needs, and only runs of equal lags (index order = the
@@ -1969,7 +1962,6 @@ __device__ void greedy_rounds_packed(const LargeArgs& a, const uint64_t* key, in
                     // (the moved-bins sort's first barrier stands between these reads and its writes to the same memory)
                 }
             }
-#endif
             if constexpr (EC >= 2) {
                 // few bins move?  A topic that has the property has it round after round (the bulk of a power-law topic);
                 // one that does not (lags spread like the totals) has every bin move in every round: after a look that
@@ -2476,10 +2468,8 @@ hipError_t launch_rounds(const LargeArgs& a, const SortBufs& b, int threads, hip
     });
     if (e != hipSuccess) return e;
     LA_LAUNCH((greedy_rounds_kernel<EC>), dim3(count), dim3(threads), lds, stream, a, b, items, scratch, order);
-    if (!items) {
-        int grid = (int)((a.n_part + 255) / 256);
-        LA_LAUNCH(map_ranks_kernel, dim3(grid > 2048 ? 2048 : grid), dim3(256), 0, stream, a, b, (const LargeItem*)nullptr, (char*)nullptr);
-    }
+    if (!items)
+        LA_LAUNCH(map_ranks_kernel, dim3(grid_256(a.n_part)), dim3(256), 0, stream, a, b, (const LargeItem*)nullptr, (char*)nullptr);
     return hipGetLastError();
 }
 
@@ -2724,7 +2714,7 @@ static hipError_t sort_prepare(LargeScratch& scratch, int64_t n, hipStream_t str
 // pass is still a launch (3-4.5 us apiece: cfg5 launches 6 such, a 33.5 M-partition keys-first sort 3 + 3 redo slots).
 // build_keys_kernel raises kStatusBounds on a partition outside the bounds.
 static uint32_t bounds_pass_mask(const LargeArgs& a) {
-    uint32_t mask = (1u << kDigits) - 1;
+    uint32_t mask = kAllPasses;
     if (a.max_lag_hint < 0 || a.max_id_hint < 0) return mask;
     const int lag_bits = a.max_lag_hint > 0 ? 64 - __builtin_clzll((unsigned long long)a.max_lag_hint) : 0;
     const int id_bits = a.max_id_hint > 0 ? 64 - __builtin_clzll((unsigned long long)a.max_id_hint) : 0;
@@ -2734,72 +2724,102 @@ static uint32_t bounds_pass_mask(const LargeArgs& a) {
     return mask;
 }
 
-// plan + the 12 (mostly skipped) passes; keys/vals/hist/unsorted flag must already be in buffer 0
-// `pass_mask`: passes the HOST knows can matter (bit p = digit p); the kernels of the others are not even launched.  The
-// device-side plan still decides among the launched ones (a launched pass whose digit turns out constant returns at
-// once), and it marks every pass outside the mask as skipped by itself -- the caller guarantees those digits are
-// constant (key bits that cannot be set) or the ids ascending.
-// A pass is ONE launch (onesweep_pass_kernel) -- or four, when the sort was prepared for the multi-kernel form.
-static void sort_run_passes(const SortBufs& b, hipStream_t stream, uint32_t* status, hipEvent_t planned = nullptr,
-                            uint32_t pass_mask = (1u << kDigits) - 1, const LargeItem* items = nullptr, int count = 1,
-                            int max_tiles = 0, char* scratch = nullptr, int slot0 = 0) {
-    // `items`: `count` topics of ONE tile class (b.sweep_threads), sorted side by side -- grid.y picks the topic, grid.x is as
-    // wide as the class's largest topic (max_tiles); the plan of all of them is the caller's (one launch over every class).
-    // slot0 = kDigits: the redo slots of a keys-first sort (same digits, see tie_repair_kernel).
-    if (!items && slot0 == 0)
-        LA_LAUNCH(plan_kernel, dim3(kDigits), dim3(kRadix), 0, stream, b, (const LargeItem*)nullptr, (char*)nullptr);
-    if (planned) (void)hipEventRecord(planned, stream);
-    if (slot0 == kDigits && b.tile_state) {
-        // the redo slots of a keys-first sort: one launch (onesweep_redo_kernel), a grid that is resident at once -- at most 64
-        // workgroups over all the launch's topics (a workgroup of 1 024 threads keeps 130 KB of LDS: one per CU; the lanes of a
-        // host-buffer call may run up to four such launches side by side on their streams: 4 x 64 = the chip's 256 CUs, so
-        // every launch's workgroups become resident whatever the others do -- a workgroup waiting for a CU behind spinning
-        // ones of ANOTHER launch would otherwise be a deadlock in the making)
-        int gx = items ? max_tiles : b.n_tiles;
-        const int per_topic = 64 / (items ? (count < 64 ? count : 64) : 1);
-        if (gx > per_topic) gx = per_topic < 1 ? 1 : per_topic;
-        const dim3 grid(gx, items ? count : 1);
-        if (b.sweep_threads == 1024) {
-            if (b.atomic_rank) LA_LAUNCH((onesweep_redo_kernel<true, 1024>), grid, dim3(1024), 0, stream, b, pass_mask, status, items, scratch);
-            else LA_LAUNCH((onesweep_redo_kernel<false, 1024>), grid, dim3(1024), 0, stream, b, pass_mask, status, items, scratch);
-        } else if (b.sweep_threads == 512) {
-            if (b.atomic_rank) LA_LAUNCH((onesweep_redo_kernel<true, 512>), grid, dim3(512), 0, stream, b, pass_mask, status, items, scratch);
-            else LA_LAUNCH((onesweep_redo_kernel<false, 512>), grid, dim3(512), 0, stream, b, pass_mask, status, items, scratch);
-        } else {
-            if (b.atomic_rank) LA_LAUNCH((onesweep_redo_kernel<true, 256>), grid, dim3(256), 0, stream, b, pass_mask, status, items, scratch);
-            else LA_LAUNCH((onesweep_redo_kernel<false, 256>), grid, dim3(256), 0, stream, b, pass_mask, status, items, scratch);
+// (b.sweep_threads, b.atomic_rank) as compile-time values: f(std::bool_constant<atomic rank>, std::integral_constant<int, threads>)
+template <typename F>
+static void with_sweep_class(const SortBufs& b, F&& f) {
+    auto with_rank = [&](auto threads) {
+        if (b.atomic_rank) f(std::true_type{}, threads);
+        else f(std::false_type{}, threads);
+    };
+    if (b.sweep_threads == 1024) with_rank(std::integral_constant<int, 1024>{});
+    else if (b.sweep_threads == 512) with_rank(std::integral_constant<int, 512>{});
+    else with_rank(std::integral_constant<int, 256>{});
+}
+
+// One tile class of a set of sort launches: `n` topics from item `first` on whose passes run `sweep_threads` wide -- grid.y
+// picks the topic, grid.x is as wide as the class's largest topic (max_tiles).
+struct SortClass {
+    int first, n, sweep_threads, max_tiles;
+};
+
+// What one set of sort launches covers.  `items == nullptr`: ONE topic, its buffers b's own, one class of one topic
+// (sort_job_single).  Otherwise `count` topics side by side, in tile-class order: b holds what they share (atomic_rank,
+// keys_first_force), an item its topic's buffers as offsets from `base`.
+struct SortJob {
+    SortBufs b;
+    const LargeItem* items;
+    int count;
+    char* base;
+    SortClass cls[3];                  // (a sweep is 256, 512 or 1 024 threads wide)
+    int n_cls;
+    bool keys_first;                   // some topic may sort keys first: sample scan, tie repair and redo slots are launched
+    int64_t max_n;                     // elements of the largest topic
+    // passes the HOST knows can matter (bit p = digit p); the kernels of the others are not even launched.  The device-side
+    // plan still decides among the launched ones (a launched pass whose digit turns out constant returns at once), and it marks
+    // every pass outside the mask as skipped by itself -- the caller guarantees those digits are constant (key bits that cannot
+    // be set) or the ids ascending.
+    uint32_t pass_mask;
+    uint32_t* status;
+};
+
+static SortJob sort_job_single(const SortBufs& b, uint32_t pass_mask, uint32_t* status) {
+    return SortJob{b, nullptr, 1, nullptr, {{0, 1, b.sweep_threads, b.n_tiles}}, 1, b.samp != nullptr, b.n, pass_mask, status};
+}
+
+// The launched passes of every tile class.  slot0 = 0: the sort's own slots; kDigits: the redo slots of a keys-first sort (the
+// same digits again, see tie_repair_kernel).  A pass is ONE launch (onesweep_pass_kernel) -- or four, when the sort was
+// prepared for the multi-kernel form; the redo slots of a class are one launch altogether.
+static void sort_passes(const SortJob& j, hipStream_t stream, int slot0) {
+    for (int c = 0; c < j.n_cls; ++c) {
+        const SortClass& k = j.cls[c];
+        SortBufs b = j.b;
+        const LargeItem* items = nullptr;
+        if (j.items) {
+            items = j.items + k.first;
+            b.sweep_threads = k.sweep_threads;
+            b.tile_state = (unsigned long long*)j.base;            // (non-null: the single-kernel passes; items carry the real one)
         }
-        return;
-    }
-    for (int d = 0; d < kDigits; ++d) {
-        if (!((pass_mask >> d) & 1u)) continue;
-        const int p = slot0 + d;
-        if (b.tile_state) {
-            const dim3 grid(items ? max_tiles : b.n_tiles, items ? count : 1);
-            if (b.sweep_threads == 1024) {
-                if (b.atomic_rank) LA_LAUNCH((onesweep_pass_kernel<true, 1024>), grid, dim3(1024), 0, stream, b, p, status, items, scratch);
-                else LA_LAUNCH((onesweep_pass_kernel<false, 1024>), grid, dim3(1024), 0, stream, b, p, status, items, scratch);
-            } else if (b.sweep_threads == 512) {
-                if (b.atomic_rank) LA_LAUNCH((onesweep_pass_kernel<true, 512>), grid, dim3(512), 0, stream, b, p, status, items, scratch);
-                else LA_LAUNCH((onesweep_pass_kernel<false, 512>), grid, dim3(512), 0, stream, b, p, status, items, scratch);
-            } else {
-                if (b.atomic_rank) LA_LAUNCH((onesweep_pass_kernel<true, 256>), grid, dim3(256), 0, stream, b, p, status, items, scratch);
-                else LA_LAUNCH((onesweep_pass_kernel<false, 256>), grid, dim3(256), 0, stream, b, p, status, items, scratch);
-            }
+        if (slot0 == kDigits && b.tile_state) {
+            // onesweep_redo_kernel needs a grid that is resident at once -- at most 64 workgroups over all the launch's topics (a
+            // workgroup of 1 024 threads keeps 130 KB of LDS: one per CU; the lanes of a host-buffer call may run up to four such
+            // launches side by side on their streams: 4 x 64 = the chip's 256 CUs, so every launch's workgroups become resident
+            // whatever the others do -- a workgroup waiting for a CU behind spinning ones of ANOTHER launch would otherwise be
+            // a deadlock in the making)
+            const int per_topic = 64 / (k.n < 64 ? k.n : 64);
+            const dim3 grid(k.max_tiles < per_topic ? k.max_tiles : per_topic, k.n);
+            with_sweep_class(b, [&](auto atomic, auto threads) {
+                LA_LAUNCH((onesweep_redo_kernel<atomic(), threads()>), grid, dim3(threads()), 0, stream, b, j.pass_mask, j.status, items, j.base);
+            });
             continue;
         }
-        LA_LAUNCH(tile_count_kernel, dim3(b.n_tiles < 2048 ? b.n_tiles : 2048), dim3(kSortThreads), 0, stream, b, p);
-        LA_LAUNCH(scan_group_sums_kernel, dim3(b.n_groups), dim3(kRadix), 0, stream, b, p);
-        LA_LAUNCH(scan_offsets_kernel, dim3(b.n_groups), dim3(kRadix), 0, stream, b, p);
-        if (b.atomic_rank) LA_LAUNCH(tile_scatter_kernel<true>, dim3(b.n_tiles), dim3(kSortThreads), 0, stream, b, p);
-        else LA_LAUNCH(tile_scatter_kernel<false>, dim3(b.n_tiles), dim3(kSortThreads), 0, stream, b, p);
+        for (int d = 0; d < kDigits; ++d) {
+            if (!((j.pass_mask >> d) & 1u)) continue;
+            const int p = slot0 + d;
+            if (b.tile_state) {
+                with_sweep_class(b, [&](auto atomic, auto threads) {
+                    LA_LAUNCH((onesweep_pass_kernel<atomic(), threads()>), dim3(k.max_tiles, k.n), dim3(threads()), 0, stream, b, p, j.status, items, j.base);
+                });
+                continue;
+            }
+            LA_LAUNCH(tile_count_kernel, dim3(b.n_tiles < 2048 ? b.n_tiles : 2048), dim3(kSortThreads), 0, stream, b, p);
+            LA_LAUNCH(scan_group_sums_kernel, dim3(b.n_groups), dim3(kRadix), 0, stream, b, p);
+            LA_LAUNCH(scan_offsets_kernel, dim3(b.n_groups), dim3(kRadix), 0, stream, b, p);
+            if (b.atomic_rank) LA_LAUNCH(tile_scatter_kernel<true>, dim3(b.n_tiles), dim3(kSortThreads), 0, stream, b, p);
+            else LA_LAUNCH(tile_scatter_kernel<false>, dim3(b.n_tiles), dim3(kSortThreads), 0, stream, b, p);
+        }
     }
 }
 
-// The tail of sorts that may have gone keys first (b.samp of the single form; any item of a batched launch): ties into id
-// order, then -- no-ops unless a run did not fit -- the redo slots.  `max_n`: partitions of the largest topic.
-static hipError_t sort_repair_launch(const SortBufs& b, hipStream_t stream, const LargeItem* items, int count, char* scratch,
-                                     int64_t max_n) {
+// plan + the sort's passes; keys, payloads, histograms and the unsorted-ids flag must already be in buffer 0.  `planned`
+// (may be null) is recorded after the plan.
+static void sort_plan_and_passes(const SortJob& j, hipStream_t stream, hipEvent_t planned) {
+    LA_LAUNCH(plan_kernel, dim3(kDigits, j.count), dim3(kRadix), 0, stream, j.b, j.items, j.base);
+    if (planned) (void)hipEventRecord(planned, stream);
+    sort_passes(j, stream, 0);
+}
+
+// The tail of sorts that may have gone keys first: ties into id order, then a new plan for the redo slots.
+static hipError_t sort_repair_launch(const SortJob& j, hipStream_t stream) {
     static PerDeviceOnce lds_opt_in;
     const hipError_t e = lds_opt_in.run([] {
         // (exactly what the launch asks for: the kernel also has static LDS, and dynamic + static must fit the CU's 160 KB)
@@ -2807,56 +2827,72 @@ static hipError_t sort_repair_launch(const SortBufs& b, hipStream_t stream, cons
                                    (int)(2 * kRepairCap * sizeof(uint64_t)));
     });
     if (e != hipSuccess) return e;
-    int64_t gs = (max_n / 2 + 255) / 256;
+    int64_t gs = (j.max_n / 2 + 255) / 256;
     if (gs > 4096) gs = 4096;
-    LA_LAUNCH(tie_scan_kernel, dim3((unsigned)(gs < 1 ? 1 : gs), items ? count : 1), dim3(256), 0, stream, b, items, scratch);
-    int64_t gx = (max_n + kRepairWindow - 1) / kRepairWindow;
+    LA_LAUNCH(tie_scan_kernel, dim3((unsigned)(gs < 1 ? 1 : gs), j.count), dim3(256), 0, stream, j.b, j.items, j.base);
+    int64_t gx = (j.max_n + kRepairWindow - 1) / kRepairWindow;
     if (gx > 1024) gx = 1024;                                   // (128 KB of LDS each: one per CU at a time; windows grid-stride)
-    LA_LAUNCH(tie_repair_kernel, dim3((unsigned)gx, items ? count : 1), dim3(kRepairThreads),
-                       (size_t)2 * kRepairCap * sizeof(uint64_t), stream, b, items, scratch);
-    LA_LAUNCH(replan_kernel, dim3(items ? count : 1), dim3(64), 0, stream, b, items, scratch);
+    LA_LAUNCH(tie_repair_kernel, dim3((unsigned)gx, j.count), dim3(kRepairThreads), (size_t)2 * kRepairCap * sizeof(uint64_t), stream,
+              j.b, j.items, j.base);
+    LA_LAUNCH(replan_kernel, dim3(j.count), dim3(64), 0, stream, j.b, j.items, j.base);
     return hipGetLastError();
 }
 
-hipError_t large_topic_launch(LargeScratch& scratch, const LargeArgs& a, bool argmin, hipStream_t stream) {
-    const int64_t n = a.n_part;
-    if (n <= 0) {
-        // no partition metadata: every subscribed consumer still reports a total of 0 (Main.java:216-225, :283-291)
-        if (a.n_cons > 0 && a.out_total)
-            return hipMemsetAsync(a.out_total + a.c0, 0, (size_t)a.n_cons * sizeof(int64_t), stream);
-        return hipSuccess;
-    }
-    if (n > 0x7FFFFFFF || a.n_cons > kLargeMaxConsumers) return hipErrorInvalidValue;
-    SortBufs b{};
-    hipError_t e;
-    if ((e = sort_prepare(scratch, n, stream, &b, a.sort_multi_kernel != 0, true)) != hipSuccess) return e;
-    int grid = (int)((n + 255) / 256);
-    if (grid > 2048) grid = 2048;
-    LargeProfile& pf = scratch.prof;
-    const bool profile = pf.armed && !pf.recorded;
-    if (profile) {
+// A whole sort of the job's topics by (lag desc, id asc): keys, sample scan, plan, passes and -- where a topic may sort keys
+// first -- the tie repair and the redo slots (no-ops unless a run of equal lags did not fit its workgroup).
+static hipError_t sort_launch(const LargeArgs& a, const SortJob& j, hipStream_t stream, hipEvent_t planned) {
+    LA_LAUNCH(build_keys_kernel, dim3(keys_grid(j.max_n), j.count), dim3(256), 0, stream, a, j.b, j.items, j.base);
+    if (j.keys_first) LA_LAUNCH(sample_scan_kernel, dim3(j.items ? 64 : 256, j.count), dim3(256), 0, stream, j.b, j.items, j.base);
+    sort_plan_and_passes(j, stream, planned);
+    if (!j.keys_first) return hipSuccess;
+    const hipError_t e = sort_repair_launch(j, stream);
+    if (e != hipSuccess) return e;
+    sort_passes(j, stream, kDigits);
+    return hipSuccess;
+}
+
+// no partition metadata: every subscribed consumer still reports a total of 0 (Main.java:216-225, :283-291)
+static hipError_t zero_totals(const LargeArgs& a, hipStream_t stream) {
+    if (a.n_cons > 0 && a.out_total) return hipMemsetAsync(a.out_total + a.c0, 0, (size_t)a.n_cons * sizeof(int64_t), stream);
+    return hipSuccess;
+}
+
+// The phase events of the first large sort of a call that asked for them (LargeProfile): ev[0] at begin(), ev[1] and ev[2]
+// where the launcher says, ev[3] on every way out.
+struct ProfileScope {
+    LargeProfile& pf;
+    hipStream_t stream;
+    bool on = false;
+    hipError_t begin(int64_t n) {
+        if (!pf.armed || pf.recorded) return hipSuccess;
+        hipError_t e;
         for (hipEvent_t& ev : pf.ev)
             if (!ev && (e = hipEventCreate(&ev)) != hipSuccess) return e;
         pf.n = n;
         pf.recorded = true;
-        (void)hipEventRecord(pf.ev[0], stream);
+        on = true;
+        mark(0);
+        return hipSuccess;
     }
-    struct Done {                                   // the last event, on every way out
-        LargeProfile& pf; bool on; hipStream_t st;
-        ~Done() { if (on) (void)hipEventRecord(pf.ev[3], st); }
-    } done{pf, profile, stream};
-    LA_LAUNCH(build_keys_kernel, dim3(keys_grid(n)), dim3(256), 0, stream, a, b, (const LargeItem*)nullptr, (char*)nullptr);
-    if (b.samp) LA_LAUNCH(sample_scan_kernel, dim3(256), dim3(256), 0, stream, b, (const LargeItem*)nullptr, (char*)nullptr);
-    const uint32_t pass_mask = bounds_pass_mask(a);
-    sort_run_passes(b, stream, a.status, profile ? pf.ev[1] : nullptr, pass_mask);
-    if (b.samp) {
-        if ((e = sort_repair_launch(b, stream, nullptr, 1, nullptr, n)) != hipSuccess) return e;
-        sort_run_passes(b, stream, a.status, nullptr, pass_mask, nullptr, 1, 0, nullptr, kDigits);
-    }
-    if (profile) (void)hipEventRecord(pf.ev[2], stream);
+    hipEvent_t event(int i) const { return on ? pf.ev[i] : nullptr; }
+    void mark(int i) { if (on) (void)hipEventRecord(pf.ev[i], stream); }
+    ~ProfileScope() { mark(3); }
+};
+
+hipError_t large_topic_launch(LargeScratch& scratch, const LargeArgs& a, bool argmin, hipStream_t stream) {
+    const int64_t n = a.n_part;
+    if (n <= 0) return zero_totals(a, stream);
+    if (n > 0x7FFFFFFF || a.n_cons > kLargeMaxConsumers) return hipErrorInvalidValue;
+    SortBufs b{};
+    hipError_t e;
+    if ((e = sort_prepare(scratch, n, stream, &b, a.sort_multi_kernel != 0, true)) != hipSuccess) return e;
+    ProfileScope prof{scratch.prof, stream};
+    if ((e = prof.begin(n)) != hipSuccess) return e;
+    if ((e = sort_launch(a, sort_job_single(b, bounds_pass_mask(a), a.status), stream, prof.event(1))) != hipSuccess) return e;
+    prof.mark(2);
     LargeArgs al = a;
     al.rounds_follow = argmin ? 0 : 1;
-    LA_LAUNCH(emit_ids_kernel, dim3(grid), dim3(256), 0, stream, al, b, (const LargeItem*)nullptr, (char*)nullptr);
+    LA_LAUNCH(emit_ids_kernel, dim3(grid_256(n)), dim3(256), 0, stream, al, b, (const LargeItem*)nullptr, (char*)nullptr);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     if (a.n_cons == 0) return hipSuccess;
 
@@ -2930,8 +2966,11 @@ hipError_t large_topics_launch(LargeScratch& scratch, const LargeArgs* args, int
     }
     LargeItem* h_items = (LargeItem*)sg.h;
     int32_t* h_order = (int32_t*)((char*)sg.h + items_bytes);
-    int64_t max_n = 0;
-    bool any_keys_first = false, force_keys_first = false;
+    // job.b: what is common to a launch's items besides their buffers
+    SortJob job{};
+    job.b.atomic_rank = large_atomic_rank_supported();
+    job.count = count;
+    job.base = base;
     for (int j = 0; j < count; ++j) {
         const int i = idx[(size_t)j];
         const SortLayout& L = lay[(size_t)i];
@@ -2944,9 +2983,14 @@ hipError_t large_topics_launch(LargeScratch& scratch, const LargeArgs* args, int
         it.o_samp = L.keys_first ? z + L.o_samp : 0;               // (z + o_samp > 0: the control block comes first)
         it.o_flag = z + L.o_flag;
         it.samp_bits = L.samp_bits; it.pad = 0;
-        any_keys_first = any_keys_first || L.keys_first != 0;
-        force_keys_first = force_keys_first || L.keys_first == 2;
-        if (args[i].n_part > max_n) max_n = args[i].n_part;
+        job.keys_first = job.keys_first || L.keys_first != 0;
+        if (L.keys_first == 2) job.b.keys_first_force = 1;
+        if (L.n > job.max_n) job.max_n = L.n;
+        if (job.n_cls == 0 || job.cls[job.n_cls - 1].sweep_threads != L.sweep_threads)
+            job.cls[job.n_cls++] = SortClass{j, 0, L.sweep_threads, 0};
+        SortClass& k = job.cls[job.n_cls - 1];
+        ++k.n;
+        if (L.n_tiles > k.max_tiles) k.max_tiles = L.n_tiles;
     }
     struct Cls { int ec, threads, first, n; };
     std::vector<Cls> cls;
@@ -2969,63 +3013,22 @@ hipError_t large_topics_launch(LargeScratch& scratch, const LargeArgs* args, int
     const int32_t* d_order = (const int32_t*)((const char*)scratch.d_items + items_bytes);
     if ((e = hipMemsetAsync(base, 0, zero, stream)) != hipSuccess) return e;
 
-    LargeProfile& pf = scratch.prof;
-    const bool profile = pf.armed && !pf.recorded;
-    if (profile) {
-        for (hipEvent_t& ev : pf.ev)
-            if (!ev && (e = hipEventCreate(&ev)) != hipSuccess) return e;
-        pf.n = h_items[0].n_part;
-        pf.recorded = true;
-        (void)hipEventRecord(pf.ev[0], stream);
-    }
-    const int gx = keys_grid(max_n);
-    // a0: the batch's arrays and flags, shared by every item (an item overrides the four segment fields); b0: what is common
-    // to a launch's items besides their buffers
+    ProfileScope prof{scratch.prof, stream};
+    if ((e = prof.begin(h_items[0].n_part)) != hipSuccess) return e;
+    // a0: the batch's arrays and flags, shared by every item (an item overrides the four segment fields)
     LargeArgs a0 = args[0];
-    SortBufs b0{};
-    b0.atomic_rank = large_atomic_rank_supported();
-    b0.keys_first_force = force_keys_first ? 1 : 0;
-    uint32_t* status = args[0].status;
-    LA_LAUNCH(build_keys_kernel, dim3(gx, count), dim3(256), 0, stream, a0, b0, d_items, base);
-    if (any_keys_first) LA_LAUNCH(sample_scan_kernel, dim3(64, count), dim3(256), 0, stream, b0, d_items, base);
-    LA_LAUNCH(plan_kernel, dim3(kDigits, count), dim3(kRadix), 0, stream, b0, d_items, base);
-    if (profile) (void)hipEventRecord(pf.ev[1], stream);
-    for (int first = 0; first < count;) {                          // one set of pass launches per tile class
-        const int sweep = lay[(size_t)idx[(size_t)first]].sweep_threads;
-        int n = 0, max_tiles = 0;
-        while (first + n < count && lay[(size_t)idx[(size_t)(first + n)]].sweep_threads == sweep) {
-            if (h_items[first + n].n_tiles > max_tiles) max_tiles = h_items[first + n].n_tiles;
-            ++n;
-        }
-        SortBufs bc = b0;
-        bc.sweep_threads = sweep;
-        bc.tile_state = (unsigned long long*)base;                 // (non-null: the single-kernel passes; items carry the real one)
-        sort_run_passes(bc, stream, status, nullptr, bounds_pass_mask(a0), d_items + first, n, max_tiles, base);
-        first += n;
-    }
-    if (any_keys_first) {
-        if ((e = sort_repair_launch(b0, stream, d_items, count, base, max_n)) != hipSuccess) return e;
-        for (int first = 0; first < count;) {                      // the redo slots (no-ops unless a run did not fit), per class
-            const int sweep = lay[(size_t)idx[(size_t)first]].sweep_threads;
-            int n = 0, max_tiles = 0;
-            while (first + n < count && lay[(size_t)idx[(size_t)(first + n)]].sweep_threads == sweep) {
-                if (h_items[first + n].n_tiles > max_tiles) max_tiles = h_items[first + n].n_tiles;
-                ++n;
-            }
-            SortBufs bc = b0;
-            bc.sweep_threads = sweep;
-            bc.tile_state = (unsigned long long*)base;
-            sort_run_passes(bc, stream, status, nullptr, bounds_pass_mask(a0), d_items + first, n, max_tiles, base, kDigits);
-            first += n;
-        }
-    }
-    if (profile) (void)hipEventRecord(pf.ev[2], stream);
+    job.items = d_items;
+    job.pass_mask = bounds_pass_mask(a0);
+    job.status = a0.status;
+    if ((e = sort_launch(a0, job, stream, prof.event(1))) != hipSuccess) return e;
+    prof.mark(2);
+    const SortBufs& b0 = job.b;
+    const int gx = keys_grid(job.max_n);
     a0.rounds_follow = 1;
     LA_LAUNCH(emit_ids_kernel, dim3(gx, count), dim3(256), 0, stream, a0, b0, d_items, base);
     for (const Cls& c : cls)
         if ((e = launch_rounds_class(c.ec, c.threads, a0, b0, stream, d_items, base, d_order + c.first, c.n)) != hipSuccess) return e;
     if (!cls.empty()) LA_LAUNCH(map_ranks_kernel, dim3(gx, count), dim3(256), 0, stream, a0, b0, d_items, base);
-    if (profile) (void)hipEventRecord(pf.ev[3], stream);
     return hipGetLastError();
 }
 
@@ -3074,10 +3077,7 @@ __global__ __launch_bounds__(256) void huge_round_kernel(LargeArgs a, SortBufs p
 
 hipError_t huge_topic_launch(LargeScratch& scratch, const LargeArgs& a, hipStream_t stream) {
     const int64_t P = a.n_part, C = a.n_cons;
-    if (P <= 0) {
-        if (C > 0 && a.out_total) return hipMemsetAsync(a.out_total + a.c0, 0, (size_t)C * sizeof(int64_t), stream);
-        return hipSuccess;
-    }
+    if (P <= 0) return zero_totals(a, stream);
     if (P > 0x7FFFFFFF || C > 0x7FFFFFFF || C <= 0) return hipErrorInvalidValue;
     const SortLayout lp = sort_layout(P, a.sort_multi_kernel != 0, true), lc = sort_layout(C, false);
     hipError_t e;
@@ -3088,17 +3088,9 @@ hipError_t huge_topic_launch(LargeScratch& scratch, const LargeArgs& a, hipStrea
     SortBufs bins[2] = {sort_bind(lc, base + lp.zero_bytes, base + zero + lp.data_bytes),
                         sort_bind(lc, base + lp.zero_bytes + lc.zero_bytes, base + zero + lp.data_bytes + lc.data_bytes)};
     if ((e = hipMemsetAsync(base, 0, lp.zero_bytes, stream)) != hipSuccess) return e;
-    const int grid = keys_grid(P);
-    LA_LAUNCH(build_keys_kernel, dim3(grid), dim3(256), 0, stream, a, bp, (const LargeItem*)nullptr, (char*)nullptr);
-    if (bp.samp) LA_LAUNCH(sample_scan_kernel, dim3(256), dim3(256), 0, stream, bp, (const LargeItem*)nullptr, (char*)nullptr);
-    sort_run_passes(bp, stream, a.status);
-    if (bp.samp) {
-        if ((e = sort_repair_launch(bp, stream, nullptr, 1, nullptr, P)) != hipSuccess) return e;
-        sort_run_passes(bp, stream, a.status, nullptr, (1u << kDigits) - 1, nullptr, 1, 0, nullptr, kDigits);
-    }
-    LA_LAUNCH(emit_ids_kernel, dim3(grid), dim3(256), 0, stream, a, bp, (const LargeItem*)nullptr, (char*)nullptr);
-    int cgrid = (int)((C + 255) / 256);
-    if (cgrid > 1024) cgrid = 1024;
+    if ((e = sort_launch(a, sort_job_single(bp, kAllPasses, a.status), stream, nullptr)) != hipSuccess) return e;
+    LA_LAUNCH(emit_ids_kernel, dim3(keys_grid(P)), dim3(256), 0, stream, a, bp, (const LargeItem*)nullptr, (char*)nullptr);
+    const int cgrid = grid_256(C, 1024);
     const int64_t rounds = (P + C - 1) / C;
     for (int64_t r = 0; r < rounds; ++r) {
         const SortBufs& cur = bins[r & 1];
@@ -3106,7 +3098,7 @@ hipError_t huge_topic_launch(LargeScratch& scratch, const LargeArgs& a, hipStrea
         const int last = r + 1 == rounds;
         if (!last && (e = hipMemsetAsync((char*)next.ctl, 0, lc.zero_bytes, stream)) != hipSuccess) return e;
         LA_LAUNCH(huge_round_kernel, dim3(cgrid), dim3(256), 0, stream, a, bp, cur, next, r, r == 0 ? 1 : 0, last);
-        if (!last) sort_run_passes(next, stream, a.status, nullptr, 0xFF0u);       // the 8 digits of the totals; ids stay in order
+        if (!last) sort_plan_and_passes(sort_job_single(next, 0xFF0u, a.status), stream, nullptr);   // the 8 digits of the totals; ids stay in order
     }
     return hipGetLastError();
 }
@@ -3120,20 +3112,12 @@ __global__ __launch_bounds__(1024) void group_small_kernel(int n, int32_t n_memb
     __shared__ uint32_t start[kSmallGroupM];          // counts, then the groups' cursors
     __shared__ uint32_t wsum[1024 / kWave];
     __shared__ uint32_t turn;
-#ifndef LA_GROUP_UNSTAGED
     __shared__ int32_t s_in[7 * kSmallGroupN];        // ranks, ids, topics of the entries; the lists; the chunks' group leaders
     group_small_body_staged<1024, kSmallGroupM>(n, n_members, n_topics, part_off, out_partition, member_rank, member_off,
                                                 grouped_topic, grouped_partition, grouped_entry, start, wsum, &turn, s_in,
                                                 s_in + kSmallGroupN, s_in + 2 * kSmallGroupN, s_in + 3 * kSmallGroupN, s_in + 4 * kSmallGroupN,
                                                 reinterpret_cast<uint32_t*>(s_in + 5 * kSmallGroupN),
-                                                             reinterpret_cast<uint32_t*>(s_in + 6 * kSmallGroupN));
-#elif defined(LA_GROUP_SUB)                                   // (lab builds: tools/group_probe.py compares the forms on one box)
-    group_small_body<1024, kSmallGroupM, LA_GROUP_SUB>(n, n_members, n_topics, part_off, out_partition, member_rank, member_off,
-                                                       grouped_topic, grouped_partition, grouped_entry, start, wsum, &turn);
-#else
-    group_small_body<1024, kSmallGroupM>(n, n_members, n_topics, part_off, out_partition, member_rank, member_off, grouped_topic,
-                                         grouped_partition, grouped_entry, start, wsum, &turn);
-#endif
+                                                reinterpret_cast<uint32_t*>(s_in + 6 * kSmallGroupN));
     if (fin_flag) {
         // the last launch of a zero-copy call (la_host.hip, assign_small_zc): this ONE workgroup's stores into the host's memory
         // are out, then `done | status` goes where the calling thread is spinning -- no separate finishing launch
@@ -3173,65 +3157,43 @@ hipError_t group_by_member_launch(LargeScratch& scratch, int64_t n, int32_t n_me
     }
     SortBufs b{};
     if ((e = sort_prepare(scratch, n, stream, &b)) != hipSuccess) return e;
-    int grid = (int)((n + 255) / 256);
-    if (grid > 2048) grid = 2048;
+    const int grid = grid_256(n);
     LA_LAUNCH(member_keys_kernel, dim3(grid), dim3(256), 0, stream, member_rank, b);
     // key = rank + 1 <= n_members: only its low ceil(bits / 8) digits can differ; the payload (entry index) is ascending.
-    // Launching just those passes matters for the small batches a real group leader sends: every skipped pass used to
-    // cost four empty launches (~50 launches, ~190 us, for a 100-partition rebalance).
+    // Launching just those passes matters for the small batches a real group leader sends: a skipped pass is still a
+    // launch (four in the four-kernel form: ~50 launches, ~190 us, for a 100-partition rebalance).
     uint32_t mask = 0;
     for (int d = 0; d < 8 && ((uint64_t)n_members >> (8 * d)) != 0; ++d) mask |= 1u << (4 + d);
-    sort_run_passes(b, stream, status, nullptr, mask);
+    sort_plan_and_passes(sort_job_single(b, mask, status), stream, nullptr);
     LA_LAUNCH(member_emit_kernel, dim3(grid), dim3(256), 0, stream, b, n_members, n_topics, part_off,
                        out_partition, member_off, grouped_topic, grouped_partition, grouped_entry, status);
     return hipGetLastError();
 }
 
+// ---- lab builds: the kernels' instrumentation arrays (tools/*_probe.py find the exports with hasattr) -------------------------
+// Reads a __device__ array of counters into `out` and, with `reset`, zeroes it.
+template <typename T>
+static int debug_read(const T& symbol, unsigned long long* out, int reset) {
+    hipError_t e = hipMemcpyFromSymbol(out, HIP_SYMBOL(symbol), sizeof(T));
+    if (e == hipSuccess && reset) {
+        const T zero{};
+        e = hipMemcpyToSymbol(HIP_SYMBOL(symbol), &zero, sizeof(T));
+    }
+    return e == hipSuccess ? 0 : -3;
+}
+#define LA_DEBUG_EXPORT extern "C" __attribute__((visibility("default"))) int
 #ifdef LA_GROUP_CLOCKS
-extern "C" __attribute__((visibility("default"))) int la_debug_group_clocks(unsigned long long* out, int reset) {
-    hipError_t e = hipMemcpyFromSymbol(out, HIP_SYMBOL(g_group_clocks), sizeof(g_group_clocks));
-    if (e == hipSuccess && reset) {
-        unsigned long long zero[12] = {};
-        e = hipMemcpyToSymbol(HIP_SYMBOL(g_group_clocks), zero, sizeof zero);
-    }
-    return e == hipSuccess ? 0 : -3;
-}
+LA_DEBUG_EXPORT la_debug_group_clocks(unsigned long long* out, int reset) { return debug_read(g_group_clocks, out, reset); }
 #endif
-
 #ifdef LA_SWEEP_CLOCKS
-extern "C" __attribute__((visibility("default"))) int la_debug_sweep_clocks(unsigned long long* out, int reset) {
-    hipError_t e = hipMemcpyFromSymbol(out, HIP_SYMBOL(g_sweep_clocks), sizeof(g_sweep_clocks));
-    if (e == hipSuccess && reset) {
-        unsigned long long zero[12] = {};
-        e = hipMemcpyToSymbol(HIP_SYMBOL(g_sweep_clocks), zero, sizeof zero);
-    }
-    return e == hipSuccess ? 0 : -3;
-}
+LA_DEBUG_EXPORT la_debug_sweep_clocks(unsigned long long* out, int reset) { return debug_read(g_sweep_clocks, out, reset); }
 #endif
-
 #ifdef LA_LOOKBACK_STATS
-extern "C" __attribute__((visibility("default"))) int la_debug_lookback_stats(unsigned long long* out, int reset) {
-    hipError_t e = hipMemcpyFromSymbol(out, HIP_SYMBOL(g_lookback_stats), sizeof(g_lookback_stats));
-    if (e == hipSuccess && reset) {
-        unsigned long long zero[8] = {};
-        e = hipMemcpyToSymbol(HIP_SYMBOL(g_lookback_stats), zero, sizeof zero);
-    }
-    return e == hipSuccess ? 0 : -3;
-}
+LA_DEBUG_EXPORT la_debug_lookback_stats(unsigned long long* out, int reset) { return debug_read(g_lookback_stats, out, reset); }
 #endif
-
 #ifdef LA_ROUND_CLOCKS
-extern "C" __attribute__((visibility("default"))) int la_debug_round_stamps(unsigned long long* out) {
-    return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_round_stamp), sizeof(g_round_stamp)) == hipSuccess ? 0 : -3;
-}
-extern "C" __attribute__((visibility("default"))) int la_debug_round_clocks(unsigned long long* out, int reset) {
-    hipError_t e = hipMemcpyFromSymbol(out, HIP_SYMBOL(g_round_clocks), sizeof(g_round_clocks));
-    if (e == hipSuccess && reset) {
-        unsigned long long zero[16] = {};
-        e = hipMemcpyToSymbol(HIP_SYMBOL(g_round_clocks), zero, sizeof zero);
-    }
-    return e == hipSuccess ? 0 : -3;
-}
+LA_DEBUG_EXPORT la_debug_round_stamps(unsigned long long* out) { return debug_read(g_round_stamp, out, 0); }
+LA_DEBUG_EXPORT la_debug_round_clocks(unsigned long long* out, int reset) { return debug_read(g_round_clocks, out, reset); }
 #endif
 
 void large_scratch_release(LargeScratch& s) {
