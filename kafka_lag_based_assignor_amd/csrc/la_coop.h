@@ -14,22 +14,13 @@ namespace la {
 constexpr int kCoopLaunches = 2;            // insert | lookup: what la_last_launches reports at most (lagassign.h)
 constexpr int64_t kCoopMaxOwned = 1ll << 40;      // beyond it the table is not even asked for (hipErrorOutOfMemory)
 
-// ---- device code both compile units share: the key, its first slot, a wavefront sum, the bisection of an offset array ----------
+// ---- device code both compile units share: the key, its first slot, the bisection of an offset array --------------------------
 __device__ __forceinline__ uint64_t coop_key(int32_t topic, int32_t id) {
     return ((uint64_t)(uint32_t)(topic + 1) << 32) | (uint32_t)id;
 }
 
 __device__ __forceinline__ uint64_t coop_first_slot(uint64_t key, int bits) {       // Fibonacci hashing over both halves of the key
     return (key * 0x9E3779B97F4A7C15ull) >> (64 - bits);
-}
-
-__device__ __forceinline__ uint64_t wave_sum_u64(uint64_t v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, d), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), d);
-        v += ((uint64_t)hi << 32) | lo;
-    }
-    return v;
 }
 
 // largest r in [lo, hi) with off[r] <= x, for lo < hi; with offsets that do not ascend some r of that range all the same

@@ -258,44 +258,24 @@ hipError_t cooperative_adjust_launch(CoopScratch& s, const CoopCall& c, uint32_t
     if (c.topic_withheld && T && (e = hipMemsetAsync(c.topic_withheld, 0, (size_t)T * 8, stream)) != hipSuccess) return e;
     if (c.summary && (e = hipMemsetAsync(c.summary, 0, 6 * 8, stream)) != hipSuccess) return e;
 
-    const dim3 block(kMovesThreads);
-    int resident = 0;
     if (n > 0) {
         if ((e = hipMemsetAsync(a.keys, 0, (size_t)8 << a.bits, stream)) != hipSuccess) return e;
         a.n_chunks = (n + kMovesChunk - 1) / kMovesChunk;
         // (the grid also shares the check of the M + 1 offsets: a few owned entries of very many members get workgroups for it)
         const int64_t want = std::max<int64_t>(a.n_chunks, M / kMovesThreads + 1);
-        if (M <= kMovesLdsMaxMembers) {
-            const size_t lds = (size_t)(M + 1) * 8;
-            if ((e = moves_resident(coop_insert_kernel<true>, 0, lds, &resident)) != hipSuccess) return e;
-            LA_LAUNCH((coop_insert_kernel<true>), dim3((unsigned)std::min<int64_t>(want, resident)), block, lds, stream, a);
-        } else {
-            if ((e = moves_resident(coop_insert_kernel<false>, 1, 0, &resident)) != hipSuccess) return e;
-            LA_LAUNCH((coop_insert_kernel<false>), dim3((unsigned)std::min<int64_t>(want, resident)), block, 0, stream, a);
-        }
-        if ((e = hipGetLastError()) != hipSuccess) return e;
+        e = M <= kMovesLdsMaxMembers ? launch_resident<coop_insert_kernel<true>>(want, kMovesThreads, (size_t)(M + 1) * 8, stream, a)
+                                     : launch_resident<coop_insert_kernel<false>>(want, kMovesThreads, 0, stream, a);
+        if (e != hipSuccess) return e;
     }
     if (T > 0 && N > 0) {
         a.n_chunks = (N + kMovesChunk - 1) / kMovesChunk;
         const int64_t want = std::max<int64_t>(a.n_chunks, T / kMovesThreads + 1);      // (as above, for the T + 1 part offsets)
         const bool bins = (c.member_kept || c.member_fresh || c.member_pending || c.member_release) && M > 0 &&
                           M <= kMovesLdsMaxMembers && N < kMovesMaxBinned;
-        if (bins) {
-            tables_for(4 * M, &a.tables, &a.stride);
-            const size_t lds = (size_t)a.tables * a.stride * 4;
-            static PerDeviceOnce lds_opt_in;
-            if ((e = lds_opt_in.run([] {
-                     return hipFuncSetAttribute((const void*)coop_lookup_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                (int)kCoopMaxBinBytes);
-                 })) != hipSuccess)
-                return e;
-            if ((e = moves_resident(coop_lookup_kernel<true>, 2, lds, &resident)) != hipSuccess) return e;
-            LA_LAUNCH((coop_lookup_kernel<true>), dim3((unsigned)std::min<int64_t>(want, resident)), block, lds, stream, a);
-        } else {
-            if ((e = moves_resident(coop_lookup_kernel<false>, 3, 0, &resident)) != hipSuccess) return e;
-            LA_LAUNCH((coop_lookup_kernel<false>), dim3((unsigned)std::min<int64_t>(want, resident)), block, 0, stream, a);
-        }
-        if ((e = hipGetLastError()) != hipSuccess) return e;
+        if (!bins) return launch_resident<coop_lookup_kernel<false>>(want, kMovesThreads, 0, stream, a);
+        tables_for(4 * M, kMovesFewBins, kMovesMaxTables, &a.tables, &a.stride);
+        const size_t lds = (size_t)a.tables * a.stride * 4;
+        return launch_resident_lds<coop_lookup_kernel<true>, kCoopMaxBinBytes>(want, kMovesThreads, lds, stream, a);
     }
     return hipSuccess;
 }

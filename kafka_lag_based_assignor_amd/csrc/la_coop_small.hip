@@ -29,7 +29,6 @@
 // zero-copy host call.  The target comes from device memory, the offsets, the owned arrays and every output lie in the call's
 // mapped staging buffer, the target is handed on to the host from the stage phase where it is wanted, and the launch ends with
 // `done | status` in the word the calling thread spins on.  kFinish == false is the kernel as it was.
-#include "la_moves_shared.h"
 #include "la_coop.h"
 
 #include <type_traits>
@@ -335,14 +334,8 @@ hipError_t cooperative_round_launch(CoopScratch& s, LargeScratch& large, const C
         a.r = r;
         a.status = status;
         a.bits = r.c.n_owned > 0 ? ceil_log2(2 * r.c.n_owned) : 1;
-        static PerDeviceOnce lds_opt_in;
-        if ((e = lds_opt_in.run([] {
-                 return hipFuncSetAttribute((const void*)coop_round_small_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            (int)kCoopSmallLdsBytes);
-             })) != hipSuccess)
-            return e;
-        LA_LAUNCH(coop_round_small_kernel<false>, dim3(1), dim3(NT), kCoopSmallLdsBytes, stream, a);
-        return hipGetLastError();
+        if ((e = opt_in_lds<coop_round_small_kernel<false>, kCoopSmallLdsBytes>()) != hipSuccess) return e;
+        return launch_grid<coop_round_small_kernel<false>>(1, NT, kCoopSmallLdsBytes, stream, a);
     }
     // the general form: the table in device memory, then the grouping of the adjusted ranks
     CoopCall c = r.c;
@@ -368,14 +361,9 @@ hipError_t cooperative_round_finish_launch(const CoopRoundCall& r, int32_t* targ
     a.target_partition = target_partition;
     a.target_rank = target_rank;
     a.fin_flag = fin_flag;
-    static PerDeviceOnce lds_opt_in;
-    const hipError_t e = lds_opt_in.run([] {
-        return hipFuncSetAttribute((const void*)coop_round_small_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)kCoopSmallLdsBytes);
-    });
+    const hipError_t e = opt_in_lds<coop_round_small_kernel<true>, kCoopSmallLdsBytes>();
     if (e != hipSuccess) return e;
-    LA_LAUNCH(coop_round_small_kernel<true>, dim3(1), dim3(NT), kCoopSmallLdsBytes, stream, a);
-    return hipGetLastError();
+    return launch_grid<coop_round_small_kernel<true>>(1, NT, kCoopSmallLdsBytes, stream, a);
 }
 
 }  // namespace la

@@ -204,6 +204,27 @@ __device__ __forceinline__ uint32_t wave_or_u32(uint32_t v) {
     return v;
 }
 
+// sums over the whole wavefront, result in every lane
+__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += (uint32_t)__shfl_xor((int)v, d);
+    return v;
+}
+
+__device__ __forceinline__ uint64_t wave_sum_u64(uint64_t v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, d), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), d);
+        v += ((uint64_t)hi << 32) | lo;
+    }
+    return v;
+}
+
+// a wrapping 64-bit add to a counter in device memory that other workgroups add to as well
+__device__ __forceinline__ void global_add(int64_t* p, uint64_t v) {
+    __hip_atomic_fetch_add((unsigned long long*)p, (unsigned long long)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 // LDS accesses made by one wave are executed in order; these only stop the compiler from
 // moving them across the point where lanes exchange data through LDS.
 __device__ __forceinline__ void wave_lds_fence() {

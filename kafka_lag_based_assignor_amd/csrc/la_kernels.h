@@ -3,37 +3,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <atomic>
+#include "la_launch.h"
 
 namespace la {
-
-// Kernel launches of the whole library, counted where they are issued: la_last_launches (lagassign.h) reports the difference
-// over one call -- how a test asserts "one launch" for a batch whose bounds prove that every tile packs.  Process-wide (the
-// lanes of a host-buffer call launch from their own threads), relaxed: a diagnostic, not a synchronisation point.
-inline std::atomic<uint64_t> g_kernel_launches{0};
-#define LA_LAUNCH(...)                                                        \
-    do {                                                                      \
-        ::la::g_kernel_launches.fetch_add(1, std::memory_order_relaxed);      \
-        hipLaunchKernelGGL(__VA_ARGS__);                                      \
-    } while (0)
-
-// hipFuncSetAttribute(MaxDynamicSharedMemorySize) applies to the CURRENT device, and a process may hold contexts
-// on several: one bit per device id remembers where a kernel has been opted in (ids >= 32: set on every launch).
-// Calls may come from several host threads (one per shard lane), hence the atomic.
-struct PerDeviceOnce {
-    std::atomic<uint32_t> mask{0};
-    template <typename F>
-    hipError_t run(F&& set) {
-        int dev = 0;
-        hipError_t e = hipGetDevice(&dev);
-        if (e != hipSuccess) return e;
-        const uint32_t bit = (dev >= 0 && dev < 32) ? (1u << dev) : 0u;
-        if (bit && (mask.load(std::memory_order_acquire) & bit)) return hipSuccess;
-        if ((e = set()) != hipSuccess) return e;
-        if (bit) mask.fetch_or(bit, std::memory_order_release);
-        return hipSuccess;
-    }
-};
 
 // device status word bits (la_ctx::d_status)
 constexpr uint32_t kStatusShape = 1u;      // a topic exceeded the shape hint
@@ -316,11 +288,7 @@ constexpr int32_t kMovesNoPrevious = -2;                // LA_MOVES_NO_PREVIOUS 
 struct MovesScratch {           // of one shard, grown lazily: never the assign scratch (results kept on the device stay valid)
     void* table = nullptr;      // the global form's hash table
     size_t table_cap = 0;
-    void* d_items = nullptr;    // its topic list, built in h_items (pinned) and copied on the call's stream
-    size_t d_items_cap = 0;
-    void* h_items = nullptr;
-    size_t h_items_cap = 0;
-    hipEvent_t copied = nullptr;    // the last copy out of h_items
+    StagedList list;            // its topic list
 };
 
 struct MovesCall {              // la_moves_args (lagassign.h), validated
@@ -373,11 +341,7 @@ constexpr uint32_t kVerdictIds = 1u, kVerdictOrder = 2u, kVerdictOwner = 4u, kVe
 struct VerifyScratch {          // of one shard, grown lazily: never the assign scratch (results kept on the device stay valid)
     void* work = nullptr;       // the global form's tables, one allocation carved into regions
     size_t work_cap = 0;
-    void* d_items = nullptr;    // its topic list, built in h_items (pinned) and copied on the call's stream
-    size_t d_items_cap = 0;
-    void* h_items = nullptr;
-    size_t h_items_cap = 0;
-    hipEvent_t copied = nullptr;    // the last copy out of h_items
+    StagedList list;            // its topic list
 };
 
 struct VerifyCall {             // la_device_batch (lagassign.h) as la_verify_assignment_device reads it, validated

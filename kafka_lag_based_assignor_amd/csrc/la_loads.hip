@@ -55,16 +55,6 @@ struct LoadsArgs {
     int32_t total16;                // total_lag + head_k is 16-byte aligned
 };
 
-__device__ __forceinline__ void global_add(int64_t* p, uint64_t v) {
-    __hip_atomic_fetch_add((unsigned long long*)p, (unsigned long long)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-__device__ __forceinline__ uint64_t wave_sum_u64(uint64_t v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += (uint64_t)__shfl_xor((unsigned long long)v, d);
-    return v;
-}
-
 template <bool LDS>
 __global__ __launch_bounds__(kLoadsThreads) void member_loads_kernel(LoadsArgs a) {
     extern __shared__ uint64_t loads_bins[];
@@ -169,39 +159,6 @@ inline int64_t head_elems(const int32_t* p, int64_t n) {
     return h < n ? h : n;
 }
 
-// tables of `bins` bins (stride: bins made odd) that fit `slots`, a power of two up to kLoadsMaxTables
-inline void tables_for(int64_t bins, int slots, int32_t* tables, int32_t* stride) {
-    const int64_t s = (bins < 1 ? 1 : bins) | 1;
-    int t = 1;
-    while (t * 2 <= kLoadsMaxTables && (int64_t)t * 2 * s <= slots) t *= 2;
-    *tables = t;
-    *stride = (int32_t)s;
-}
-
-// Resident workgroups of a form for its dynamic LDS, per device (as the tile path: two gfx950 devices need not expose the same
-// number of CUs).  One word per (device, form): LDS bytes << 32 | workgroups; several lanes may ask at once.  It remembers the
-// LAST table size only: a caller that alternates between member counts with different table sizes asks the runtime again on
-// every call (host arithmetic, a few microseconds; a rebalance has one member count).
-template <typename K>
-hipError_t loads_resident(K kernel, int form, size_t lds, int* out) {
-    static std::atomic<uint64_t> s_cache[32][2];
-    int dev = 0, cus = 0, per_cu = 0;
-    hipError_t e;
-    if ((e = hipGetDevice(&dev)) != hipSuccess) return e;
-    const bool cached = dev >= 0 && dev < 32;
-    if (cached) {
-        const uint64_t c = s_cache[dev][form].load(std::memory_order_relaxed);
-        if ((uint32_t)c != 0 && (c >> 32) == lds) { *out = (int)(uint32_t)c; return hipSuccess; }
-    }
-    if ((e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev)) != hipSuccess) return e;
-    if ((e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kLoadsThreads, lds)) != hipSuccess) return e;
-    if (per_cu < 1) per_cu = 1;
-    if (cus < 1) cus = 1;
-    *out = cus * per_cu;
-    if (cached) s_cache[dev][form].store(((uint64_t)lds << 32) | (uint32_t)*out, std::memory_order_relaxed);
-    return hipSuccess;
-}
-
 }  // namespace
 
 hipError_t member_loads_launch(int64_t n, const int32_t* member_rank, int64_t k, const int32_t* cons_rank,
@@ -238,14 +195,14 @@ hipError_t member_loads_launch(int64_t n, const int32_t* member_rank, int64_t k,
     a.tables_p = a.tables_k = 1;
     a.stride_p = a.stride_k = 1;
     if (lds) {
-        tables_for((int64_t)n_members + 1, kLoadsLdsBytes / 4, &a.tables_p, &a.stride_p);
-        tables_for((int64_t)n_members, kLoadsLdsBytes / 8, &a.tables_k, &a.stride_k);
+        tables_for((int64_t)n_members + 1, kLoadsLdsBytes / 4, kLoadsMaxTables, &a.tables_p, &a.stride_p);
+        tables_for((int64_t)n_members, kLoadsLdsBytes / 8, kLoadsMaxTables, &a.tables_k, &a.stride_k);
         const size_t bp = n > 0 ? (size_t)a.tables_p * a.stride_p * 4 : 0, bk = k > 0 ? (size_t)a.tables_k * a.stride_k * 8 : 0;
         lds_bytes = bp > bk ? bp : bk;
     }
     int resident = 0;
-    if (lds) e = loads_resident(member_loads_kernel<true>, 0, lds_bytes, &resident);
-    else e = loads_resident(member_loads_kernel<false>, 1, 0, &resident);
+    e = lds ? resident_workgroups<member_loads_kernel<true>>(kLoadsThreads, lds_bytes, &resident)
+            : resident_workgroups<member_loads_kernel<false>>(kLoadsThreads, 0, &resident);
     if (e != hipSuccess) return e;
 
     // Workgroups per half: what its vectors need (two per thread and pass for the ranks, one for the pairs), at least one where
@@ -269,10 +226,8 @@ hipError_t member_loads_launch(int64_t n, const int32_t* member_rank, int64_t k,
     gp = std::max(gp, ceil_div(n, kLoadsMaxPerBlock));                  // (only a buffer of terabytes gets here)
     if (gp + gk > 0x7FFFFFFF) return hipErrorInvalidValue;
     a.grid_p = (int32_t)gp;
-    const dim3 grid((unsigned)(gp + gk)), block(kLoadsThreads);
-    if (lds) LA_LAUNCH((member_loads_kernel<true>), grid, block, lds_bytes, stream, a);
-    else LA_LAUNCH((member_loads_kernel<false>), grid, block, 0, stream, a);
-    return hipGetLastError();
+    return lds ? launch_grid<member_loads_kernel<true>>(gp + gk, kLoadsThreads, lds_bytes, stream, a)
+               : launch_grid<member_loads_kernel<false>>(gp + gk, kLoadsThreads, 0, stream, a);
 }
 
 }  // namespace la

@@ -181,10 +181,8 @@ __global__ __launch_bounds__(kMovesThreads) void moves_global_kernel(MovesArgs a
 }  // namespace
 
 void moves_scratch_release(MovesScratch& s) {
-    if (s.copied) { (void)hipEventSynchronize(s.copied); (void)hipEventDestroy(s.copied); }
+    s.list.release();
     if (s.table) (void)hipFree(s.table);
-    if (s.d_items) (void)hipFree(s.d_items);
-    if (s.h_items) (void)hipHostFree(s.h_items);
     s = MovesScratch{};
 }
 
@@ -209,7 +207,7 @@ hipError_t assignment_moves_launch(MovesScratch& s, const MovesCall& c, const in
     const bool bins = (c.member_gained || c.member_lost) && M > 0 && M <= kMovesLdsMaxMembers && N < kMovesMaxBinned;
     size_t bin_bytes = 0;
     if (bins) {
-        tables_for(2 * M, &a.tables, &a.stride);
+        tables_for(2 * M, kMovesFewBins, kMovesMaxTables, &a.tables, &a.stride);
         bin_bytes = (size_t)a.tables * a.stride * 4;
     }
 
@@ -226,8 +224,8 @@ hipError_t assignment_moves_launch(MovesScratch& s, const MovesCall& c, const in
         if (n_big > 0) {
             if (n_big > 0x7FFFFFFF) return hipErrorInvalidValue;
             const size_t item_bytes = (size_t)n_big * sizeof(MovesBig);
-            if ((e = moves_items_reserve(s, item_bytes)) != hipSuccess) return e;
-            MovesBig* items = static_cast<MovesBig*>(s.h_items);
+            if ((e = s.list.reserve(item_bytes)) != hipSuccess) return e;
+            MovesBig* items = static_cast<MovesBig*>(s.list.h);
             int64_t slots = 0, chunks = 0, j = 0;
             for (int64_t t = 0; t < T; ++t) {
                 const int64_t np = h_part_off[t + 1] - h_part_off[t];
@@ -243,11 +241,10 @@ hipError_t assignment_moves_launch(MovesScratch& s, const MovesCall& c, const in
                 chunks += (np + kMovesChunk - 1) / kMovesChunk;
             }
             if ((e = grow_device(&s.table, &s.table_cap, (size_t)slots * 8)) != hipSuccess) return e;
-            if ((e = hipMemcpyAsync(s.d_items, s.h_items, item_bytes, hipMemcpyHostToDevice, stream)) != hipSuccess) return e;
-            if ((e = hipEventRecord(s.copied, stream)) != hipSuccess) return e;
+            if ((e = s.list.upload(item_bytes, stream)) != hipSuccess) return e;
             if ((e = hipMemsetAsync(s.table, 0, (size_t)slots * 8, stream)) != hipSuccess) return e;
             a.table = static_cast<uint64_t*>(s.table);
-            a.big = static_cast<const MovesBig*>(s.d_items);
+            a.big = static_cast<const MovesBig*>(s.list.d);
             a.n_big = (int32_t)n_big;
             a.n_chunks = chunks;
         }
@@ -258,38 +255,15 @@ hipError_t assignment_moves_launch(MovesScratch& s, const MovesCall& c, const in
         a.skip_large = global_form ? 1 : 0;
         a.table_bits = ceil_log2(2 * a.cap);
         const size_t lds = ((size_t)8 << a.table_bits) + bin_bytes + 8;
-        static PerDeviceOnce lds_opt_in;
-        if ((e = lds_opt_in.run([] {
-                 hipError_t e2 = hipFuncSetAttribute((const void*)moves_lds_kernel<true>,
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMovesMaxLdsBytes);
-                 if (e2 != hipSuccess) return e2;
-                 return hipFuncSetAttribute((const void*)moves_lds_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            (int)kMovesMaxLdsBytes);
-             })) != hipSuccess)
-            return e;
-        int resident = 0;
-        if (bins) e = moves_resident(moves_lds_kernel<true>, 0, lds, &resident);
-        else e = moves_resident(moves_lds_kernel<false>, 1, lds, &resident);
+        e = bins ? launch_resident_lds<moves_lds_kernel<true>, kMovesMaxLdsBytes>(T, kMovesThreads, lds, stream, a)
+                 : launch_resident_lds<moves_lds_kernel<false>, kMovesMaxLdsBytes>(T, kMovesThreads, lds, stream, a);
         if (e != hipSuccess) return e;
-        const dim3 grid((unsigned)std::min<int64_t>(T, resident)), block(kMovesThreads);
-        if (bins) LA_LAUNCH((moves_lds_kernel<true>), grid, block, lds, stream, a);
-        else LA_LAUNCH((moves_lds_kernel<false>), grid, block, lds, stream, a);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     if (a.n_big > 0) {
-        int resident = 0;
-        const dim3 block(kMovesThreads);
-        if ((e = moves_resident(moves_global_kernel<0, false>, 2, 0, &resident)) != hipSuccess) return e;
-        LA_LAUNCH((moves_global_kernel<0, false>), dim3((unsigned)std::min<int64_t>(a.n_chunks, resident)), block, 0, stream, a);
-        if (bins) {
-            if ((e = moves_resident(moves_global_kernel<1, true>, 3, bin_bytes, &resident)) != hipSuccess) return e;
-            LA_LAUNCH((moves_global_kernel<1, true>), dim3((unsigned)std::min<int64_t>(a.n_chunks, resident)), block, bin_bytes,
-                      stream, a);
-        } else {
-            if ((e = moves_resident(moves_global_kernel<1, false>, 4, 0, &resident)) != hipSuccess) return e;
-            LA_LAUNCH((moves_global_kernel<1, false>), dim3((unsigned)std::min<int64_t>(a.n_chunks, resident)), block, 0, stream, a);
-        }
-        if ((e = hipGetLastError()) != hipSuccess) return e;
+        if ((e = launch_resident<moves_global_kernel<0, false>>(a.n_chunks, kMovesThreads, 0, stream, a)) != hipSuccess) return e;
+        e = bins ? launch_resident<moves_global_kernel<1, true>>(a.n_chunks, kMovesThreads, bin_bytes, stream, a)
+                 : launch_resident<moves_global_kernel<1, false>>(a.n_chunks, kMovesThreads, 0, stream, a);
+        if (e != hipSuccess) return e;
     }
     return hipSuccess;
 }

@@ -315,14 +315,10 @@ __global__ __launch_bounds__(kMovesThreads) void moves_layouts_global_kernel(Lay
     if (bad) atomicOr(a.status, bad);
 }
 
+// a phase without steps launches nothing
 template <int PHASE, bool BINS>
-hipError_t launch_phase(const LayoutsArgs& a, int form, size_t lds, hipStream_t stream) {
-    int resident = 0;
-    const hipError_t e = moves_resident(moves_layouts_global_kernel<PHASE, BINS>, form, lds, &resident);
-    if (e != hipSuccess) return e;
-    LA_LAUNCH((moves_layouts_global_kernel<PHASE, BINS>), dim3((unsigned)std::min<int64_t>(a.n_chunks[PHASE], resident)),
-              dim3(kMovesThreads), lds, stream, a);
-    return hipSuccess;
+hipError_t launch_phase(const LayoutsArgs& a, size_t lds, hipStream_t stream) {
+    return launch_resident<moves_layouts_global_kernel<PHASE, BINS>>(a.n_chunks[PHASE], kMovesThreads, lds, stream, a);
 }
 
 }  // namespace
@@ -359,7 +355,7 @@ hipError_t assignment_moves_layouts_launch(MovesScratch& s, const MovesLayoutsCa
     const bool bins = (c.c.member_gained || c.c.member_lost) && M > 0 && M <= kMovesLdsMaxMembers && N + NP < kMovesMaxBinned;
     size_t bin_bytes = 0;
     if (bins) {
-        tables_for(2 * M, &a.tables, &a.stride);
+        tables_for(2 * M, kMovesFewBins, kMovesMaxTables, &a.tables, &a.stride);
         bin_bytes = (size_t)a.tables * a.stride * 4;
     }
 
@@ -377,8 +373,8 @@ hipError_t assignment_moves_layouts_launch(MovesScratch& s, const MovesLayoutsCa
         }
         if (n_big > 0) {
             const size_t item_bytes = (size_t)n_big * sizeof(LayoutsBig);
-            if ((e = moves_items_reserve(s, item_bytes)) != hipSuccess) return e;
-            LayoutsBig* items = static_cast<LayoutsBig*>(s.h_items);
+            if ((e = s.list.reserve(item_bytes)) != hipSuccess) return e;
+            LayoutsBig* items = static_cast<LayoutsBig*>(s.list.h);
             int64_t slots = 0, j = 0;
             for (int64_t t = 0; t < T; ++t) {
                 const int64_t np = h_part_off[t + 1] - h_part_off[t];
@@ -401,11 +397,10 @@ hipError_t assignment_moves_layouts_launch(MovesScratch& s, const MovesLayoutsCa
                 slots += n_slots;
             }
             if ((e = grow_device(&s.table, &s.table_cap, (size_t)slots * 8)) != hipSuccess) return e;
-            if ((e = hipMemcpyAsync(s.d_items, s.h_items, item_bytes, hipMemcpyHostToDevice, stream)) != hipSuccess) return e;
-            if ((e = hipEventRecord(s.copied, stream)) != hipSuccess) return e;
+            if ((e = s.list.upload(item_bytes, stream)) != hipSuccess) return e;
             if (slots && (e = hipMemsetAsync(s.table, 0, (size_t)slots * 8, stream)) != hipSuccess) return e;
             a.table = static_cast<uint64_t*>(s.table);
-            a.big = static_cast<const LayoutsBig*>(s.d_items);
+            a.big = static_cast<const LayoutsBig*>(s.list.d);
             a.n_big = (int32_t)n_big;
         }
     }
@@ -415,32 +410,14 @@ hipError_t assignment_moves_layouts_launch(MovesScratch& s, const MovesLayoutsCa
         a.skip_large = global_form ? 1 : 0;
         a.table_bits = ceil_log2(2 * a.cap);
         const size_t lds = ((size_t)8 << a.table_bits) + bin_bytes + kLayoutsCounterBytes;
-        static PerDeviceOnce lds_opt_in;
-        if ((e = lds_opt_in.run([] {
-                 hipError_t e2 = hipFuncSetAttribute((const void*)moves_layouts_lds_kernel<true>,
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLayoutsMaxLdsBytes);
-                 if (e2 != hipSuccess) return e2;
-                 return hipFuncSetAttribute((const void*)moves_layouts_lds_kernel<false>,
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLayoutsMaxLdsBytes);
-             })) != hipSuccess)
-            return e;
-        int resident = 0;
-        if (bins) e = moves_resident(moves_layouts_lds_kernel<true>, 0, lds, &resident);
-        else e = moves_resident(moves_layouts_lds_kernel<false>, 1, lds, &resident);
+        e = bins ? launch_resident_lds<moves_layouts_lds_kernel<true>, kLayoutsMaxLdsBytes>(T, kMovesThreads, lds, stream, a)
+                 : launch_resident_lds<moves_layouts_lds_kernel<false>, kLayoutsMaxLdsBytes>(T, kMovesThreads, lds, stream, a);
         if (e != hipSuccess) return e;
-        const dim3 grid((unsigned)std::min<int64_t>(T, resident)), block(kMovesThreads);
-        if (bins) LA_LAUNCH((moves_layouts_lds_kernel<true>), grid, block, lds, stream, a);
-        else LA_LAUNCH((moves_layouts_lds_kernel<false>), grid, block, lds, stream, a);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
     }
-    if (a.n_chunks[kInsert] > 0 && (e = launch_phase<kInsert, false>(a, 2, 0, stream)) != hipSuccess) return e;
-    if (a.n_chunks[kLookup] > 0 &&
-        (e = bins ? launch_phase<kLookup, true>(a, 3, bin_bytes, stream) : launch_phase<kLookup, false>(a, 4, 0, stream)) != hipSuccess)
-        return e;
-    if (a.n_chunks[kSweep] > 0 &&
-        (e = bins ? launch_phase<kSweep, true>(a, 5, bin_bytes, stream) : launch_phase<kSweep, false>(a, 6, 0, stream)) != hipSuccess)
-        return e;
-    return a.n_big > 0 ? hipGetLastError() : hipSuccess;
+    if ((e = launch_phase<kInsert, false>(a, 0, stream)) != hipSuccess) return e;
+    e = bins ? launch_phase<kLookup, true>(a, bin_bytes, stream) : launch_phase<kLookup, false>(a, 0, stream);
+    if (e != hipSuccess) return e;
+    return bins ? launch_phase<kSweep, true>(a, bin_bytes, stream) : launch_phase<kSweep, false>(a, 0, stream);
 }
 
 }  // namespace la

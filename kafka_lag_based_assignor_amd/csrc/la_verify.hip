@@ -97,12 +97,6 @@ struct VerifyLayout {
     size_t bytes;
 };
 
-inline int ceil_log2(int64_t x) {                  // smallest b with 2^b >= x, at least 1
-    int b = 1;
-    while (((int64_t)1 << b) < x) ++b;
-    return b;
-}
-
 inline VerifyLayout layout_for(int64_t cap_p, int64_t cap_c) {
     VerifyLayout l{};
     const size_t a = std::max((size_t)8 << ceil_log2(2 * cap_p), (size_t)8 * (size_t)(cap_p + cap_c));
@@ -488,49 +482,10 @@ __global__ __launch_bounds__(kVgThreads) void verify_global_kernel(VerifyGlobalA
     if (bad) atomicOr(a.status, bad);
 }
 
-// a x b and a + b in size_t; false: the result does not fit
-inline bool mul_ok(size_t a, size_t b, size_t* out) { return !__builtin_mul_overflow(a, b, out); }
-inline bool add_ok(size_t a, size_t b, size_t* out) { return !__builtin_add_overflow(a, b, out); }
-
-inline int64_t ceil_sqrt(int64_t x) {               // smallest r >= 1 with r r >= x
-    int64_t r = (int64_t)__builtin_sqrt((double)x);
-    if (r < 1) r = 1;
-    while (r * r < x) ++r;
-    while (r > 1 && (r - 1) * (r - 1) >= x) --r;
-    return r;
-}
-
-hipError_t grow_verify_device(void** p, size_t* cap, size_t bytes) {
-    if (bytes <= *cap) return hipSuccess;
-    if (*p) { (void)hipFree(*p); *p = nullptr; *cap = 0; }
-    size_t want = 0;
-    if (!add_ok(bytes, bytes / 4 + 256, &want)) return hipErrorOutOfMemory;
-    const hipError_t e = hipMalloc(p, want);
-    if (e != hipSuccess) { *p = nullptr; (void)hipGetLastError(); return hipErrorOutOfMemory; }
-    *cap = want;
-    return hipSuccess;
-}
-
-hipError_t verify_cus(int* out) {                   // compute units of the current device (asked once per device)
-    static std::atomic<int> s_cus[32];
-    int dev = 0, cus = 0;
-    hipError_t e;
-    if ((e = hipGetDevice(&dev)) != hipSuccess) return e;
-    const bool cached = dev >= 0 && dev < 32;
-    if (cached && (cus = s_cus[dev].load(std::memory_order_relaxed)) > 0) { *out = cus; return hipSuccess; }
-    if ((e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev)) != hipSuccess) return e;
-    if (cus < 1) cus = 1;
-    if (cached) s_cus[dev].store(cus, std::memory_order_relaxed);
-    *out = cus;
-    return hipSuccess;
-}
-
+// a phase of the global form: a grid of 8 workgroups per compute unit walks its steps (a phase without steps launches nothing)
 template <int PHASE>
 hipError_t verify_global_launch(const VerifyGlobalArgs& a, int64_t steps, int cus, hipStream_t stream) {
-    if (steps <= 0) return hipSuccess;
-    const dim3 grid((unsigned)std::min<int64_t>(steps, (int64_t)cus * 8)), block(kVgThreads);
-    LA_LAUNCH((verify_global_kernel<PHASE>), grid, block, 0, stream, a);
-    return hipGetLastError();
+    return launch_grid<verify_global_kernel<PHASE>>(std::min<int64_t>(steps, (int64_t)cus * 8), kVgThreads, 0, stream, a);
 }
 
 // Lists the topics over the LDS limit from the host's offsets, takes their working memory and enqueues the global form.
@@ -549,23 +504,10 @@ hipError_t verify_global_form(VerifyScratch& s, const VerifyCall& c, const int64
 
     size_t item_bytes = 0;
     if (!mul_ok((size_t)n_big, sizeof(VerifyBig), &item_bytes)) return hipErrorOutOfMemory;
-    if (s.copied && (e = hipEventSynchronize(s.copied)) != hipSuccess) return e;      // the last call's copy has read h_items
-    if (item_bytes > s.h_items_cap) {
-        if (s.h_items) { (void)hipHostFree(s.h_items); s.h_items = nullptr; s.h_items_cap = 0; }
-        size_t want = 0;
-        if (!add_ok(item_bytes, item_bytes / 4 + 256, &want)) return hipErrorOutOfMemory;
-        if (hipHostMalloc(&s.h_items, want, hipHostMallocDefault) != hipSuccess) {
-            s.h_items = nullptr;
-            (void)hipGetLastError();
-            return hipErrorOutOfMemory;
-        }
-        s.h_items_cap = want;
-    }
-    if ((e = grow_verify_device(&s.d_items, &s.d_items_cap, item_bytes)) != hipSuccess) return e;
-    if (!s.copied && (e = hipEventCreateWithFlags(&s.copied, hipEventDisableTiming)) != hipSuccess) return e;
+    if ((e = s.list.reserve(item_bytes)) != hipSuccess) return e;
 
     // regions, counted in elements; every sum is checked (a count that does not fit cannot be allocated either)
-    VerifyBig* items = static_cast<VerifyBig*>(s.h_items);
+    VerifyBig* items = static_cast<VerifyBig*>(s.list.h);
     size_t n_table = 0, n_part = 0, n_slot = 0, n_cons = 0, n_sum = 0;
     int64_t steps[3] = {0, 0, 0};
     int64_t j = 0;
@@ -609,9 +551,9 @@ hipError_t verify_global_form(VerifyScratch& s, const VerifyCall& c, const int64
            add_ok(words8, n_sum, &words8) && add_ok(n_slot, (size_t)n_big, &words4) && mul_ok(words8, 8, &bytes8) &&
            mul_ok(words4, 4, &bytes4) && add_ok(bytes8, bytes4, &bytes);
     if (!fits) return hipErrorOutOfMemory;
-    if ((e = grow_verify_device(&s.work, &s.work_cap, bytes)) != hipSuccess) return e;
+    if ((e = grow_device(&s.work, &s.work_cap, bytes)) != hipSuccess) return e;
     int cus = 0;
-    if ((e = verify_cus(&cus)) != hipSuccess) return e;
+    if ((e = device_cus(&cus)) != hipSuccess) return e;
 
     VerifyWork g{};
     g.table = static_cast<uint64_t*>(s.work);
@@ -622,12 +564,11 @@ hipError_t verify_global_form(VerifyScratch& s, const VerifyCall& c, const int64
     g.sums = reinterpret_cast<uint64_t*>(g.tot_last + n_cons);
     g.slot = reinterpret_cast<uint32_t*>(g.sums + n_sum);
     g.bits = g.slot + n_slot;
-    g.big = static_cast<const VerifyBig*>(s.d_items);
+    g.big = static_cast<const VerifyBig*>(s.list.d);
     g.n_big = (int32_t)std::min<int64_t>(n_big, 0x7FFFFFFF);      // (T is 32 bits wide)
     for (int d = 0; d < 3; ++d) g.steps[d] = steps[d];
 
-    if ((e = hipMemcpyAsync(s.d_items, s.h_items, item_bytes, hipMemcpyHostToDevice, stream)) != hipSuccess) return e;
-    if ((e = hipEventRecord(s.copied, stream)) != hipSuccess) return e;
+    if ((e = s.list.upload(item_bytes, stream)) != hipSuccess) return e;
     if ((e = hipMemsetAsync(g.table, 0, n_table * 8, stream)) != hipSuccess) return e;
     if (n_slot && (e = hipMemsetAsync(g.slot, 0xFF, n_slot * 4, stream)) != hipSuccess) return e;
     if ((e = hipMemsetAsync(g.bits, 0, (size_t)n_big * 4, stream)) != hipSuccess) return e;
@@ -646,35 +587,11 @@ hipError_t verify_global_form(VerifyScratch& s, const VerifyCall& c, const int64
     return hipSuccess;
 }
 
-// Resident workgroups of the kernel for a workgroup size and its dynamic LDS, per device; one word per device:
-// LDS bytes << 40 | threads << 24 | workgroups.  It remembers the last request only (host arithmetic otherwise).
-hipError_t verify_resident(int threads, size_t lds, int* out) {
-    static std::atomic<uint64_t> s_cache[32];
-    int dev = 0, cus = 0, per_cu = 0;
-    hipError_t e;
-    if ((e = hipGetDevice(&dev)) != hipSuccess) return e;
-    const bool cached = dev >= 0 && dev < 32;
-    const uint64_t key = ((uint64_t)lds << 40) | ((uint64_t)threads << 24);
-    if (cached) {
-        const uint64_t w = s_cache[dev].load(std::memory_order_relaxed);
-        if ((w & 0xFFFFFFu) != 0 && (w & ~(uint64_t)0xFFFFFFu) == key) { *out = (int)(w & 0xFFFFFFu); return hipSuccess; }
-    }
-    if ((e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev)) != hipSuccess) return e;
-    if ((e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, verify_kernel, threads, lds)) != hipSuccess) return e;
-    if (per_cu < 1) per_cu = 1;
-    if (cus < 1) cus = 1;
-    *out = (int)std::min<int64_t>((int64_t)cus * per_cu, 0xFFFFFF);
-    if (cached) s_cache[dev].store(key | (uint32_t)*out, std::memory_order_relaxed);
-    return hipSuccess;
-}
-
 }  // namespace
 
 void verify_scratch_release(VerifyScratch& s) {
-    if (s.copied) { (void)hipEventSynchronize(s.copied); (void)hipEventDestroy(s.copied); }
+    s.list.release();
     if (s.work) (void)hipFree(s.work);
-    if (s.d_items) (void)hipFree(s.d_items);
-    if (s.h_items) (void)hipHostFree(s.h_items);
     s = VerifyScratch{};
 }
 
@@ -707,17 +624,7 @@ hipError_t verify_assignment_launch(VerifyScratch* large, const VerifyCall& c, c
     a.off_kidx = l.off_kidx;
     a.off_bits = l.off_bits;
     const int threads = a.cap_p <= kVerifyFewPartitions ? kVerifyFewThreads : kVerifyThreads;
-    static PerDeviceOnce lds_opt_in;
-    if ((e = lds_opt_in.run([] {
-             return hipFuncSetAttribute((const void*)verify_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)kVerifyMaxLdsBytes);
-         })) != hipSuccess)
-        return e;
-    int resident = 0;
-    if ((e = verify_resident(threads, l.bytes, &resident)) != hipSuccess) return e;
-    const dim3 grid((unsigned)std::min<int64_t>(c.n_topics, resident)), block((unsigned)threads);
-    LA_LAUNCH(verify_kernel, grid, block, l.bytes, stream, a);
-    return hipGetLastError();
+    return launch_resident_lds<verify_kernel, kVerifyMaxLdsBytes>(c.n_topics, threads, l.bytes, stream, a);
 }
 
 }  // namespace la
