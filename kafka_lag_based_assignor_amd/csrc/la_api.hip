@@ -225,7 +225,7 @@ int stage_topic_lists(la_ctx* ctx, Lane& ln, const BatchPlan& plan, int64_t T, h
     return LA_OK;
 }
 
-int launch_block_topics(la_ctx* ctx, Lane& ln, const la_device_batch* b, const BatchPlan& plan, const int32_t* d_lists,
+int launch_block_topics(la_ctx* ctx, const la_device_batch* b, const BatchPlan& plan, const int32_t* d_lists, uint32_t* status,
                         hipStream_t stream) {
     la::BlockArgs g{};
     g.part_off = b->d_part_off;
@@ -239,7 +239,7 @@ int launch_block_topics(la_ctx* ctx, Lane& ln, const la_device_batch* b, const B
     g.out_pid = b->d_out_partition;
     g.out_rank = b->d_out_member_rank;
     g.out_total = b->d_out_total_lag;
-    g.status = ln.status();
+    g.status = status;
     g.reset_latest = (b->reset_mode == LA_RESET_LATEST) ? 1 : 0;
     if (!d_lists) {
         // a handful of block topics: their indices travel in the kernel arguments (no copy, no event)
@@ -262,7 +262,8 @@ int launch_block_topics(la_ctx* ctx, Lane& ln, const la_device_batch* b, const B
     return LA_OK;
 }
 
-int launch_large_topics(la_ctx* ctx, Lane& ln, const la_device_batch* b, const BatchPlan& plan, bool argmin, hipStream_t stream) {
+int launch_large_topics(la_ctx* ctx, Lane& ln, const la_device_batch* b, const BatchPlan& plan, bool argmin, uint32_t* status,
+                        hipStream_t stream) {
     // The per-topic loop of assign(Map,Map) (Main.java:177-184) is independent across topics: all large topics of the batch
     // run SIDE BY SIDE (la::large_topics_launch: every phase one launch over all of them, one greedy workgroup per topic),
     // in groups bounded by scratch memory.  Topics with more consumers than the one-workgroup greedy holds take the
@@ -306,7 +307,7 @@ int launch_large_topics(la_ctx* ctx, Lane& ln, const la_device_batch* b, const B
         const bool bounded_large = (b->flags & LA_FLAG_BOUNDS) && b->max_lag_hint >= 0 && b->max_partition_id_hint >= 0;
         g.max_lag_hint = bounded_large ? b->max_lag_hint : -1;
         g.max_id_hint = bounded_large ? b->max_partition_id_hint : -1;
-        g.status = ln.status();
+        g.status = status;
         hipError_t e = hipSuccess;
         if (c > la::kLargeMaxConsumers) {
             if (int rc = flush()) return rc;
@@ -330,8 +331,11 @@ int launch_large_topics(la_ctx* ctx, Lane& ln, const la_device_batch* b, const B
 
 }  // namespace
 
-// The dispatcher shared by the host and device entry points.
-int enqueue_batch(la_ctx* ctx, Lane& ln, const la_device_batch* b, hipStream_t stream) {
+// The dispatcher shared by the host and device entry points (`staged`: what a staged host-buffer call adds, see la_ctx.h).
+int enqueue_batch(la_ctx* ctx, Lane& ln, const la_device_batch* b, hipStream_t stream, StagedBatch* staged) {
+    uint32_t* const status = staged && staged->status ? staged->status : ln.d_status;
+    const la::TileTail* const tail = staged ? staged->tail : nullptr;
+    bool* const tail_done = staged ? &staged->tail_done : nullptr;
     if (b->n_topics < 0 || b->n_partitions < 0 || b->n_consumers < 0)
         return fail(ctx, LA_EINVAL, "negative size");
     if (b->n_topics == 0) return LA_OK;
@@ -374,7 +378,7 @@ int enqueue_batch(la_ctx* ctx, Lane& ln, const la_device_batch* b, hipStream_t s
     a.out_pid = b->d_out_partition;
     a.out_rank = b->d_out_member_rank;
     a.out_total = b->d_out_total_lag;
-    a.status = ln.status();
+    a.status = status;
     a.reset_latest = (b->reset_mode == LA_RESET_LATEST) ? 1 : 0;
     a.n_total = b->n_partitions;
     a.flags = b->flags & (LA_FLAG_INDEX64 | LA_FLAG_DEFER_WIDE);
@@ -438,9 +442,9 @@ int enqueue_batch(la_ctx* ctx, Lane& ln, const la_device_batch* b, hipStream_t s
         if (proven(b->max_partitions_per_topic, b->max_consumers_per_topic)) a.flags |= la::kTileNoDefer;
         next_counters(a);
         LA_HIP(ctx, counter_err);
-        if (ln.tail_wanted && tile_mode == 0) a.tail = ln.tail;           // the batch is this one launch
+        if (tail && tile_mode == 0) a.tail = *tail;                       // the batch is this one launch
         LA_HIP(ctx, la::wave_tile_launch(a, b->max_partitions_per_topic, b->max_consumers_per_topic, tile_mode, stream,
-                                         &ln.tail_done));
+                                         tail_done));
         return LA_OK;
     }
     la_device_batch with_host;
@@ -487,13 +491,13 @@ int enqueue_batch(la_ctx* ctx, Lane& ln, const la_device_batch* b, hipStream_t s
         next_counters(run);
         LA_HIP(ctx, counter_err);
         // (a tail only when nothing else of the batch runs behind this launch)
-        if (ln.tail_wanted && tile_mode == 0 && plan.n_block_all == 0 && plan.n_large == 0) run.tail = ln.tail;
-        LA_HIP(ctx, la::wave_tile_launch(run, plan.tile_mp, plan.tile_mc, tile_mode, stream, &ln.tail_done));
+        if (tail && tile_mode == 0 && plan.n_block_all == 0 && plan.n_large == 0) run.tail = *tail;
+        LA_HIP(ctx, la::wave_tile_launch(run, plan.tile_mp, plan.tile_mc, tile_mode, stream, tail_done));
     }
     if (plan.n_block_all > 0)
-        if (int rc = launch_block_topics(ctx, ln, b, plan, d_lists, stream)) return rc;
+        if (int rc = launch_block_topics(ctx, b, plan, d_lists, status, stream)) return rc;
     if (plan.n_large > 0)
-        if (int rc = launch_large_topics(ctx, ln, b, plan, argmin, stream)) return rc;
+        if (int rc = launch_large_topics(ctx, ln, b, plan, argmin, status, stream)) return rc;
     return LA_OK;
 }
 

@@ -54,9 +54,6 @@ struct Lane {
     hipStream_t stream = nullptr;
     uint32_t* d_status = nullptr;        // 256 B: word 0 = status bits, words 16..19 = deferred-tile counters
     uint32_t* h_status = nullptr;        // pinned word the status is copied to (one stream sync per call)
-    uint32_t* status_word = nullptr;     // small-batch call: the status word lives inside the call's one device staging
-                                         // buffer (uploaded as zero with the inputs, downloaded with the results)
-    uint32_t* status() const { return status_word ? status_word : d_status; }
     // tile path: list of tiles the packed kernel leaves to the wide kernel, and which of the two
     // counters (d_status + 16 / + 17 words) the next launch uses
     DevBuf defer;
@@ -71,10 +68,6 @@ struct Lane {
     } stage[4];
     unsigned stage_next = 0;
     la::LargeScratch large;              // scratch of the large-topic path and of la_group_by_member
-    // a zero-copy small call asks the dispatcher to hang its tail (lists + completion word, la::TileTail) on the batch's tile
-    // launch; honoured only when the batch IS one single-launch tile kernel -- tail_done says whether it was
-    la::TileTail tail{};
-    bool tail_wanted = false, tail_done = false;
     std::vector<uint8_t> topic_class;    // host scratch of the dispatcher: path / class of every topic
     std::vector<int64_t> host_offsets;   // offsets fetched from the device when the caller gave no host copy
 };
@@ -223,7 +216,6 @@ struct la_ctx {
                                          // 1 = lanes (a host thread per stream; pageable arrays), 2 = three streams, no threads (pinned)
     std::vector<void*> comms;            // la_allgather_results: one ncclComm_t per shard, created on first use
     size_t zero_copy_bytes = 0;          // calls whose staging layout is at most this large run zero-copy (assign_small_zc)
-    size_t small_bytes = 0;              // ... and up to this large as ONE staging buffer at all (zero-copy or one copy)
     int last_shards = 0;                 // shards the last call used
     int32_t last_bounds[65] = {};        // their topic ranges
     la_call_hints hints{};               // la_hint_next_call: what the caller knows about its next host-buffer assign call
@@ -277,11 +269,11 @@ inline int reserve(la_ctx* ctx, DevBuf& b, size_t bytes) {
     return LA_OK;
 }
 
-inline int reserve_host(la_ctx* ctx, HostBuf& b, size_t bytes) {
+inline int reserve_host(la_ctx* ctx, HostBuf& b, size_t bytes, unsigned flags = hipHostMallocPortable) {
     if (bytes <= b.cap) return LA_OK;
     if (b.p) { LA_HIP(ctx, hipHostFree(b.p)); b.p = nullptr; b.cap = 0; }
     const size_t want = bytes + bytes / 4 + 256;
-    LA_HIP(ctx, hipHostMalloc(&b.p, want, hipHostMallocPortable));
+    LA_HIP(ctx, hipHostMalloc(&b.p, want, flags));
     b.cap = want;
     return LA_OK;
 }
@@ -382,7 +374,16 @@ int shard_entry(la_ctx* ctx, int shard, const char* on_throw, F&& body) {
 }
 
 // ---- la_api.hip: the dispatcher shared by the host and device entry points ---------------------------------------------
-int enqueue_batch(la_ctx* ctx, Lane& ln, const la_device_batch* b, hipStream_t stream);
+// What a staged host-buffer call (la_host.hip) asks of the dispatcher on top of the batch; every other caller passes nothing.
+struct StagedBatch {
+    uint32_t* status = nullptr;          // the status word of this batch's kernels instead of the lane's: a one-copy call keeps it inside
+                                         // its device staging buffer (uploaded as zero with the inputs, downloaded with the results)
+    // a zero-copy call asks for its tail (lists + completion word, la::TileTail) on the batch's tile launch; honoured only when the
+    // batch IS one single-launch tile kernel -- tail_done says whether it was
+    const la::TileTail* tail = nullptr;
+    bool tail_done = false;
+};
+int enqueue_batch(la_ctx* ctx, Lane& ln, const la_device_batch* b, hipStream_t stream, StagedBatch* staged = nullptr);
 
 // ---- la_host.hip: the host-buffer calls ------------------------------------------------------------------------------------
 struct Shape {
@@ -405,6 +406,7 @@ struct HostCall {
     bool use_begin = false;
     // la_assign_batch_sparse: `begin` arrives as (position, value) pairs for the partitions without a committed offset; the
     // dense array the kernels read is rebuilt on the device (zero + scatter), chunk by chunk
+    int memory = -1;                     // how the call's arrays can be reached (call_memory: probed on first use, -1 before)
     bool mapped = false;                 // every array of the call is pinned AND device-mapped: the kernels read / write it in place
     bool sparse = false;                 // (set by the sparse entry points; assign_host clears it where the list is ignored)
     int64_t n_none = 0;

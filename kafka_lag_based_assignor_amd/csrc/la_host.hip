@@ -1,23 +1,18 @@
-// la_host.hip -- everything that exists to serve the host-buffer calls of include/lagassign.h: the planner, the three chunked
-// pipelines, the staged small-call forms, assign_host and the grouping of the results it leaves on the device.
+// la_host.hip -- everything that exists to serve the host-buffer calls of include/lagassign.h: the one builder of their device
+// batches (device_batch), the three chunked pipelines (run_lane, run_shard_async, run_shard_mapped), the staged small-call forms
+// (assign_small_zc, assign_small), the planner, assign_host and the grouping of the results it leaves on the device.
 #include "la_ctx.h"
 
 namespace {
 
-// Validates offsets (and, if given, the ascending-rank contract) on the host.
-int scan_shape(la_ctx* ctx, int32_t T, const int64_t* part_off, const int64_t* cons_off,
-               const int32_t* cons_rank, Shape* s) {
+// Validates the offsets on the host and measures the call.
+int scan_shape(la_ctx* ctx, int32_t T, const int64_t* part_off, const int64_t* cons_off, Shape* s) {
     if (part_off[0] != 0 || cons_off[0] != 0) return fail(ctx, LA_EINVAL, "part_off[0] and cons_off[0] must be 0");
     for (int32_t t = 0; t < T; ++t) {
         const int64_t p = part_off[t + 1] - part_off[t], c = cons_off[t + 1] - cons_off[t];
         if (p < 0 || c < 0) return fail(ctx, LA_EINVAL, "offsets of topic %d decrease", t);
         if (p > s->max_p) s->max_p = p;
         if (c > s->max_c) s->max_c = c;
-        if (cons_rank)
-            for (int64_t k = cons_off[t] + 1; k < cons_off[t + 1]; ++k)
-                if (cons_rank[k - 1] >= cons_rank[k])
-                    return fail(ctx, LA_EINVAL,
-                                "cons_rank of topic %d is not strictly ascending at %lld", t, (long long)k);
     }
     s->n = part_off[T];
     s->k = cons_off[T];
@@ -28,21 +23,34 @@ constexpr int64_t kMinChunkPartitions = 1 << 19;   // a chunk's copies must be l
 constexpr int64_t kMidChunkPartitions = 100000;    // pageable arrays: from two such chunks on, a mid-size shard runs on two lanes
 constexpr int kMaxChunks = 64;
 
-// What the device batch of every pipeline shares; each pipeline then sets only what is its own: sizes and arrays.  The caller's
-// hints ride along: bounds that hold for the whole call hold for every chunk and shard of it.
-la_device_batch host_batch(const HostCall& c) {
-    la_device_batch b{};
-    b.reset_mode = c.reset_mode == LA_RESET_LATEST ? LA_RESET_LATEST : LA_RESET_EARLIEST;
-    b.algo = LA_ALGO_AUTO;
-    b.max_partitions_per_topic = c.shape.max_p;
-    b.max_consumers_per_topic = c.shape.max_c;
-    b.flags = LA_FLAG_RAGGED;        // the offsets are on the host anyway: let the dispatcher look at the shapes
+// THE device batch of a host-buffer call: every pipeline and staged form builds its batches here.  `w` says where the arrays of
+// the call -- or of the shard or chunk of it that the batch covers -- lie on the device, whatever brought them there (a pipeline's
+// copies, a staging buffer, the caller's own mapped memory), and the sizes and host offsets that go with them.  It fills in
+// every slot whether the call uses it or not (d_end_off: the lags, for la_assign_batch_lags); the rules are applied here, once:
+// `begin` only where the call reads it, the lags in the slot of the end offsets, totals only where the caller wants them.  The
+// caller's hints ride along: bounds that hold for the whole call hold for every chunk and shard of it.
+la_device_batch device_batch(const HostCall& c, la_device_batch w) {
+    w.reset_mode = c.reset_mode == LA_RESET_LATEST ? LA_RESET_LATEST : LA_RESET_EARLIEST;
+    w.algo = LA_ALGO_AUTO;
+    w.max_partitions_per_topic = c.shape.max_p;
+    w.max_consumers_per_topic = c.shape.max_c;
+    w.flags = LA_FLAG_RAGGED;        // the offsets are on the host anyway: let the dispatcher look at the shapes
     if (c.bounded) {
-        b.flags |= LA_FLAG_BOUNDS;
-        b.max_lag_hint = c.max_lag;
-        b.max_partition_id_hint = c.max_id;
+        w.flags |= LA_FLAG_BOUNDS;
+        w.max_lag_hint = c.max_lag;
+        w.max_partition_id_hint = c.max_id;
     }
-    return b;
+    if (!c.use_begin) w.d_begin_off = nullptr;
+    w.d_lag = c.lag ? w.d_end_off : nullptr;
+    if (!c.out_total) w.d_out_total_lag = nullptr;
+    return w;
+}
+
+// A batch with nothing to assign is not launched; its consumers -- the nk entries from k_first on -- still report a total of 0.
+int assign_or_zero(la_ctx* ctx, Lane& ln, const la_device_batch& b, size_t np, int64_t k_first, size_t nk, hipStream_t st) {
+    if (np) return enqueue_batch(ctx, ln, &b, st);
+    if (b.d_out_total_lag && nk) LA_HIP(ctx, hipMemsetAsync(b.d_out_total_lag + k_first, 0, nk * 8, st));
+    return LA_OK;
 }
 
 struct ShardPlan {
@@ -143,28 +151,6 @@ int prepare_shard(la_ctx* ctx, const HostCall& c, Shard& sh, ShardPlan& sp) {
     return LA_OK;
 }
 
-// Sparse begin offsets of chunk ci: `copy` (non-null) uploads the chunk's slice of the (position, begin) list, `kern`
-// (non-null) zeroes the chunk's part of the dense array and scatters the slice into it.  One stream may play both roles.
-int sparse_begin_chunk(la_ctx* ctx, const HostCall& c, Shard& sh, const ShardPlan& sp, int ci, Lane& ln, hipStream_t copy,
-                       hipStream_t kern) {
-    const int64_t j0 = sp.none_at[(size_t)ci], j1 = sp.none_at[(size_t)ci + 1], at = j0 - sp.none_at[0];
-    const size_t m = (size_t)(j1 - j0);
-    const int32_t a = sp.chunk[(size_t)ci], z = sp.chunk[(size_t)ci + 1];
-    const int64_t p0 = sp.lpo[a], p1 = sp.lpo[z];
-    int64_t* d_idx = (int64_t*)sh.none_idx.p + at;
-    int64_t* d_val = (int64_t*)sh.none_val.p + at;
-    if (copy && m) {
-        LA_HIP(ctx, hipMemcpyAsync(d_idx, c.none_index + j0, m * 8, hipMemcpyHostToDevice, copy));
-        LA_HIP(ctx, hipMemcpyAsync(d_val, c.none_begin + j0, m * 8, hipMemcpyHostToDevice, copy));
-    }
-    if (kern) {
-        if (p1 > p0) LA_HIP(ctx, hipMemsetAsync((int64_t*)sh.begin.p + p0, 0, (size_t)(p1 - p0) * 8, kern));
-        LA_HIP(ctx, la::sparse_begin_launch((int64_t)m, d_idx, d_val, sp.P0, sp.P0 + p0, sp.P0 + p1, (int64_t*)sh.begin.p,
-                                            ln.d_status, kern));
-    }
-    return LA_OK;
-}
-
 // Chunk ci of a shard: its topics [a, z) in the shard's numbering, its partitions [p0, p1) and consumer entries [k0, k1) in the
 // shard's buffers, where they start in the caller's arrays (gp, gk), and how many there are (np, nk).
 struct Chunk {
@@ -180,6 +166,26 @@ Chunk chunk_of(const ShardPlan& sp, int ci) {
     ck.gp = sp.P0 + ck.p0; ck.gk = sp.K0 + ck.k0;              // the chunk in the caller's arrays
     ck.np = (size_t)(ck.p1 - ck.p0); ck.nk = (size_t)(ck.k1 - ck.k0);
     return ck;
+}
+
+// Sparse begin offsets of chunk ci: `copy` (non-null) uploads the chunk's slice of the (position, begin) list, `kern`
+// (non-null) zeroes the chunk's part of the dense array and scatters the slice into it.  One stream may play both roles.
+int sparse_begin_chunk(la_ctx* ctx, const HostCall& c, Shard& sh, const ShardPlan& sp, int ci, const Chunk& ck, Lane& ln,
+                       hipStream_t copy, hipStream_t kern) {
+    const int64_t j0 = sp.none_at[(size_t)ci], j1 = sp.none_at[(size_t)ci + 1], at = j0 - sp.none_at[0], p0 = ck.p0, p1 = ck.p1;
+    const size_t m = (size_t)(j1 - j0);
+    int64_t* d_idx = (int64_t*)sh.none_idx.p + at;
+    int64_t* d_val = (int64_t*)sh.none_val.p + at;
+    if (copy && m) {
+        LA_HIP(ctx, hipMemcpyAsync(d_idx, c.none_index + j0, m * 8, hipMemcpyHostToDevice, copy));
+        LA_HIP(ctx, hipMemcpyAsync(d_val, c.none_begin + j0, m * 8, hipMemcpyHostToDevice, copy));
+    }
+    if (kern) {
+        if (p1 > p0) LA_HIP(ctx, hipMemsetAsync((int64_t*)sh.begin.p + p0, 0, (size_t)(p1 - p0) * 8, kern));
+        LA_HIP(ctx, la::sparse_begin_launch((int64_t)m, d_idx, d_val, sp.P0, sp.P0 + p0, sp.P0 + p1, (int64_t*)sh.begin.p,
+                                            ln.d_status, kern));
+    }
+    return LA_OK;
 }
 
 // H2D of a chunk's per-partition slices (a sparse begin list and the consumer ranks travel their pipeline's own way).
@@ -212,29 +218,38 @@ int chunk_copy_out(la_ctx* ctx, const HostCall& c, Shard& sh, const Chunk& ck, h
     return LA_OK;
 }
 
-// The device batch of topics [a, z) of a shard whose arrays were copied to its buffers.
+// What chunk ci of a shard does on the device between the copies of its per-partition slices in and of its results out, on
+// lane ln: the sparse-begin scatter, the check of its consumers, and its batch -- all on stream `kern`.  `copy` is the stream
+// that brings the chunk's own sparse list and consumer ranks up first, or null where the pipeline has already sent the shard's.
 // The chunk is a topic sub-range of the shard's batch: same arrays, offsets advanced to its first topic.
 // n_partitions / n_consumers stay the shard's totals -- they bound the kernels' clamped loads, which may
 // touch (and ignore) elements of neighbouring chunks.
-la_device_batch chunk_batch(const HostCall& c, const Shard& sh, const ShardPlan& sp, int32_t a, int32_t z) {
-    la_device_batch b = host_batch(c);
-    b.n_topics = z - a;
-    b.n_partitions = sp.n;
-    b.n_consumers = sp.k;
-    b.d_part_off = (const int64_t*)sh.part_off.p + a;
-    b.d_partition_id = (const int32_t*)sh.pid.p;
-    b.d_begin_off = c.use_begin ? (const int64_t*)sh.begin.p : nullptr;
-    b.d_end_off = (const int64_t*)sh.end.p;
-    b.d_committed_off = (const int64_t*)sh.committed.p;
-    b.d_lag = c.lag ? (const int64_t*)sh.end.p : nullptr;
-    b.d_cons_off = (const int64_t*)sh.cons_off.p + a;
-    b.d_cons_rank = (const int32_t*)sh.cons_rank.p;
-    b.d_out_partition = (int32_t*)sh.out_pid.p;
-    b.d_out_member_rank = (int32_t*)sh.out_rank.p;
-    b.d_out_total_lag = c.out_total ? (int64_t*)sh.out_total.p : nullptr;
-    b.h_part_off = sp.lpo + a;
-    b.h_cons_off = sp.lco + a;
-    return b;
+int chunk_device_work(la_ctx* ctx, const HostCall& c, Shard& sh, const ShardPlan& sp, int ci, const Chunk& ck, Lane& ln,
+                      hipStream_t copy, hipStream_t kern) {
+    // (list entries where there are no partitions: the kernel reports them)
+    if (c.sparse && (ck.np || sp.none_at[(size_t)ci + 1] > sp.none_at[(size_t)ci]))
+        if (int rc = sparse_begin_chunk(ctx, c, sh, sp, ci, ck, ln, copy, kern)) return rc;
+    if (ck.nk) {
+        if (copy)
+            LA_HIP(ctx, hipMemcpyAsync((int32_t*)sh.cons_rank.p + ck.k0, c.cons_rank + ck.gk, ck.nk * 4, hipMemcpyHostToDevice, copy));
+        // the ascending-rank contract of cons_rank is checked on the device (one pass over K entries there
+        // instead of ~1 ns per entry of host time), reported by sync_status as LA_EINVAL
+        LA_HIP(ctx, la::check_consumers_launch(ck.z - ck.a, (const int64_t*)sh.cons_off.p + ck.a,
+                                               (const int32_t*)sh.cons_rank.p, ln.d_status, kern));
+    }
+    la_device_batch w{};
+    w.n_topics = ck.z - ck.a; w.n_partitions = sp.n; w.n_consumers = sp.k;
+    w.d_part_off = (const int64_t*)sh.part_off.p + ck.a;
+    w.d_cons_off = (const int64_t*)sh.cons_off.p + ck.a;
+    w.d_partition_id = (const int32_t*)sh.pid.p;
+    w.d_begin_off = (const int64_t*)sh.begin.p;
+    w.d_end_off = (const int64_t*)sh.end.p;
+    w.d_committed_off = (const int64_t*)sh.committed.p;
+    w.d_cons_rank = (const int32_t*)sh.cons_rank.p;
+    w.d_out_partition = (int32_t*)sh.out_pid.p; w.d_out_member_rank = (int32_t*)sh.out_rank.p;
+    w.d_out_total_lag = (int64_t*)sh.out_total.p;
+    w.h_part_off = sp.lpo + ck.a; w.h_cons_off = sp.lco + ck.a;
+    return assign_or_zero(ctx, ln, device_batch(c, w), ck.np, ck.k0, ck.nk, kern);
 }
 
 // One lane of one shard: takes the shard's chunks in order until none is left.  Per chunk: H2D of its slices,
@@ -246,38 +261,14 @@ int run_lane(la_ctx* ctx, const HostCall& c, Shard& sh, ShardPlan& sp, int lane_
     hipStream_t st = ln.stream;
     if (lane_idx > 0) LA_HIP(ctx, hipStreamWaitEvent(st, sh.ready, 0));
     const int n_chunks = (int)sp.chunk.size() - 1;
-    auto run_chunk = [&](int ci) -> int {
-        const Chunk ck = chunk_of(sp, ci);
-        const int32_t a = ck.a, z = ck.z;
-        const int64_t k0 = ck.k0, gk = ck.gk;
-        const size_t np = ck.np, nk = ck.nk;
-        if (int rc = chunk_copy_in(ctx, c, sh, ck, st)) return rc;
-        if (c.sparse && np)
-            if (int rc = sparse_begin_chunk(ctx, c, sh, sp, ci, ln, st, st)) return rc;
-        if (c.sparse && !np && sp.none_at[(size_t)ci + 1] > sp.none_at[(size_t)ci])      // entries where there are no partitions:
-            if (int rc = sparse_begin_chunk(ctx, c, sh, sp, ci, ln, st, st)) return rc;       // the kernel reports them
-        if (nk) {
-            LA_HIP(ctx, hipMemcpyAsync((int32_t*)sh.cons_rank.p + k0, c.cons_rank + gk, nk * 4, hipMemcpyHostToDevice, st));
-            // the ascending-rank contract of cons_rank is checked on the device (one pass over K entries there
-            // instead of ~1 ns per entry of host time), reported by sync_status as LA_EINVAL
-            LA_HIP(ctx, la::check_consumers_launch(z - a, (const int64_t*)sh.cons_off.p + a,
-                                                   (const int32_t*)sh.cons_rank.p, ln.d_status, st));
-        }
-        const la_device_batch b = chunk_batch(c, sh, sp, a, z);
-        if (np == 0) {
-            // nothing to assign in this chunk; its consumers still report a total of 0
-            if (c.out_total && nk)
-                LA_HIP(ctx, hipMemsetAsync((int64_t*)sh.out_total.p + k0, 0, nk * 8, st));
-        } else if (int rc = enqueue_batch(ctx, ln, &b, st)) {
-            return rc;
-        }
-        return chunk_copy_out(ctx, c, sh, ck, st);
-    };
     int rc = LA_OK;
     while (!stop.load(std::memory_order_relaxed)) {
         const int ci = sp.next.fetch_add(1);
         if (ci >= n_chunks) break;
-        if ((rc = run_chunk(ci))) break;
+        const Chunk ck = chunk_of(sp, ci);
+        if ((rc = chunk_copy_in(ctx, c, sh, ck, st)) || (rc = chunk_device_work(ctx, c, sh, sp, ci, ck, ln, st, st)) ||
+            (rc = chunk_copy_out(ctx, c, sh, ck, st)))
+            break;
     }
     const int rs = sync_status(ctx, ln, st);     // also when stopping early: nothing of this lane stays in flight
     return rc ? rc : rs;
@@ -302,15 +293,6 @@ bool is_pinned(const void* p, size_t bytes) {
     if ((at.devicePointer == nullptr) != (az.devicePointer == nullptr)) return false;
     if (at.devicePointer && (const char*)az.devicePointer - (const char*)at.devicePointer != span) return false;
     return true;
-}
-
-bool call_is_pinned(const HostCall& c) {
-    const size_t n = (size_t)c.shape.n, k = (size_t)c.shape.k;
-    return is_pinned(c.pid, n * 4) && is_pinned(c.end, n * 8) && is_pinned(c.committed, n * 8) && is_pinned(c.lag, n * 8) &&
-           (!c.use_begin || c.sparse || is_pinned(c.begin, n * 8)) &&
-           (!c.sparse || (is_pinned(c.none_index, (size_t)c.n_none * 8) && is_pinned(c.none_begin, (size_t)c.n_none * 8))) &&
-           is_pinned(c.cons_rank, k * 4) && is_pinned(c.out_pid, n * 4) &&
-           is_pinned(c.out_rank, n * 4) && is_pinned(c.out_total, k * 8);
 }
 
 // One shard of a call whose arrays are all pinned: no worker threads.  The calling thread enqueues, per chunk,
@@ -349,31 +331,16 @@ int run_shard_async(la_ctx* ctx, const HostCall& c, Shard& sh, ShardPlan& sp) {
     }
     for (int ci = 0; ci < n_chunks; ++ci) {
         const Chunk ck = chunk_of(sp, ci);
-        const int32_t a = ck.a, z = ck.z;
-        const int64_t k0 = ck.k0;
-        const size_t np = ck.np, nk = ck.nk;
         hipEvent_t ev_in = sh.chunk_ev[(size_t)(2 * ci)], ev_out = sh.chunk_ev[(size_t)(2 * ci + 1)];
         hipStream_t si = sh.copy_in[ci % Shard::kCopyIn];
-        if (np) {
+        if (ck.np) {
             if (int rc = chunk_copy_in(ctx, c, sh, ck, si)) return rc;
             LA_HIP(ctx, hipEventRecord(ev_in, si));
             LA_HIP(ctx, hipStreamWaitEvent(sk, ev_in, 0));
-            if (c.sparse)
-                if (int rc = sparse_begin_chunk(ctx, c, sh, sp, ci, ln, nullptr, sk)) return rc;
         }
-        if (c.sparse && !np && sp.none_at[(size_t)ci + 1] > sp.none_at[(size_t)ci])      // entries where there are no partitions:
-            if (int rc = sparse_begin_chunk(ctx, c, sh, sp, ci, ln, nullptr, sk)) return rc;  // the kernel reports them
-        if (nk)
-            LA_HIP(ctx, la::check_consumers_launch(z - a, (const int64_t*)sh.cons_off.p + a, (const int32_t*)sh.cons_rank.p,
-                                                   ln.d_status, sk));
-        const la_device_batch b = chunk_batch(c, sh, sp, a, z);
-        if (np == 0) {
-            if (c.out_total && nk) LA_HIP(ctx, hipMemsetAsync((int64_t*)sh.out_total.p + k0, 0, nk * 8, sk));
-        } else if (int rc = enqueue_batch(ctx, ln, &b, sk)) {
-            return rc;
-        }
+        if (int rc = chunk_device_work(ctx, c, sh, sp, ci, ck, ln, nullptr, sk)) return rc;
         LA_HIP(ctx, hipEventRecord(ev_out, sk));
-        const bool any_out = (np && c.out_pid) || (c.out_total && nk);
+        const bool any_out = (ck.np && c.out_pid) || (c.out_total && ck.nk);
         if (any_out) LA_HIP(ctx, hipStreamWaitEvent(so, ev_out, 0));
         if (int rc = chunk_copy_out(ctx, c, sh, ck, so)) return rc;
     }
@@ -396,33 +363,49 @@ T* mapped_ptr(T* host) {
     return (T*)d;
 }
 
-bool call_is_mapped(const HostCall& c) {
-    // first AND last byte of every array: an array registered only in part (hipHostRegister of a sub-range), or one
-    // that runs past its registration, must not be handed to kernels that read and write it in place -- its device view has to
-    // exist at both ends and advance with the host view in between; anything else takes a copying pipeline.
-    auto ok = [](const void* p, size_t bytes) {
-        if (p == nullptr || bytes == 0) return true;
-        const char* d0 = mapped_ptr((const char*)p);
-        const char* d1 = mapped_ptr((const char*)p + (bytes - 1));
-        return d0 != nullptr && d1 != nullptr && (size_t)(d1 - d0) == bytes - 1;
-    };
-    const size_t n = (size_t)c.shape.n, k = (size_t)c.shape.k, tb = ((size_t)c.T + 1) * 8, m = (size_t)c.n_none * 8;
-    return ok(c.part_off, tb) && ok(c.cons_off, tb) && ok(c.pid, n * 4) && ok(c.end, n * 8) && ok(c.committed, n * 8) &&
-           ok(c.lag, n * 8) && ok(c.begin, n * 8) && ok(c.none_index, m) && ok(c.none_begin, m) && ok(c.cons_rank, k * 4) &&
-           ok(c.out_pid, n * 4) && ok(c.out_rank, n * 4) && ok(c.out_total, k * 8);
+// first AND last byte: an array registered only in part (hipHostRegister of a sub-range), or one that runs past
+// its registration, must not be handed to kernels that read and write it in place -- its device view has to exist at both
+// ends and advance with the host view in between; anything else takes a copying pipeline.  NULL / zero bytes count as mapped.
+bool is_mapped(const void* p, size_t bytes) {
+    if (p == nullptr || bytes == 0) return true;
+    const char* d0 = mapped_ptr((const char*)p);
+    const char* d1 = mapped_ptr((const char*)p + (bytes - 1));
+    return d0 != nullptr && d1 != nullptr && (size_t)(d1 - d0) == bytes - 1;
 }
+
+// ok(pointer, bytes) over the arrays of a (normalised) call: all of them, or with `copied_only` those a copying pipeline moves
+// between the caller and the device -- not the offsets, which go up from the shard plan's own copy, and not a `begin` the call
+// never reads.  (A sparse call has no dense `begin` and every other call no list: assign_host has nulled them.)
+bool call_arrays_all(const HostCall& c, bool copied_only, bool (*ok)(const void*, size_t)) {
+    const size_t n = (size_t)c.shape.n, k = (size_t)c.shape.k, tb = ((size_t)c.T + 1) * 8, m = (size_t)c.n_none * 8;
+    const struct { const void* p; size_t bytes; bool copied; } arrays[] = {
+        {c.part_off, tb, false}, {c.cons_off, tb, false}, {c.pid, n * 4, true}, {c.end, n * 8, true}, {c.committed, n * 8, true},
+        {c.lag, n * 8, true}, {c.begin, n * 8, c.use_begin}, {c.none_index, m, true}, {c.none_begin, m, true},
+        {c.cons_rank, k * 4, true}, {c.out_pid, n * 4, true}, {c.out_rank, n * 4, true}, {c.out_total, k * 8, true}};
+    for (const auto& x : arrays)
+        if ((x.copied || !copied_only) && !ok(x.p, x.bytes)) return false;
+    return true;
+}
+
+// every array that is copied is pinned: the call can take the thread-less three-stream pipeline
+bool call_is_pinned(const HostCall& c) { return call_arrays_all(c, true, is_pinned); }
+// every array is mapped, copied or not: the kernels would address all of them
+bool call_is_mapped(const HostCall& c) { return call_arrays_all(c, false, is_mapped); }
 
 int run_shard_mapped(la_ctx* ctx, const HostCall& c, Shard& sh, ShardPlan& sp) {
     LA_HIP(ctx, hipSetDevice(sh.device));
     Lane& ln = sh.lanes[0];
     hipStream_t st = ln.stream;
-    const int32_t Ts = sp.t1 - sp.t0;
-    const int64_t* m_part_off = mapped_ptr(c.part_off);
-    const int64_t* m_cons_off = mapped_ptr(c.cons_off);
-    const int32_t* m_cons_rank = mapped_ptr(c.cons_rank);
+    la_device_batch w{};
+    w.n_topics = sp.t1 - sp.t0;
+    w.n_partitions = c.shape.n;                                                  // (positions are the caller's: the bound is too)
+    w.n_consumers = c.shape.k;
+    w.d_part_off = mapped_ptr(c.part_off) + sp.t0;
+    w.d_cons_off = mapped_ptr(c.cons_off) + sp.t0;
+    w.d_cons_rank = mapped_ptr(c.cons_rank);
     if (sp.k)
-        LA_HIP(ctx, la::check_consumers_launch(Ts, m_cons_off + sp.t0, m_cons_rank, ln.d_status, st));
-    const int64_t* d_begin = c.use_begin ? mapped_ptr(c.begin) : nullptr;
+        LA_HIP(ctx, la::check_consumers_launch(w.n_topics, w.d_cons_off, w.d_cons_rank, ln.d_status, st));
+    w.d_begin_off = mapped_ptr(c.begin);
     if (c.sparse) {
         int64_t* db = (int64_t*)sh.begin.p;
         const int64_t j0 = sp.none_at.front(), j1 = sp.none_at.back();
@@ -430,35 +413,21 @@ int run_shard_mapped(la_ctx* ctx, const HostCall& c, Shard& sh, ShardPlan& sp) {
         if (sp.n) LA_HIP(ctx, hipMemsetAsync(db + sp.P0, 0, (size_t)sp.n * 8, st));
         LA_HIP(ctx, la::sparse_begin_launch(j1 - j0, mapped_ptr(c.none_index) + j0, mapped_ptr(c.none_begin) + j0, 0, sp.P0,
                                             sp.P0 + sp.n, db, ln.d_status, st));
-        d_begin = db;
+        w.d_begin_off = db;
     }
-    la_device_batch b = host_batch(c);
-    b.n_topics = Ts;
-    b.n_partitions = c.shape.n;                                                  // (positions are the caller's: the bound is too)
-    b.n_consumers = c.shape.k;
-    b.d_part_off = m_part_off + sp.t0;
-    b.d_partition_id = mapped_ptr(c.pid);
-    b.d_begin_off = d_begin;
-    b.d_end_off = mapped_ptr(c.lag ? c.lag : c.end);
-    b.d_committed_off = mapped_ptr(c.committed);
-    b.d_lag = c.lag ? mapped_ptr(c.lag) : nullptr;
-    b.d_cons_off = m_cons_off + sp.t0;
-    b.d_cons_rank = m_cons_rank;
+    w.d_partition_id = mapped_ptr(c.pid);
+    w.d_end_off = mapped_ptr(c.lag ? c.lag : c.end);
+    w.d_committed_off = mapped_ptr(c.committed);
     // results the caller asked for land in its arrays; those it leaves on the device go to the shard's own buffers, addressed
     // by the caller's positions (only positions of this shard's topics are ever stored)
     // (the shard's own buffers hold positions [P0, P0 + n) only; their "position 0" is an address computed in integers, never
     //  dereferenced below P0)
     auto rebased = [&](void* base) { return (int32_t*)((uintptr_t)base - (uintptr_t)sp.P0 * sizeof(int32_t)); };
-    b.d_out_partition = c.out_pid ? mapped_ptr(c.out_pid) : rebased(sh.out_pid.p);
-    b.d_out_member_rank = c.out_pid ? mapped_ptr(c.out_rank) : rebased(sh.out_rank.p);
-    b.d_out_total_lag = c.out_total ? mapped_ptr(c.out_total) : nullptr;
-    b.h_part_off = c.part_off + sp.t0;
-    b.h_cons_off = c.cons_off + sp.t0;
-    if (sp.n == 0) {
-        if (c.out_total && sp.k) LA_HIP(ctx, hipMemsetAsync(mapped_ptr(c.out_total) + sp.K0, 0, (size_t)sp.k * 8, st));
-        return LA_OK;
-    }
-    return enqueue_batch(ctx, ln, &b, st);
+    w.d_out_partition = c.out_pid ? mapped_ptr(c.out_pid) : rebased(sh.out_pid.p);
+    w.d_out_member_rank = c.out_pid ? mapped_ptr(c.out_rank) : rebased(sh.out_rank.p);
+    w.d_out_total_lag = mapped_ptr(c.out_total);
+    w.h_part_off = c.part_off + sp.t0; w.h_cons_off = c.cons_off + sp.t0;
+    return assign_or_zero(ctx, ln, device_batch(c, w), (size_t)sp.n, sp.K0, (size_t)sp.k, st);
 }
 
 // Waits for everything run_shard_async enqueued on this shard (also after an error elsewhere: nothing stays in flight).
@@ -487,11 +456,22 @@ constexpr size_t kMappedSmallGroupedBytes = 3u << 20;      // ... and beyond thi
 constexpr size_t kPinnedSmallBytes = 2u << 20;             // pinned, not mapped: beyond this the three-stream pipeline
 constexpr size_t kSmallHostCheck = 16384;      // consumer entries up to which the small path validates the ranks on the host
 
+// One output of a staged call: where the caller wants it (null: it does not), and where it lies in the staging layout.
+struct StagedOut { void* to; size_t off, bytes; };
+// In the order of the layout.  The member lists are those of a grouped call, or of the ADJUSTED assignment of a cooperative one,
+// whose eight outputs follow them; the ungrouped results come last, so that a download can stop short of them.
+enum { kOutTotals, kOutMemberOff, kOutListTopic, kOutListPartition, kOutKept, kOutFresh, kOutPending, kOutRelease, kOutWithheld,
+       kOutSummary, kOutPrevOwner, kOutCoopRank, kOutPid, kOutRank, kStagedOuts };
+
 struct SmallLayout {
-    size_t po, co, pid, end, com, beg, cr, status, ot, goff, gt, gp, op, orank, total;
+    size_t po, co, pid, end, com, beg, cr, status, total;
     // la_assign_batch_cooperative, fused form (carved for such a call only: every other call's layout is what it was): the owned
-    // arrays on the upload side of the status word, the round's counting outputs and per-entry outputs on the download side
-    size_t oo, otp, opp, cnt[4], held, sum, prev, coop;
+    // arrays on the upload side of the status word
+    size_t oo, otp, opp;
+    StagedOut out[kStagedOuts];                               // the download side of the status word
+    // output `slot` in the copy of the layout at `base`: at() wherever it lies, want() only where the caller wants it
+    template <typename T> T* at(const char* base, int slot) const { return (T*)(base + out[slot].off); }
+    template <typename T> T* want(const char* base, int slot) const { return out[slot].to ? at<T>(base, slot) : nullptr; }
 };
 
 SmallLayout small_layout(const HostCall& c) {
@@ -499,6 +479,8 @@ SmallLayout small_layout(const HostCall& c) {
     size_t off = 0;
     auto carve = [&](size_t bytes) { const size_t o = off; off = (off + bytes + 16 + 255) & ~(size_t)255; return o; };
     SmallLayout L{};
+    // (`room`: the slot holds its bytes even where the caller does not want them -- the kernels write there all the same)
+    auto out = [&](int slot, void* to, size_t bytes, bool room = false) { L.out[slot] = {to, carve(to || room ? bytes : 0), bytes}; };
     L.po = carve((T + 1) * 8);
     L.co = carve((T + 1) * 8);
     L.pid = carve(n * 4);
@@ -514,26 +496,29 @@ SmallLayout small_layout(const HostCall& c) {
         L.opp = carve(no * 4);
     }
     L.status = carve(256);                                    // last word of the upload, first of the download
-    L.ot = carve(k * 8);
+    out(kOutTotals, c.out_total, k * 8, true);
     const bool grouped = c.g_members >= 0;                    // la_assign_batch_grouped: the CSR rides in the same download
     if (q) {                                                  // the lists of the ADJUSTED assignment take the CSR's place
         const size_t M = (size_t)q->c.n_members;
-        L.goff = carve((M + 1) * 8);
-        L.gt = carve(q->grouped_topic ? n * 4 : 0);
-        L.gp = carve(n * 4);
-        int64_t* const want[4] = {q->c.member_kept, q->c.member_fresh, q->c.member_pending, q->c.member_release};
-        for (int w = 0; w < 4; ++w) L.cnt[w] = carve(want[w] ? M * 8 : 0);
-        L.held = carve(q->c.topic_withheld ? T * 8 : 0);
-        L.sum = carve(q->c.summary ? 6 * 8 : 0);
-        L.prev = carve(q->c.prev_owner ? n * 4 : 0);
-        L.coop = carve(q->c.coop_rank ? n * 4 : 0);
+        out(kOutMemberOff, q->member_off, (M + 1) * 8, true);
+        out(kOutListTopic, q->grouped_topic, n * 4);
+        out(kOutListPartition, q->grouped_partition, n * 4, true);
+        out(kOutKept, q->c.member_kept, M * 8);
+        out(kOutFresh, q->c.member_fresh, M * 8);
+        out(kOutPending, q->c.member_pending, M * 8);
+        out(kOutRelease, q->c.member_release, M * 8);
+        out(kOutWithheld, q->c.topic_withheld, T * 8);
+        out(kOutSummary, q->c.summary, 6 * 8);
+        out(kOutPrevOwner, q->c.prev_owner, n * 4);
+        out(kOutCoopRank, q->c.coop_rank, n * 4);
     } else {
-        L.goff = carve(grouped ? ((size_t)c.g_members + 1) * 8 : 0);
-        L.gt = carve(grouped && c.g_topic ? n * 4 : 0);
-        L.gp = carve(grouped ? n * 4 : 0);
+        // (a call whose lists take their own round trip keeps g_off and its kin but has g_members < 0: not wanted HERE)
+        out(kOutMemberOff, grouped ? c.g_off : nullptr, ((size_t)c.g_members + 1) * 8);
+        out(kOutListTopic, grouped ? c.g_topic : nullptr, n * 4);
+        out(kOutListPartition, grouped ? c.g_part : nullptr, n * 4);
     }
-    L.op = carve(n * 4);
-    L.orank = carve(n * 4);
+    out(kOutPid, c.out_pid, n * 4, true);
+    out(kOutRank, c.out_rank, n * 4, true);
     L.total = off;
     return L;
 }
@@ -553,15 +538,6 @@ SmallLayout small_layout(const HostCall& c) {
 // (assign_small) is what LA_ZERO_COPY_BYTES=<smaller> still selects (A/B, tests).
 constexpr size_t kZeroCopyBytes = 12u << 20;
 
-int reserve_host_coherent(la_ctx* ctx, HostBuf& b, size_t bytes) {
-    if (bytes <= b.cap) return LA_OK;
-    if (b.p) { LA_HIP(ctx, hipHostFree(b.p)); b.p = nullptr; b.cap = 0; }
-    const size_t want = bytes + bytes / 4 + 256;
-    LA_HIP(ctx, hipHostMalloc(&b.p, want, hipHostMallocPortable | hipHostMallocMapped | hipHostMallocCoherent));
-    b.cap = want;
-    return LA_OK;
-}
-
 // The staged forms pack the caller's arrays into one buffer and unpack the results: plain memcpy.  From a few megabytes on that
 // is most of the call on ONE thread (~35 GB/s: 100 us for the inputs of 100 000 partitions), so the pieces are handed out to
 // the context's parked threads as well -- the calling thread starts on the first piece at once and simply does all of them
@@ -573,8 +549,7 @@ constexpr size_t kParallelCopyBytes = 3u << 20, kCopyPieceBytes = 256u << 10;
 void copy_pieces(la_ctx* ctx, const CopyPiece* cp, int n) {
     size_t total = 0;
     for (int i = 0; i < n; ++i) total += cp[i].bytes;
-    static const bool serial = getenv("LA_NO_PARALLEL_COPY") != nullptr;                // (A/B hook)
-    if (total < kParallelCopyBytes || serial) {
+    if (total < kParallelCopyBytes) {
         for (int i = 0; i < n; ++i)
             if (cp[i].bytes) memcpy(cp[i].dst, cp[i].src, cp[i].bytes);
         return;
@@ -639,49 +614,40 @@ int small_fill_inputs(la_ctx* ctx, const HostCall& c, const SmallLayout& L, char
     return LA_OK;
 }
 
-// The device batch of a staged call: inputs at in_base, results at out_base, the totals at totals_base (NULL: not wanted), all
-// three laid out by L.
-la_device_batch small_batch(const HostCall& c, const SmallLayout& L, char* in_base, char* out_base, char* totals_base) {
-    la_device_batch b = host_batch(c);
-    b.n_topics = c.T;
-    b.n_partitions = c.shape.n;
-    b.n_consumers = c.shape.k;
-    b.d_part_off = (const int64_t*)(in_base + L.po);
-    b.d_partition_id = (const int32_t*)(in_base + L.pid);
-    b.d_begin_off = c.use_begin ? (const int64_t*)(in_base + L.beg) : nullptr;
-    b.d_end_off = (const int64_t*)(in_base + L.end);
-    b.d_committed_off = (const int64_t*)(in_base + L.com);
-    b.d_lag = c.lag ? (const int64_t*)(in_base + L.end) : nullptr;
-    b.d_cons_off = (const int64_t*)(in_base + L.co);
-    b.d_cons_rank = (const int32_t*)(in_base + L.cr);
-    b.d_out_partition = (int32_t*)(out_base + L.op);
-    b.d_out_member_rank = (int32_t*)(out_base + L.orank);
-    b.d_out_total_lag = totals_base ? (int64_t*)(totals_base + L.ot) : nullptr;
-    b.h_part_off = c.part_off;
-    b.h_cons_off = c.cons_off;
-    return b;
+// The device batch of a staged call: inputs (and totals) at in_base, results at out_base, both laid out by L.
+la_device_batch small_batch(const HostCall& c, const SmallLayout& L, char* in_base, char* out_base) {
+    la_device_batch w{};
+    w.n_topics = c.T; w.n_partitions = c.shape.n; w.n_consumers = c.shape.k;
+    w.d_part_off = (const int64_t*)(in_base + L.po);
+    w.d_cons_off = (const int64_t*)(in_base + L.co);
+    w.d_partition_id = (const int32_t*)(in_base + L.pid);
+    w.d_begin_off = (const int64_t*)(in_base + L.beg);
+    w.d_end_off = (const int64_t*)(in_base + L.end);
+    w.d_committed_off = (const int64_t*)(in_base + L.com);
+    w.d_cons_rank = (const int32_t*)(in_base + L.cr);
+    w.d_out_partition = L.at<int32_t>(out_base, kOutPid); w.d_out_member_rank = L.at<int32_t>(out_base, kOutRank);
+    w.d_out_total_lag = L.at<int64_t>(in_base, kOutTotals);
+    w.h_part_off = c.part_off; w.h_cons_off = c.cons_off;
+    return device_batch(c, w);
 }
 
-// The end both staged forms share.  Every member's list of a grouped call, from the host side `h` of the staging buffer into
-// the caller's arrays (`pieces`: through copy_pieces), and what la_group_last_by_member would read: the offsets at po_base and
-// the results at res_base, both device addresses.
-void small_unpack(la_ctx* ctx, const HostCall& c, Shard& sh, const SmallLayout& L, const char* h, bool pieces,
+// The end both staged forms share, only ever after a status of zero.  Every output the caller wants, from the host side `h` of
+// the staging buffer into its arrays (`pieces`: through copy_pieces; `n_slots`: kOutPid where the ungrouped results do not come
+// from h); the lists of a grouped or cooperative call are then done; and what la_group_last_by_member would read: the offsets at
+// po_base and the results at res_base, both device addresses.
+void small_unpack(la_ctx* ctx, const HostCall& c, Shard& sh, const SmallLayout& L, const char* h, bool pieces, int n_slots,
                   const char* po_base, const char* res_base) {
-    const size_t n = (size_t)c.shape.n;
-    if (c.g_members >= 0) {
-        memcpy(c.g_off, h + L.goff, ((size_t)c.g_members + 1) * 8);
-        if (n && pieces) {
-            const CopyPiece out[2] = {{c.g_part, h + L.gp, n * 4}, {c.g_topic, h + L.gt, c.g_topic ? n * 4 : 0}};
-            copy_pieces(ctx, out, 2);
-        } else if (n) {
-            memcpy(c.g_part, h + L.gp, n * 4);
-            if (c.g_topic) memcpy(c.g_topic, h + L.gt, n * 4);
-        }
-        if (c.grouped_done) *c.grouped_done = true;
-    }
+    CopyPiece cp[kStagedOuts];
+    int n = 0;
+    for (int s = 0; s < n_slots; ++s)
+        if (L.out[s].to && L.out[s].bytes) cp[n++] = {L.out[s].to, h + L.out[s].off, L.out[s].bytes};
+    if (pieces) copy_pieces(ctx, cp, n);
+    else for (int i = 0; i < n; ++i) memcpy(cp[i].dst, cp[i].src, cp[i].bytes);
+    if (c.g_members >= 0 && c.grouped_done) *c.grouped_done = true;
+    if (c.coop) *c.coop_done = true;
     sh.last_part_off = (const int64_t*)(po_base + L.po);
-    sh.last_out_pid = (const int32_t*)(res_base + L.op);
-    sh.last_out_rank = (const int32_t*)(res_base + L.orank);
+    sh.last_out_pid = L.at<const int32_t>(res_base, kOutPid);
+    sh.last_out_rank = L.at<const int32_t>(res_base, kOutRank);
 }
 
 // One group_by_member launch over the results of a staged call: offsets at po_base, results in the device buffer d, the lists to
@@ -690,64 +656,131 @@ hipError_t small_group_launch(const HostCall& c, Lane& ln, const SmallLayout& L,
                               char* lists_base, uint32_t* status, hipStream_t st, uint32_t* fin_flag = nullptr,
                               bool* finished = nullptr) {
     return la::group_by_member_launch(ln.large, c.shape.n, c.g_members, c.T, (const int64_t*)(po_base + L.po),
-                                      (const int32_t*)(d + L.op), (const int32_t*)(d + L.orank), (int64_t*)(lists_base + L.goff),
-                                      c.g_topic ? (int32_t*)(lists_base + L.gt) : nullptr, (int32_t*)(lists_base + L.gp), nullptr,
-                                      status, st, fin_flag, finished);
+                                      L.at<const int32_t>(d, kOutPid), L.at<const int32_t>(d, kOutRank),
+                                      L.at<int64_t>(lists_base, kOutMemberOff), L.want<int32_t>(lists_base, kOutListTopic),
+                                      L.at<int32_t>(lists_base, kOutListPartition), nullptr, status, st, fin_flag, finished);
 }
 
 // la_assign_batch_cooperative, fused form: the round of a zero-copy call as its last launch.  The target at d (device memory),
 // the part offsets and the owned arrays at m (the device's view of the staging buffer), every output to m, the completion word
 // where the calling thread spins.
 hipError_t small_coop_launch(const HostCall& c, Lane& ln, const SmallLayout& L, char* m, const char* d, hipStream_t st) {
-    const la::CoopRoundCall& q = *c.coop;
-    la::CoopRoundCall r = q;
+    la::CoopRoundCall r = *c.coop;
     r.c.n_topics = c.T;
     r.c.n_partitions = c.shape.n;
     r.c.part_off = (const int64_t*)(m + L.po);
-    r.c.out_partition = (const int32_t*)(d + L.op);
-    r.c.out_member_rank = (const int32_t*)(d + L.orank);
-    const bool owned = q.c.n_owned > 0;
+    r.c.out_partition = L.at<const int32_t>(d, kOutPid);
+    r.c.out_member_rank = L.at<const int32_t>(d, kOutRank);
+    const bool owned = r.c.n_owned > 0;
     r.c.owned_off = owned ? (const int64_t*)(m + L.oo) : nullptr;
     r.c.owned_topic = owned ? (const int32_t*)(m + L.otp) : nullptr;
     r.c.owned_partition = owned ? (const int32_t*)(m + L.opp) : nullptr;
-    r.c.member_kept = q.c.member_kept ? (int64_t*)(m + L.cnt[0]) : nullptr;
-    r.c.member_fresh = q.c.member_fresh ? (int64_t*)(m + L.cnt[1]) : nullptr;
-    r.c.member_pending = q.c.member_pending ? (int64_t*)(m + L.cnt[2]) : nullptr;
-    r.c.member_release = q.c.member_release ? (int64_t*)(m + L.cnt[3]) : nullptr;
-    r.c.topic_withheld = q.c.topic_withheld ? (int64_t*)(m + L.held) : nullptr;
-    r.c.summary = q.c.summary ? (int64_t*)(m + L.sum) : nullptr;
-    r.c.prev_owner = q.c.prev_owner ? (int32_t*)(m + L.prev) : nullptr;
-    r.c.coop_rank = q.c.coop_rank ? (int32_t*)(m + L.coop) : nullptr;
-    r.member_off = (int64_t*)(m + L.goff);
-    r.grouped_topic = q.grouped_topic ? (int32_t*)(m + L.gt) : nullptr;
-    r.grouped_partition = (int32_t*)(m + L.gp);
-    return la::cooperative_round_finish_launch(r, c.out_pid ? (int32_t*)(m + L.op) : nullptr, c.out_pid ? (int32_t*)(m + L.orank) : nullptr,
-                                               ln.d_status, (uint32_t*)(m + L.status), st);
+    r.c.member_kept = L.want<int64_t>(m, kOutKept);
+    r.c.member_fresh = L.want<int64_t>(m, kOutFresh);
+    r.c.member_pending = L.want<int64_t>(m, kOutPending);
+    r.c.member_release = L.want<int64_t>(m, kOutRelease);
+    r.c.topic_withheld = L.want<int64_t>(m, kOutWithheld);
+    r.c.summary = L.want<int64_t>(m, kOutSummary);
+    r.c.prev_owner = L.want<int32_t>(m, kOutPrevOwner);
+    r.c.coop_rank = L.want<int32_t>(m, kOutCoopRank);
+    r.member_off = L.at<int64_t>(m, kOutMemberOff);
+    r.grouped_topic = L.want<int32_t>(m, kOutListTopic);
+    r.grouped_partition = L.at<int32_t>(m, kOutListPartition);
+    return la::cooperative_round_finish_launch(r, L.want<int32_t>(m, kOutPid), L.want<int32_t>(m, kOutRank), ln.d_status,
+                                               (uint32_t*)(m + L.status), st);
 }
 
-// ... and its outputs, from the host side of the staging buffer into the caller's arrays (only ever after a status of zero)
-void small_coop_unpack(const HostCall& c, const SmallLayout& L, const char* h) {
-    const la::CoopRoundCall& q = *c.coop;
-    const size_t n = (size_t)c.shape.n, M = (size_t)q.c.n_members, T = (size_t)c.T;
-    memcpy(q.member_off, h + L.goff, (M + 1) * 8);
-    memcpy(q.grouped_partition, h + L.gp, n * 4);
-    if (q.grouped_topic) memcpy(q.grouped_topic, h + L.gt, n * 4);
-    int64_t* const want[4] = {q.c.member_kept, q.c.member_fresh, q.c.member_pending, q.c.member_release};
-    for (int w = 0; w < 4; ++w)
-        if (want[w] && M) memcpy(want[w], h + L.cnt[w], M * 8);
-    if (q.c.topic_withheld && T) memcpy(q.c.topic_withheld, h + L.held, T * 8);
-    if (q.c.summary) memcpy(q.c.summary, h + L.sum, 6 * 8);
-    if (q.c.prev_owner) memcpy(q.c.prev_owner, h + L.prev, n * 4);
-    if (q.c.coop_rank) memcpy(q.c.coop_rank, h + L.coop, n * 4);
-    *c.coop_done = true;
+// The tail (lists + completion word) a zero-copy call asks the dispatcher to hang on its batch b's tile launch; false: none.
+// ONE launch for the whole rebalance where the batch is one resident tile launch: its last workgroup builds the lists and
+// stores the completion word -- otherwise the grouping / finishing launches of small_zc_enqueue.  Where that pays was measured at
+// the C ABI (profiles/r05_ae_fused_tail.txt): with lists, 100 / 500 partitions 22-24 / 25 us fused against 25 / 26.5 us with the
+// one-workgroup grouping as its own launch, but 2 000 partitions 37-38 against 34 -- the tail is 256 threads of the tile
+// kernel, the grouping kernel 1 024, and every workgroup of a fused launch pays a system-scope fence -- so the lists are fused
+// up to kTailMaxEntries entries; a call WITHOUT lists is faster with the plain finishing launch at every size (100
+// partitions 16.6 against 18.6 us, 10 000: 31 against 38) and never takes the tail.  LA_FUSED_TAIL=all restores round
+// 5's first form (every staged call that can), LA_NO_FUSED_TAIL=1 never fuses.
+bool small_tail_request(const HostCall& c, const SmallLayout& L, Lane& ln, const char* m, const la_device_batch& b, la::TileTail* t) {
+    static const bool no_tail = getenv("LA_NO_FUSED_TAIL") != nullptr;                 // (A/B hooks)
+    static const bool tail_all = [] { const char* e = getenv("LA_FUSED_TAIL"); return e && !strcmp(e, "all"); }();
+    const bool grouped = c.g_members >= 0;
+    const bool one_wg_lists = grouped ? (c.shape.n <= (tail_all ? la::kSmallGroupN : la::kTailMaxEntries) &&
+                                         (int64_t)c.g_members + 2 <= la::kTailGroupM)
+                                      : tail_all;
+    // (a cooperative call never: its round is its own 1 024-thread launch)
+    if (!one_wg_lists || no_tail || (size_t)c.shape.k > kSmallHostCheck || c.coop) return false;
+    *t = la::TileTail{};
+    t->enabled = 1;
+    t->n_members = grouped ? c.g_members : 0;
+    t->n = (int32_t)c.shape.n; t->n_topics = c.T;
+    t->part_off = (const int64_t*)(m + L.po);
+    t->out_pid = b.d_out_partition; t->out_rank = b.d_out_member_rank;
+    t->member_off = L.want<int64_t>(m, kOutMemberOff);
+    t->grouped_topic = L.want<int32_t>(m, kOutListTopic);
+    t->grouped_partition = L.want<int32_t>(m, kOutListPartition);
+    t->counter = ln.d_status + 24;
+    t->fin_flag = (uint32_t*)(m + L.status);
+    return true;
+}
+
+// Puts the lane's status word, and with `tail_counter` the counter of the tile kernel's tail, back to zero behind whatever is
+// on the stream: the next call must not inherit bits that kernels of a failed one OR-ed in, nor workgroups they counted done
+// (ADVICE r4).
+hipError_t lane_words_reset(Lane& ln, hipStream_t st, bool tail_counter) {
+    const hipError_t e = hipMemsetAsync(ln.d_status, 0, sizeof(uint32_t), st);
+    if (tail_counter) (void)hipMemsetAsync(ln.d_status + 24, 0, sizeof(uint32_t), st);
+    return e;
+}
+
+// The kernels of a zero-copy call: the batch, and the launch that ends the call by storing `done | status` into the completion
+// word -- the tile kernel's tail, the one-workgroup grouping, the cooperative round, or else a finishing launch of its own.
+int small_zc_enqueue(la_ctx* ctx, const HostCall& c, Lane& ln, const SmallLayout& L, char* m, char* d, char* res, hipStream_t st) {
+    uint32_t* const fin_flag = (uint32_t*)(m + L.status);
+    // the totals: only when the caller wants them (device_batch)
+    const la_device_batch b = small_batch(c, L, m, res);
+    la::TileTail tail;
+    StagedBatch staged;
+    if (small_tail_request(c, L, ln, m, b, &tail)) staged.tail = &tail;
+    if (int rc = enqueue_batch(ctx, ln, &b, st, &staged)) return rc;
+    bool finished = staged.tail_done;                                    // (the one-workgroup grouping also finishes the call)
+    if (c.g_members >= 0 && !finished)
+        if (const hipError_t e = small_group_launch(c, ln, L, m, d, m, ln.d_status, st, fin_flag, &finished); e != hipSuccess)
+            return hip_fail(ctx, e, "group_by_member: %s");
+    if (c.coop) {
+        if (const hipError_t e = small_coop_launch(c, ln, L, m, d, st); e != hipSuccess) return hip_fail(ctx, e, "cooperative_round: %s");
+        finished = true;
+    }
+    if (!finished)
+        if (const hipError_t e = la::finish_status_launch(ln.d_status, fin_flag, st); e != hipSuccess)
+            return fail(ctx, LA_EHIP, "finish launch: %s", hipGetErrorString(e));
+    return LA_OK;
+}
+
+// The wait of a zero-copy call: a spin on the completion word; should it never come (a fault on the stream), the runtime will
+// say why.  *status <- what the kernels flagged.
+int small_zc_wait(la_ctx* ctx, Lane& ln, volatile uint32_t* flag, hipStream_t st, uint32_t* status) {
+    uint32_t f = 0;
+    for (uint64_t spins = 0;; ++spins) {
+        f = *flag;
+        if (f & 0x80000000u) break;
+        if ((spins & 0xFFFu) == 0xFFFu) {
+            const hipError_t q = hipStreamQuery(st);
+            if (q == hipSuccess) { f = *flag; if (f & 0x80000000u) break; LA_HIP(ctx, hipStreamSynchronize(st)); f = *flag | 0x80000000u; break; }
+            if (q != hipErrorNotReady) {
+                (void)lane_words_reset(ln, st, true);                                // (best effort after a stream error)
+                return fail(ctx, LA_EHIP, "zero-copy call: %s", hipGetErrorString(q));
+            }
+        }
+    }
+    std::atomic_thread_fence(std::memory_order_acquire);
+    *status = f & 0x7FFFFFFFu;
+    return LA_OK;
 }
 
 int assign_small_zc(la_ctx* ctx, const HostCall& c, Shard& sh, const SmallLayout& L) {
     LA_HIP(ctx, hipSetDevice(sh.device));
     Lane& ln = sh.lanes[0];
     hipStream_t st = ln.stream;
-    const size_t n = (size_t)c.shape.n, k = (size_t)c.shape.k;
-    if (int rc = reserve_host_coherent(ctx, sh.zc_h, L.total)) return rc;
+    if (int rc = reserve_host(ctx, sh.zc_h, L.total, hipHostMallocPortable | hipHostMallocMapped | hipHostMallocCoherent)) return rc;
     if (int rc = reserve(ctx, sh.small_d, L.total)) return rc;           // the ungrouped result (same layout, device side)
     char* h = (char*)sh.zc_h.p;
     char* d = (char*)sh.small_d.p;
@@ -758,107 +791,39 @@ int assign_small_zc(la_ctx* ctx, const HostCall& c, Shard& sh, const SmallLayout
     volatile uint32_t* flag = (volatile uint32_t*)(h + L.status);
     *flag = 0;
     std::atomic_thread_fence(std::memory_order_seq_cst);
-    if (k > kSmallHostCheck)
+    if ((size_t)c.shape.k > kSmallHostCheck)
         LA_HIP(ctx, la::check_consumers_launch(c.T, (const int64_t*)(m + L.co), (const int32_t*)(m + L.cr), ln.d_status, st));
     const bool grouped = c.g_members >= 0;
-    // results the caller reads go to the host's memory; those only the grouping reads stay on the device.  The totals: only
-    // when the caller wants them
+    // results the caller reads go to the host's memory; those only the grouping reads stay on the device
     // (a cooperative call: the round reads the target on the device and hands it on to the host itself where it is wanted)
     char* res = (c.out_pid && !grouped && !c.coop) ? m : d;
-    const la_device_batch b = small_batch(c, L, m, res, c.out_total ? m : nullptr);
-    // ONE launch for the whole rebalance where the batch is one resident tile launch: its last workgroup builds the lists and
-    // stores the completion word -- otherwise the grouping / finishing launches below.  Where that pays was measured at the C
-    // ABI (profiles/r05_ae_fused_tail.txt): with lists, 100 / 500 partitions 22-24 / 25 us fused against 25 / 26.5 us with the
-    // one-workgroup grouping as its own launch, but 2 000 partitions 37-38 against 34 -- the tail is 256 threads of the tile
-    // kernel, the grouping kernel 1 024, and every workgroup of a fused launch pays a system-scope fence -- so the lists are fused
-    // up to kTailMaxEntries entries; a call WITHOUT lists is faster with the plain finishing launch at every size (100
-    // partitions 16.6 against 18.6 us, 10 000: 31 against 38) and never takes the tail.  LA_FUSED_TAIL=all restores round
-    // 5's first form (every staged call that can), LA_NO_FUSED_TAIL=1 never fuses.
-    static const bool no_tail = getenv("LA_NO_FUSED_TAIL") != nullptr;                 // (A/B hooks)
-    static const bool tail_all = [] { const char* e = getenv("LA_FUSED_TAIL"); return e && !strcmp(e, "all"); }();
-    const bool one_wg_lists = grouped ? (c.shape.n <= (tail_all ? la::kSmallGroupN : la::kTailMaxEntries) &&
-                                         (int64_t)c.g_members + 2 <= la::kTailGroupM)
-                                      : tail_all;
-    ln.tail_done = false;
-    ln.tail_wanted = one_wg_lists && !no_tail && k <= kSmallHostCheck && !c.coop;      // (the round is its own 1 024-thread launch)
-    if (ln.tail_wanted) {
-        ln.tail = la::TileTail{};
-        ln.tail.enabled = 1;
-        ln.tail.n_members = grouped ? c.g_members : 0;
-        ln.tail.n = (int32_t)c.shape.n;
-        ln.tail.n_topics = c.T;
-        ln.tail.part_off = (const int64_t*)(m + L.po);
-        ln.tail.out_pid = b.d_out_partition;
-        ln.tail.out_rank = b.d_out_member_rank;
-        ln.tail.member_off = grouped ? (int64_t*)(m + L.goff) : nullptr;
-        ln.tail.grouped_topic = grouped && c.g_topic ? (int32_t*)(m + L.gt) : nullptr;
-        ln.tail.grouped_partition = grouped ? (int32_t*)(m + L.gp) : nullptr;
-        ln.tail.counter = ln.d_status + 24;
-        ln.tail.fin_flag = (uint32_t*)(m + L.status);
-    }
-    int rc = enqueue_batch(ctx, ln, &b, st);
-    ln.tail_wanted = false;
-    bool finished = ln.tail_done;                                        // (the one-workgroup grouping also finishes the call)
-    ln.tail_done = false;
-    if (rc == LA_OK && grouped && !finished) {
-        const hipError_t e = small_group_launch(c, ln, L, m, d, m, ln.d_status, st, (uint32_t*)(m + L.status), &finished);
-        if (e != hipSuccess) rc = hip_fail(ctx, e, "group_by_member: %s");
-    }
-    if (rc == LA_OK && c.coop) {
-        const hipError_t e = small_coop_launch(c, ln, L, m, d, st);
-        if (e != hipSuccess) rc = hip_fail(ctx, e, "cooperative_round: %s");
-        finished = true;
-    }
-    if (rc == LA_OK && !finished) {
-        const hipError_t e = la::finish_status_launch(ln.d_status, (uint32_t*)(m + L.status), st);
-        if (e != hipSuccess) rc = fail(ctx, LA_EHIP, "finish launch: %s", hipGetErrorString(e));
-    }
-    if (rc != LA_OK) {
+    if (int rc = small_zc_enqueue(ctx, c, ln, L, m, d, res, st)) {
         // nothing of this call stays in flight or behind: kernels already enqueued may have OR-ed bits into the lane's status word
-        // (and counted themselves done on the tail's counter) -- the next call must not inherit them
+        // (and counted themselves done on the tail's counter)
         (void)hipStreamSynchronize(st);
-        (void)hipMemsetAsync(ln.d_status, 0, sizeof(uint32_t), st);
-        (void)hipMemsetAsync(ln.d_status + 24, 0, sizeof(uint32_t), st);
+        (void)lane_words_reset(ln, st, true);
         (void)hipStreamSynchronize(st);
         return rc;
     }
-    // the wait: a spin on the flag word; should the flag never come (a fault on the stream), the runtime will say why
-    uint32_t f = 0;
-    for (uint64_t spins = 0;; ++spins) {
-        f = *flag;
-        if (f & 0x80000000u) break;
-        if ((spins & 0xFFFu) == 0xFFFu) {
-            const hipError_t q = hipStreamQuery(st);
-            if (q == hipSuccess) { f = *flag; if (f & 0x80000000u) break; LA_HIP(ctx, hipStreamSynchronize(st)); f = *flag | 0x80000000u; break; }
-            if (q != hipErrorNotReady) {
-                (void)hipMemsetAsync(ln.d_status, 0, sizeof(uint32_t), st);          // (best effort after a stream error)
-                (void)hipMemsetAsync(ln.d_status + 24, 0, sizeof(uint32_t), st);
-                return fail(ctx, LA_EHIP, "zero-copy call: %s", hipGetErrorString(q));
-            }
-        }
-    }
-    std::atomic_thread_fence(std::memory_order_acquire);
-    const uint32_t status = f & 0x7FFFFFFFu;
+    uint32_t status = 0;
+    if (int rc = small_zc_wait(ctx, ln, flag, st, &status)) return rc;
     if (status) {
-        LA_HIP(ctx, hipMemsetAsync(ln.d_status, 0, sizeof(uint32_t), st));
+        // The completion word has arrived, so the tail's counter needs nothing: a launch that carried the tail has put it back to
+        // zero itself before it stored the word (tile_tail: "the next call's count"), and no other launch of the call touches it.
+        // The status word does: the tail and the grouping launch read it and leave it as it is.
+        LA_HIP(ctx, lane_words_reset(ln, st, false));
         LA_HIP(ctx, hipStreamSynchronize(st));
         return status_error(ctx, status);
     }
-    if (c.out_total && k) memcpy(c.out_total, h + L.ot, k * 8);
-    if (c.out_pid && n) {
-        if (grouped) {
-            // (no caller asks for both forms today: the ungrouped arrays would need their own trip)
-            LA_HIP(ctx, hipMemcpyAsync(c.out_pid, d + L.op, n * 4, hipMemcpyDeviceToHost, st));
-            LA_HIP(ctx, hipMemcpyAsync(c.out_rank, d + L.orank, n * 4, hipMemcpyDeviceToHost, st));
-            LA_HIP(ctx, hipStreamSynchronize(st));
-        } else {
-            const CopyPiece out[2] = {{c.out_pid, h + L.op, n * 4}, {c.out_rank, h + L.orank, n * 4}};
-            copy_pieces(ctx, out, 2);
-        }
+    if (grouped && c.out_pid && c.shape.n) {
+        // (no caller asks for both forms today: the ungrouped arrays would need their own trip)
+        const size_t nb4 = (size_t)c.shape.n * 4;
+        LA_HIP(ctx, hipMemcpyAsync(c.out_pid, L.at<int32_t>(d, kOutPid), nb4, hipMemcpyDeviceToHost, st));
+        LA_HIP(ctx, hipMemcpyAsync(c.out_rank, L.at<int32_t>(d, kOutRank), nb4, hipMemcpyDeviceToHost, st));
+        LA_HIP(ctx, hipStreamSynchronize(st));
     }
     // what la_group_last_by_member would read: valid only where the results stayed on the device
-    small_unpack(ctx, c, sh, L, h, /*pieces=*/true, m, res);
-    if (c.coop) small_coop_unpack(c, L, h);
+    small_unpack(ctx, c, sh, L, h, /*pieces=*/true, grouped ? kOutPid : kStagedOuts, m, res);
     return LA_OK;
 }
 
@@ -866,7 +831,6 @@ int assign_small(la_ctx* ctx, const HostCall& c, Shard& sh, const SmallLayout& L
     LA_HIP(ctx, hipSetDevice(sh.device));
     Lane& ln = sh.lanes[0];
     hipStream_t st = ln.stream;
-    const size_t n = (size_t)c.shape.n, k = (size_t)c.shape.k;
     if (int rc = reserve(ctx, sh.small_d, L.total)) return rc;
     if (int rc = reserve_host(ctx, sh.small_h, L.total)) return rc;
     char* h = (char*)sh.small_h.p;
@@ -874,38 +838,29 @@ int assign_small(la_ctx* ctx, const HostCall& c, Shard& sh, const SmallLayout& L
     if (int rc = small_fill_inputs(ctx, c, L, h)) return rc;
     memset(h + L.status, 0, 256);
     LA_HIP(ctx, hipMemcpyAsync(d, h, L.status + 256, hipMemcpyHostToDevice, st));
-    ln.status_word = (uint32_t*)(d + L.status);
-    struct Restore { Lane& l; ~Restore() { l.status_word = nullptr; } } restore{ln};
-    if (k > kSmallHostCheck) {
-        LA_HIP(ctx, la::check_consumers_launch(c.T, (const int64_t*)(d + L.co), (const int32_t*)(d + L.cr),
-                                               ln.status_word, st));
-    }
-    // the totals always: they sit between the status and the results
-    const la_device_batch b = small_batch(c, L, d, d, d);
-    if (int rc = enqueue_batch(ctx, ln, &b, st)) {
+    // the status word of this call's kernels lives inside its device staging buffer: uploaded as zero with the inputs,
+    // downloaded with the results
+    StagedBatch staged;
+    staged.status = (uint32_t*)(d + L.status);
+    if ((size_t)c.shape.k > kSmallHostCheck)
+        LA_HIP(ctx, la::check_consumers_launch(c.T, (const int64_t*)(d + L.co), (const int32_t*)(d + L.cr), staged.status, st));
+    const la_device_batch b = small_batch(c, L, d, d);
+    int rc = enqueue_batch(ctx, ln, &b, st, &staged);
+    // every member's list, built where the results are: one more launch on the same stream, no second round trip
+    if (rc == LA_OK && c.g_members >= 0)
+        if (const hipError_t e = small_group_launch(c, ln, L, d, d, d, staged.status, st); e != hipSuccess)
+            rc = hip_fail(ctx, e, "group_by_member: %s");
+    if (rc) {
         (void)hipStreamSynchronize(st);
         return rc;
     }
-    if (c.g_members >= 0) {
-        // every member's list, built where the results are: one more launch on the same stream, no second round trip
-        const hipError_t e = small_group_launch(c, ln, L, d, d, d, ln.status_word, st);
-        if (e != hipSuccess) {
-            (void)hipStreamSynchronize(st);
-            return hip_fail(ctx, e, "group_by_member: %s");
-        }
-    }
     // status | totals | (member_off | grouped topic | grouped partition) | partition order | member ranks: as far as the caller wants them
-    const size_t upto = c.out_pid ? L.total : L.op;
+    const size_t upto = c.out_pid ? L.total : L.out[kOutPid].off;
     LA_HIP(ctx, hipMemcpyAsync(h + L.status, d + L.status, upto - L.status, hipMemcpyDeviceToHost, st));
     LA_HIP(ctx, hipStreamSynchronize(st));
     const uint32_t status = *(const uint32_t*)(h + L.status);
     if (status) return status_error(ctx, status);
-    if (c.out_total && k) memcpy(c.out_total, h + L.ot, k * 8);
-    if (c.out_pid && n) {
-        memcpy(c.out_pid, h + L.op, n * 4);
-        memcpy(c.out_rank, h + L.orank, n * 4);
-    }
-    small_unpack(ctx, c, sh, L, h, /*pieces=*/false, d, d);
+    small_unpack(ctx, c, sh, L, h, /*pieces=*/false, kStagedOuts, d, d);
     return LA_OK;
 }
 
@@ -934,53 +889,30 @@ int group_shard_device(la_ctx* ctx, Shard& sh, int32_t n_members, bool want_topi
     return LA_OK;
 }
 
-}  // namespace
-
-// ---- planner: contiguous topic ranges balanced by partition count -----------------------------------------
-// The shard axis is the per-topic loop of assign(Map,Map) (Main.java:177-184): assignTopic touches only its own
-// topic's bins, so any split at topic boundaries is valid; the kernels' cost is per partition, so the split
-// balances partitions.  bounds[r] = first topic boundary at or after r/parts of the partitions.  Every topic
-// lands in exactly one range; ranges may be empty.  Used for shards (devices) and for the chunks of one shard.
-void plan_ranges(const int64_t* po, int32_t t_begin, int32_t t_end, int parts, int32_t* bounds) {
-    const int64_t base = po[t_begin], total = po[t_end] - base;
-    bounds[0] = t_begin;
-    for (int r = 1; r < parts; ++r) {
-        const int64_t target = base + (total / parts) * r + (total % parts) * r / parts;
-        const int64_t* lo = std::lower_bound(po + bounds[r - 1], po + t_end + 1, target);
-        int64_t t = lo - po;
-        if (t > t_end) t = t_end;
-        bounds[r] = (int32_t)t;
+// ... into the shard's own arrays, and that CSR back to the host: the offsets, the topics (null: not wanted) and the partitions.
+// Waits, and reports what the grouping's sort flagged through the lane's status word.
+int group_shard_to_host(la_ctx* ctx, Shard& sh, int32_t n_members, int64_t* off, int32_t* topic, int32_t* part) {
+    if (int rc = group_shard_device(ctx, sh, n_members, topic != nullptr)) return rc;
+    hipStream_t st = sh.lanes[0].stream;
+    const size_t nb4 = (size_t)sh.last_n * 4;
+    LA_HIP(ctx, hipMemcpyAsync(off, sh.out_total.p, ((size_t)n_members + 1) * 8, hipMemcpyDeviceToHost, st));
+    if (sh.last_n) {
+        LA_HIP(ctx, hipMemcpyAsync(part, sh.pid.p, nb4, hipMemcpyDeviceToHost, st));
+        if (topic) LA_HIP(ctx, hipMemcpyAsync(topic, sh.cons_rank.p, nb4, hipMemcpyDeviceToHost, st));
     }
-    bounds[parts] = t_end;
+    return sync_status(ctx, sh.lanes[0], st);
 }
 
-// The sizes up to which a call is staged, and staged zero-copy: the defaults, and their lab overrides read once per context.
-void host_defaults(la_ctx* ctx) {
-    ctx->zero_copy_bytes = kZeroCopyBytes;
-    if (const char* env = getenv("LA_ZERO_COPY_BYTES")) ctx->zero_copy_bytes = (size_t)atoll(env);
-    ctx->small_bytes = kSmallBytes;
-    if (const char* env = getenv("LA_SMALL_BYTES")) ctx->small_bytes = (size_t)atoll(env);      // (lab: where the forms hand over)
-}
-
-// One host-buffer assign call.  The entry point has filled in what it was given -- the arrays, the sparse trio behind `sparse`,
-// the grouped quartet behind g_members >= 0 -- and everything else of `c` is worked out here.
-int assign_host(la_ctx* ctx, HostCall& c) {
-    if (!ctx) return LA_EINVAL;
-    ctx->last_valid = false;
-    const bool hinted = ctx->hints_set;                       // one-shot: whatever this call returns, the hints are spent
-    ctx->hints_set = false;
-    const int32_t T = c.T;
-    const int64_t *part_off = c.part_off, *cons_off = c.cons_off;
-    if (T < 0) return fail(ctx, LA_EINVAL, "n_topics < 0");
-    if (T == 0) return LA_OK;
-    if (!part_off || !cons_off) return fail(ctx, LA_EINVAL, "null offsets");
+// The caller's side of a call, checked and normalised: the hinted bounds, the shape, which arrays the call needs and reads.
+int normalise_call(la_ctx* ctx, HostCall& c, bool hinted) {
+    if (!c.part_off || !c.cons_off) return fail(ctx, LA_EINVAL, "null offsets");
     if (hinted && (ctx->hints.flags & LA_HINT_BOUNDS) && ctx->hints.max_lag >= 0 && ctx->hints.max_partition_id >= 0) {
         c.bounded = true;
         c.max_lag = ctx->hints.max_lag;
         c.max_id = ctx->hints.max_partition_id;
     }
-    // offsets are checked here; cons_rank's order on the device (run_lane)
-    if (int rc = scan_shape(ctx, T, part_off, cons_off, nullptr, &c.shape)) return rc;
+    // offsets are checked here; cons_rank's order on the device (chunk_device_work)
+    if (int rc = scan_shape(ctx, c.T, c.part_off, c.cons_off, &c.shape)) return rc;
     const Shape& s = c.shape;
     if (s.n > 0 && (!c.pid || (!c.lag && (!c.end || !c.committed)))) return fail(ctx, LA_EINVAL, "null per-partition buffer");
     if ((c.out_pid == nullptr) != (c.out_rank == nullptr))
@@ -997,84 +929,74 @@ int assign_host(la_ctx* ctx, HostCall& c) {
     } else {
         c.n_none = 0; c.none_index = nullptr; c.none_begin = nullptr;
     }
+    return LA_OK;
+}
 
-    // shards: all devices for a batch worth splitting, fewer (down to one) for a small one
-    int S = (int)ctx->shards.size();
-    if (!ctx->split_always) {
-        const int64_t by_size = s.n / kMinShardPartitions;
-        if (by_size < S) S = by_size < 1 ? 1 : (int)by_size;
-    }
-    if (S > T) S = T;
-    plan_ranges(part_off, 0, T, S, ctx->last_bounds);
-    ctx->last_shards = S;
-    const bool may_stage = S == 1 && !ctx->split_always && s.n > 0;
-    // la_assign_batch_cooperative.  FUSED: a zero-copy staged call within the round kernel's limits.  Anything else is the
-    // GENERAL form: this call is then a plain assign call into buffers of the context's own (totals | ids | ranks), and the entry
-    // point runs the round on them -- the caller's arrays see nothing before both have succeeded.
-    auto coop_general = [&] {
-        ctx->coop_target.resize((size_t)s.k + (size_t)s.n + 1);
-        c.out_total = ctx->coop_target.data();
-        c.out_pid = (int32_t*)(ctx->coop_target.data() + s.k);
-        c.out_rank = c.out_pid + s.n;
-        c.coop = nullptr;
+// How the arrays of the call can be reached: pageable, pinned, or pinned and device-mapped (`no_mapped`: the
+// LA_NO_MAPPED_PIPELINE hook -- mapped arrays then count as pinned).  Probed when first asked for and kept in the call: the
+// probes are two runtime queries per array, and the smallest calls never need them.
+enum { kMemPageable, kMemPinned, kMemMapped };
+
+int call_memory(HostCall& c, bool no_mapped) {
+    if (c.memory < 0) c.memory = !call_is_pinned(c) ? kMemPageable : (!no_mapped && call_is_mapped(c) ? kMemMapped : kMemPinned);
+    return c.memory;
+}
+
+// la_assign_batch_cooperative, the GENERAL form: this call becomes a plain assign call into buffers of the context's own
+// (totals | ids | ranks), and the entry point runs the round on them -- the caller's arrays see nothing before both have
+// succeeded.  (The outputs are other arrays now: their memory is probed anew.)
+void coop_take_general(la_ctx* ctx, HostCall& c) {
+    ctx->coop_target.resize((size_t)c.shape.k + (size_t)c.shape.n + 1);
+    c.out_total = ctx->coop_target.data();
+    c.out_pid = (int32_t*)(ctx->coop_target.data() + c.shape.k);
+    c.out_rank = c.out_pid + c.shape.n;
+    c.coop = nullptr;
+    c.memory = -1;
+}
+
+// Whether a one-shard call travels through ONE staging buffer, and with what aboard: *L <- its layout.
+// How large a layout still does.  Pageable caller arrays: kSmallBytes (12 MB) -- beyond, packing the inputs costs as much as the
+// lanes' overlapped copies.  Caller arrays that are pinned need no packing at all on the other side of the comparison:
+// device-mapped ones (la_host_alloc: the Java host's direct buffers) are read in place by the kernels from 1.25 MB on (3 MB with
+// the lists aboard, which the staged form brings back in the same round trip); pinned but not mapped ones keep round 4's 2 MB.
+// profiles/r05_o_latency_probe.txt.
+bool stage_decision(la_ctx* ctx, HostCall& c, bool no_mapped, SmallLayout* L) {
+    auto fits = [&](bool with_lists) {
+        size_t upto = kSmallBytes;
+        if (L->total > kMappedSmallBytes && call_memory(c, no_mapped) != kMemPageable) {
+            const size_t lim = c.memory == kMemMapped ? (with_lists ? kMappedSmallGroupedBytes : kMappedSmallBytes) : kPinnedSmallBytes;
+            if (lim < upto) upto = lim;
+        }
+        return L->total <= upto;
     };
-    if (c.coop) {
-        la::CoopCall probe = c.coop->c;
-        probe.n_topics = T;
-        probe.n_partitions = s.n;
-        if (!may_stage || c.coop_force_table || !la::coop_round_is_small(probe)) coop_general();
-    }
-    if (may_stage) {
-        SmallLayout L = small_layout(c);
-        // How large a layout still travels through ONE staging buffer.  Pageable caller arrays: ctx->small_bytes (12 MB) -- beyond,
-        // packing the inputs costs as much as the lanes' overlapped copies.  Caller arrays that are pinned
-        // need no packing at all on the other side of the comparison: device-mapped ones (la_host_alloc: the Java host's direct
-        // buffers) are read in place by the kernels from 1.25 MB on (3 MB with the lists aboard, which the staged form brings
-        // back in the same round trip); pinned but not mapped ones keep round 4's 2 MB.  profiles/r05_o_latency_probe.txt.
-        const bool no_pinned_rule = getenv("LA_NO_MAPPED_SMALL") || getenv("LA_NO_ASYNC_PIPELINE");
-        auto staged_upto = [&](bool with_lists) {
-            size_t upto = ctx->small_bytes;
-            if (L.total > kMappedSmallBytes && !no_pinned_rule && call_is_pinned(c)) {
-                const bool mapped = !getenv("LA_NO_MAPPED_PIPELINE") && call_is_mapped(c);
-                const size_t lim = mapped ? (with_lists ? kMappedSmallGroupedBytes : kMappedSmallBytes) : kPinnedSmallBytes;
-                if (lim < upto) upto = lim;
-            }
-            return upto;
-        };
-        size_t upto = staged_upto(c.g_members >= 0);
-        if (c.coop && (L.total > upto || L.total > ctx->zero_copy_bytes)) {
-            coop_general();
-            L = small_layout(c);
-            upto = staged_upto(false);
-        }
-        if (L.total > upto && c.g_members >= 0) {            // too large with the lists aboard: they take their own round trip
-            c.g_members = -1;
-            L = small_layout(c);
-            upto = staged_upto(false);
-        }
-        if (L.total <= upto) {
-            Shard& sh = ctx->shards[0];
-            sh.last_t0 = 0; sh.last_topics = T; sh.last_p0 = 0; sh.last_n = s.n;
-            const bool zc = L.total <= ctx->zero_copy_bytes;
-            ctx->last_pipeline = zc ? LA_PIPELINE_ZERO_COPY : LA_PIPELINE_ONE_COPY;
-            if (int rc = zc ? assign_small_zc(ctx, c, sh, L) : assign_small(ctx, c, sh, L)) return rc;
-            ctx->last_valid = true;
-            return LA_OK;
-        }
-    }
+    *L = small_layout(c);
+    // (a cooperative call is FUSED only as a zero-copy staged call)
+    if (fits(c.g_members >= 0) && !(c.coop && L->total > ctx->zero_copy_bytes)) return true;
+    // too large with everything aboard: the round of a cooperative call follows the call, the lists of a grouped one take their
+    // own round trip (no call is both) -- and what is left is asked once more
+    if (c.coop) coop_take_general(ctx, c);
+    else if (c.g_members >= 0) c.g_members = -1;
+    else return false;
+    *L = small_layout(c);
+    return fits(false);
+}
+
+// The chunked pipelines over the S shards of ctx->last_bounds: the caller's arrays read in place (mapped), sent over three
+// streams by this thread (pinned), or by a host thread per lane (pageable).
+int run_pipelines(la_ctx* ctx, HostCall& c, int S, bool no_mapped) {
     std::vector<ShardPlan> plans((size_t)S);
     struct Work { int shard, lane; };
     std::vector<Work> work;
-    const bool pinned = call_is_pinned(c) && !getenv("LA_NO_ASYNC_PIPELINE");
-    c.mapped = pinned && !getenv("LA_NO_MAPPED_PIPELINE") && call_is_mapped(c);
+    const bool pinned = call_memory(c, no_mapped) != kMemPageable;
+    c.mapped = c.memory == kMemMapped;
     ctx->last_pipeline = c.mapped ? LA_PIPELINE_MAPPED : (pinned ? 2 : 1);
     for (int i = 0; i < S; ++i) {
         ShardPlan& sp = plans[(size_t)i];
         Shard& sh = ctx->shards[(size_t)i];
         sp.t0 = ctx->last_bounds[i];
         sp.t1 = ctx->last_bounds[i + 1];
-        sp.P0 = part_off[sp.t0]; sp.n = part_off[sp.t1] - sp.P0;
-        sp.K0 = cons_off[sp.t0]; sp.k = cons_off[sp.t1] - sp.K0;
+        sp.P0 = c.part_off[sp.t0]; sp.n = c.part_off[sp.t1] - sp.P0;
+        sp.K0 = c.cons_off[sp.t0]; sp.k = c.cons_off[sp.t1] - sp.K0;
         sh.last_t0 = sp.t0; sh.last_topics = sp.t1 - sp.t0; sh.last_p0 = sp.P0; sh.last_n = sp.n;
         if (sp.t1 == sp.t0) continue;
         const int rc_prepare = prepare_shard(ctx, c, sh, sp);
@@ -1110,17 +1032,87 @@ int assign_host(la_ctx* ctx, HostCall& c) {
             const int rf = finish_shard_async(ctx, ctx->shards[(size_t)i]);
             if (rc == LA_OK) rc = rf;
         }
-        if (rc) return rc;
-        ctx->last_valid = true;
-        return LA_OK;
+        return rc;
     }
     std::atomic<bool> stop{false};
-    const int rc = run_workers(ctx, (int)work.size(), [&](int w) {
+    return run_workers(ctx, (int)work.size(), [&](int w) {
         const Work& wk = work[(size_t)w];
         const int r = run_lane(ctx, c, ctx->shards[(size_t)wk.shard], plans[(size_t)wk.shard], wk.lane, stop);
         if (r != LA_OK) stop.store(true, std::memory_order_relaxed);
         return r;
     });
+}
+
+}  // namespace
+
+// ---- planner: contiguous topic ranges balanced by partition count -----------------------------------------
+// The shard axis is the per-topic loop of assign(Map,Map) (Main.java:177-184): assignTopic touches only its own
+// topic's bins, so any split at topic boundaries is valid; the kernels' cost is per partition, so the split
+// balances partitions.  bounds[r] = first topic boundary at or after r/parts of the partitions.  Every topic
+// lands in exactly one range; ranges may be empty.  Used for shards (devices) and for the chunks of one shard.
+void plan_ranges(const int64_t* po, int32_t t_begin, int32_t t_end, int parts, int32_t* bounds) {
+    const int64_t base = po[t_begin], total = po[t_end] - base;
+    bounds[0] = t_begin;
+    for (int r = 1; r < parts; ++r) {
+        const int64_t target = base + (total / parts) * r + (total % parts) * r / parts;
+        const int64_t* lo = std::lower_bound(po + bounds[r - 1], po + t_end + 1, target);
+        int64_t t = lo - po;
+        if (t > t_end) t = t_end;
+        bounds[r] = (int32_t)t;
+    }
+    bounds[parts] = t_end;
+}
+
+// The size up to which a staged call runs zero-copy: the default, and its lab override read once per context.
+void host_defaults(la_ctx* ctx) {
+    ctx->zero_copy_bytes = kZeroCopyBytes;
+    if (const char* env = getenv("LA_ZERO_COPY_BYTES")) ctx->zero_copy_bytes = (size_t)atoll(env);
+}
+
+// One host-buffer assign call.  The entry point has filled in what it was given -- the arrays, the sparse trio behind `sparse`,
+// the grouped quartet behind g_members >= 0 -- and everything else of `c` is worked out here.
+int assign_host(la_ctx* ctx, HostCall& c) {
+    if (!ctx) return LA_EINVAL;
+    ctx->last_valid = false;
+    const bool hinted = ctx->hints_set;                       // one-shot: whatever this call returns, the hints are spent
+    ctx->hints_set = false;
+    const int32_t T = c.T;
+    if (T < 0) return fail(ctx, LA_EINVAL, "n_topics < 0");
+    if (T == 0) return LA_OK;
+    if (int rc = normalise_call(ctx, c, hinted)) return rc;
+    const Shape& s = c.shape;
+    // the one environment hook of a call, read at every call (tests and the benchmark flip it around live contexts)
+    const bool no_mapped = getenv("LA_NO_MAPPED_PIPELINE") != nullptr;
+
+    // shards: all devices for a batch worth splitting, fewer (down to one) for a small one
+    int S = (int)ctx->shards.size();
+    if (!ctx->split_always) {
+        const int64_t by_size = s.n / kMinShardPartitions;
+        if (by_size < S) S = by_size < 1 ? 1 : (int)by_size;
+    }
+    if (S > T) S = T;
+    plan_ranges(c.part_off, 0, T, S, ctx->last_bounds);
+    ctx->last_shards = S;
+    const bool may_stage = S == 1 && !ctx->split_always && s.n > 0;
+    // la_assign_batch_cooperative.  FUSED: a zero-copy staged call within the round kernel's limits.  Anything else is the
+    // GENERAL form (coop_take_general).
+    if (c.coop) {
+        la::CoopCall probe = c.coop->c;
+        probe.n_topics = T;
+        probe.n_partitions = s.n;
+        if (!may_stage || c.coop_force_table || !la::coop_round_is_small(probe)) coop_take_general(ctx, c);
+    }
+    SmallLayout L;
+    int rc;
+    if (may_stage && stage_decision(ctx, c, no_mapped, &L)) {
+        Shard& sh = ctx->shards[0];
+        sh.last_t0 = 0; sh.last_topics = T; sh.last_p0 = 0; sh.last_n = s.n;
+        const bool zc = L.total <= ctx->zero_copy_bytes;
+        ctx->last_pipeline = zc ? LA_PIPELINE_ZERO_COPY : LA_PIPELINE_ONE_COPY;
+        rc = zc ? assign_small_zc(ctx, c, sh, L) : assign_small(ctx, c, sh, L);
+    } else {
+        rc = run_pipelines(ctx, c, S, no_mapped);
+    }
     if (rc) return rc;
     ctx->last_valid = true;
     return LA_OK;
@@ -1160,13 +1152,7 @@ int group_last_impl(la_ctx* ctx, int32_t n_members, int64_t* member_off, int32_t
             }
             return LA_OK;
         }
-        if (int rc = group_shard_device(ctx, sh, n_members, grouped_topic != nullptr)) return rc;
-        LA_HIP(ctx, hipMemcpyAsync(member_off, sh.out_total.p, mb, hipMemcpyDeviceToHost, st));
-        if (n) {
-            LA_HIP(ctx, hipMemcpyAsync(grouped_partition, sh.pid.p, nb4, hipMemcpyDeviceToHost, st));
-            if (grouped_topic) LA_HIP(ctx, hipMemcpyAsync(grouped_topic, sh.cons_rank.p, nb4, hipMemcpyDeviceToHost, st));
-        }
-        return sync_status(ctx, sh.lanes[0], st);
+        return group_shard_to_host(ctx, sh, n_members, member_off, grouped_topic, grouped_partition);
     }
     // Several shards.  A member's list is its per-topic appends in topic order (Main.java:177-184, :264), and the
     // shards are contiguous topic ranges: the list is the concatenation, in shard order, of the shards' lists.
@@ -1182,18 +1168,18 @@ int group_last_impl(la_ctx* ctx, int32_t n_members, int64_t* member_off, int32_t
         if ((r = reserve_host(ctx, sh.g_off, mb)) || (r = reserve_host(ctx, sh.g_part, nb4 + 16)) ||
             (grouped_topic && (r = reserve_host(ctx, sh.g_topic, nb4 + 16))))
             return r;
-        if ((r = group_shard_device(ctx, sh, n_members, grouped_topic != nullptr))) return r;
-        hipStream_t st = sh.lanes[0].stream;
-        LA_HIP(ctx, hipMemcpyAsync(sh.g_off.p, sh.out_total.p, mb, hipMemcpyDeviceToHost, st));
-        if (sh.last_n) {
-            LA_HIP(ctx, hipMemcpyAsync(sh.g_part.p, sh.pid.p, nb4, hipMemcpyDeviceToHost, st));
-            if (grouped_topic) LA_HIP(ctx, hipMemcpyAsync(sh.g_topic.p, sh.cons_rank.p, nb4, hipMemcpyDeviceToHost, st));
-        }
-        return sync_status(ctx, sh.lanes[0], st);
+        return group_shard_to_host(ctx, sh, n_members, (int64_t*)sh.g_off.p, grouped_topic ? (int32_t*)sh.g_topic.p : nullptr,
+                                   (int32_t*)sh.g_part.p);
     });
     if (rc) return rc;
     // group g = 0 is "no consumer" (rank -1: the entries before member_off[0]), g = r + 1 is member r
     const size_t G = (size_t)n_members + 1;
+    // shard sh's entries of group g: [lo, hi) of its CSR
+    auto slice = [G](const Shard& sh, size_t g, int64_t& lo, int64_t& hi) {
+        const int64_t* so = (const int64_t*)sh.g_off.p;
+        lo = g == 0 ? 0 : so[g - 1];
+        hi = g == G - 1 ? sh.last_n : so[g];
+    };
     std::vector<int64_t> base((size_t)S * G);          // destination of shard i's slice of group g
     {
         int64_t run = 0;
@@ -1203,8 +1189,8 @@ int group_last_impl(la_ctx* ctx, int32_t n_members, int64_t* member_off, int32_t
                 const Shard& sh = ctx->shards[(size_t)i];
                 base[(size_t)i * G + g] = run;
                 if (sh.last_topics == 0) continue;
-                const int64_t* so = (const int64_t*)sh.g_off.p;
-                const int64_t lo = g == 0 ? 0 : so[g - 1], hi = g == G - 1 ? sh.last_n : so[g];
+                int64_t lo, hi;
+                slice(sh, g, lo, hi);
                 run += hi - lo;
             }
         }
@@ -1213,11 +1199,11 @@ int group_last_impl(la_ctx* ctx, int32_t n_members, int64_t* member_off, int32_t
     rc = run_workers(ctx, S, [&](int i) -> int {
         const Shard& sh = ctx->shards[(size_t)i];
         if (sh.last_topics == 0 || sh.last_n == 0) return LA_OK;
-        const int64_t* so = (const int64_t*)sh.g_off.p;
         const int32_t* sp = (const int32_t*)sh.g_part.p;
         const int32_t* stp = (const int32_t*)sh.g_topic.p;
         for (size_t g = 0; g < G; ++g) {
-            const int64_t lo = g == 0 ? 0 : so[g - 1], hi = g == G - 1 ? sh.last_n : so[g];
+            int64_t lo, hi;
+            slice(sh, g, lo, hi);
             if (hi <= lo) continue;
             const int64_t dst = base[(size_t)i * G + g];
             memcpy(grouped_partition + dst, sp + lo, (size_t)(hi - lo) * 4);

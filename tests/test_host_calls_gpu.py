@@ -527,3 +527,96 @@ def test_la_wake_leaves_the_next_call_alone(ctx):
     finally:
         multi.close()
     assert N.load().la_wake(None) == N.LA_EINVAL
+
+
+# ---- what a staged call asks of the dispatcher travels with the call, never on the lane ----------------------------------------------
+def test_a_lane_carries_nothing_from_one_call_to_the_next(ctx):
+    """Lane 0 of shard 0 serves the staged host calls AND every device entry point.  The tail a zero-copy call hangs on its tile
+    launch and the status word a one-copy call keeps in its staging buffer are arguments of that call's dispatch: the plain tile
+    dispatch of a device-entry call behind a fused-tail call carries no tail, a staged call that fails (bounds the data breaks: its
+    status arrives with the completion word) leaves the tail's counter and the status word ready for the next call, and a
+    device-entry call behind a one-copy call reports through the lane's own status word again."""
+    w = synth.make_uniform("lane", 61, 3, 40, 4, "uniform40")
+    n_members = 6
+    a = (w.part_off, w.partition_id, w.begin, w.end, w.committed, N.LA_RESET_EARLIEST, w.cons_off, w.cons_rank)
+    off, topic, part, tot, (e_pid, e_rank) = _grouped_expect(w, n_members)
+
+    def fused(what):
+        g_off, g_t, g_p, g_tot = ctx.assign_batch_grouped(*a, n_members)
+        assert ctx.last_pipeline() == N.LA_PIPELINE_ZERO_COPY and ctx.last_launches() == 1, (what, ctx.last_launches())
+        for g, e, name in zip((g_off, g_t, g_p, g_tot), (off, topic, part, tot), ("member_off", "topics", "partitions", "totals")):
+            np.testing.assert_array_equal(g, e, err_msg="%s %s" % (name, what))
+
+    fused("first")
+    _same3(_device_call(ctx, w), oracle.assign_flat(w.part_off, w.partition_id, w.lag, w.cons_off, w.cons_rank),
+           "device entry behind a fused tail")
+    # one large-path topic, staged: its keys kernel reports the lag beyond the promised bound
+    big = _topic_with_lags(np.random.default_rng(62).integers(0, 1 << 20, 20000), 4, 62)
+    ctx.hint_next_call((int(big.lag.max()) - 1, int(big.partition_id.max())))
+    with pytest.raises(N.LagAssignError) as ei:
+        ctx.assign_batch_lags(big.part_off, big.partition_id, big.lag, big.cons_off, big.cons_rank)
+    assert ei.value.code == N.LA_EINVAL and "bounds" in str(ei.value) and ctx.last_pipeline() == N.LA_PIPELINE_ZERO_COPY
+    fused("behind a failed staged call")
+
+    os.environ["LA_ZERO_COPY_BYTES"] = "0"                          # (read at la_create)
+    try:
+        one = N.Context(0)
+    finally:
+        os.environ.pop("LA_ZERO_COPY_BYTES", None)
+    with one:
+        exp = (e_pid, e_rank, tot)
+        _same3(one.assign_batch(*a), exp, "one copy")
+        assert one.last_pipeline() == N.LA_PIPELINE_ONE_COPY
+        # a shape hint within one wave tile and one topic beyond it: the kernels of the plain tile dispatch raise a status bit
+        shapes = [(250 - (i % 3), 32) for i in range(40)]
+        shapes[7] = (300, 32)
+        over = _batch_of(shapes, 7, kinds=["u20", "u40"])
+        over.max_partitions, over.max_consumers = 256, 32
+        with pytest.raises(N.LagAssignError) as ei:
+            _device_call(one, over)
+        assert ei.value.code == N.LA_ESHAPE, ei.value
+        _same3(one.assign_batch(*a), exp, "one copy again")
+        assert one.last_pipeline() == N.LA_PIPELINE_ONE_COPY
+
+
+# ---- the chunk body at its empty edges ---------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("entry", ["dense", "sparse", "lags"])
+@pytest.mark.parametrize("shapes", [[(0, 5), (900, 8), (0, 3)], [(0, 5), (0, 3)]], ids=["one_topic_of_work", "no_partitions"])
+@pytest.mark.parametrize("kind", ["lanes", "streams", "mapped"])
+def test_chunks_with_nothing_to_assign(kind, shapes, entry):
+    """Three chunks over [(0, 5), (900, 8), (0, 3)] are topics [0, 2), [2, 2) and [2, 3): one with work, one with nothing, one
+    with consumers but no partitions; [(0, 5), (0, 3)] has no partitions at all, is never staged and meets the pipelines'
+    empty-work rule directly.  Through the lanes (pageable arrays), the three streams (pinned arrays, LA_NO_MAPPED_PIPELINE) and
+    in place (pinned and mapped arrays; the list with work is small enough to be staged there): the oracle's order and ranks, and
+    a total of 0 -- written over the sentinel -- for every consumer of a partition-less topic."""
+    w = _batch_of(shapes, 70 + len(shapes), kinds=["u40", "ties"])
+    rng = np.random.default_rng(71)
+    n, k = w.n_partitions, w.cons_rank.size
+    w.committed = np.where(rng.random(n) < 0.3, -1, rng.integers(0, 1 << 20, n)).astype(np.int64)
+    w.begin = rng.integers(0, 1 << 19, n).astype(np.int64)
+    w.end = np.maximum(w.committed, w.begin) + w.lag
+    exp = _expected(w, False)
+    assert (exp[2][:5] == 0).all() and (exp[2][-3:] == 0).all()
+    flags = {"lanes": N.LA_CREATE_SPLIT_ALWAYS | 3, "streams": N.LA_CREATE_SPLIT_ALWAYS, "mapped": 0}[kind]
+    want = {"lanes": N.LA_PIPELINE_LANES, "streams": N.LA_PIPELINE_STREAMS,
+            "mapped": N.LA_PIPELINE_MAPPED if n == 0 else N.LA_PIPELINE_ZERO_COPY}[kind]
+    with N.Context(0, flags=flags) as c:
+        give = (lambda x: x) if kind == "lanes" else (lambda x: _pinned(c, x))
+        out = tuple(give(np.full(m, SENTINEL, t)) for m, t in ((n, np.int32), (n, np.int32), (k, np.int64)))
+        po, pid, co, cr = give(w.part_off), give(w.partition_id), give(w.cons_off), give(w.cons_rank)
+        if kind == "streams":
+            os.environ["LA_NO_MAPPED_PIPELINE"] = "1"               # (read at every call)
+        try:
+            if entry == "dense":
+                got = c.assign_batch(po, pid, give(w.begin), give(w.end), give(w.committed), N.LA_RESET_EARLIEST, co, cr, out=out)
+            elif entry == "sparse":
+                idx, val = N.sparse_begin(w.begin, w.committed)
+                got = c.assign_batch_sparse(po, pid, give(w.end), give(w.committed), N.LA_RESET_EARLIEST, give(idx), give(val), co, cr,
+                                            out=out)
+            else:
+                lag = oracle.compute_lags(w.begin, w.end, w.committed, False)
+                got = c.assign_batch_lags(po, pid, give(lag), co, cr, out=out)
+        finally:
+            os.environ.pop("LA_NO_MAPPED_PIPELINE", None)
+        assert c.last_pipeline() == want, c.last_pipeline()
+        _same3(got, exp, "%s, %s" % (kind, entry))
