@@ -37,6 +37,8 @@
  *                           would have produced for these inputs, checked without running it again
  *   la_cooperative_adjust_device  nothing in the reference, whose protocol is eager: the assignment a COOPERATIVE assignor
  *                           returns -- every partition that changes hands between two live members withheld for this round
+ *   la_sticky_ties_device   nothing in the reference, which orders partitions of equal lag by id: the same assignment with the
+ *                           partitions of each run of equal lag re-matched to their previous owners
  *   la_hint_next_call       nothing in the reference's arithmetic: what the marshalling loop of readTopicPartitionLags
  *                           (Main.java:344-356) knows for free -- the largest end offset and partition id it walked past
  *   la_last_phase_times     nothing: measurement hook (radix-sort phase against the HBM roofline)
@@ -264,6 +266,7 @@ const char *la_last_error(const la_ctx *ctx);
  *                la_cooperative_adjust_device (the cooperative form of a rebalance);
  *                la_cooperative_round_device / la_cooperative_round (that form and every member's list of it in one call);
  *                la_assign_batch_cooperative (a cooperative rebalance from host buffers in one call);
+ *                la_sticky_ties_device (among partitions of equal lag the previous owner keeps its own);
  *                a shim detects them by symbol lookup (dlsym / getattr) instead of by version */
 #define LA_VERSION 500
 int la_version(void);
@@ -695,6 +698,8 @@ int la_assignment_moves_device_on(la_ctx *ctx, int shard, const la_moves_args *a
  *                       checks report for that topic is unspecified.
  *   d_summary[4]        [0] topics with any of the bits 1-16, [1] topics UNCHECKED, [2] / [3] the lowest topic index counted in
  *                       [0] / [1], or -1
+ * The order la_sticky_ties_device writes, put in place of d_out_partition, reads 0 or exactly LA_VERDICT_ORDER: inside a run of
+ * equal lag its ids no longer ascend, V1, V3 and V4 hold.
  * A non-zero verdict is data, not an error: la_sync still returns LA_OK.  Offsets that leave [0, N) / [0, K) are LA_ESHAPE from
  * la_sync: nothing is read through them, and the topic reads UNCHECKED.  T == 0 and N == 0 are valid (summary 0, 0, -1, -1).
  * Of the batch's other fields: algo is not looked at, h_part_off / h_cons_off only with LA_FLAG_VERIFY_LARGE (below); flags with
@@ -915,6 +920,62 @@ typedef struct la_assign_coop_args {
     int64_t *summary;               /* [6] or NULL */
 } la_assign_coop_args;
 int la_assign_batch_cooperative(la_ctx *ctx, const la_assign_coop_args *args);
+
+/* Sticky ties: among partitions of EQUAL lag, keep the previous owner (nothing in the reference computes it).  The reference
+ * hands a topic's partitions out by (lag descending, id ascending); inside a run of equal lag it cannot tell them apart, and
+ * permuting the partitions of such a run leaves the owner at every position, every consumer's count and total and every member's
+ * load as they are.  So the reference's greedy decides who gets how much; this call decides WHICH partitions of a run, by their
+ * previous owner.  A group that has caught up (most lags 0) otherwise reshuffles nearly every partition on every rebalance.
+ * `batch` is the struct an assign call took, inputs and results, read as la_verify_assignment_device reads it: the lag from
+ * d_lag, or from begin / end / committed with reset_mode; d_part_off, d_partition_id, d_out_partition and d_out_member_rank are
+ * read; consumers, algo, the host offsets and every flag are ignored, but LA_FLAG_WIRE_OUT is LA_EINVAL (unpack first).  The
+ * call runs stream-ordered behind the assign call and behind the call that produced d_prev_owner, no sync in between.
+ * For topic t with positions i in [part_off[t], part_off[t+1]):
+ *   lag_i = the Java lag of the input partition of the topic whose id is d_out_partition[i] (a join on the id, as in verify);
+ *   a RUN is a maximal range of consecutive positions of equal lag_i;  c_i = d_out_member_rank[i];  q_i = d_prev_owner[i].
+ * Inside one run R:
+ *   1  for every c >= 0, S_c = the positions of R with c_i == c, ascending
+ *   2  for every c >= 0, W_c = the positions of R with q_i == c, ascending
+ *   3  for k < min(|S_c|, |W_c|) the partition at position W_c[k] goes to position S_c[k]
+ *   4  the partitions not placed by 3, in ascending position, go to the positions not filled by 3, in ascending position
+ *   5  d_sticky_partition[dest] = d_out_partition[src]
+ * A position is KEPT when the partition placed there has q >= 0 and q equals the position's c; "kept before" is the same count
+ * over d_out_partition as it came.  Kept after, sum over c of min(|S_c|, |W_c|) per run, is the most any permutation that keeps
+ * the lag at every position can reach.  Owners -1 (a topic without consumers) and previous owners < 0 (-1, LA_MOVES_NO_PREVIOUS)
+ * never match; a q that is no owner in the run matches nothing and is never used as an index.
+ * d_out_member_rank and d_out_total_lag stay valid for the sticky order as they are: pass d_sticky_partition in place of
+ * d_out_partition to la_cooperative_round_device, la_group_by_member_device or la_member_loads_device.  For
+ * la_verify_assignment_device the sticky order reads 0 or exactly LA_VERDICT_ORDER per topic -- ids inside a run no longer
+ * ascend; V1, V3 and V4 hold.
+ * Outputs are OVERWRITTEN:
+ *   d_sticky_partition[N]  required when N > 0; must not overlap any input (equal to d_out_partition: LA_EINVAL)
+ *   d_topic_kept[T]        kept AFTER per topic, or NULL
+ *   d_topic_saved[T]       kept after - kept before (>= 0), or NULL
+ *   d_summary[4]           kept before, kept after, topics whose order changed, topics passed through, or NULL
+ * One workgroup re-matches a topic in its LDS, which holds 4096 partitions.  A larger topic is PASSED THROUGH: its
+ * d_sticky_partition is a copy of d_out_partition, saved 0, kept the count before, and it is counted in d_summary[3] -- data, not
+ * an error: the reference's order is always a valid answer.  max_partitions_per_topic sizes the LDS as in verify: a hint that
+ * is not positive or lies over the limit asks for the limit; a topic within the limit but over the hint is LA_ESHAPE from la_sync
+ * and passed through.  Offsets that leave [0, N] are LA_ESHAPE: nothing is read through them and nothing at all is written for
+ * that topic.  LA_EINVAL from la_sync (a status bit of this call's own), the topic passed through: a duplicate id in a topic's
+ * input segment; an output id that is no input id of the topic, or appears twice.  T == 0 and N == 0 are valid (summary zeros).
+ * At most one kernel launch (la_last_launches) behind the memset of the summary; no scratch and no allocation, so the call can be
+ * captured into a graph and the results kept for la_group_last_by_member stay valid.  Buffer contract as everywhere in this
+ * header: element alignment only, no write outside [0, N) / [0, T) / [0, 4), inputs never written.
+ * The call runs on shard 0 of the context (buffers and stream on that shard's device, la_sync reports the errors); a form with a
+ * shard argument is not part of this ABI yet.
+ * struct_size: sizeof(la_sticky_args) of the caller's header; less than this library's is LA_EINVAL.  reserved must be 0. */
+typedef struct la_sticky_args {
+    int32_t struct_size;           /* sizeof(la_sticky_args) of the caller's header */
+    int32_t reserved;              /* 0 */
+    const int32_t *d_prev_owner;   /* [N] previous owner, in today's ranks, of the partition at each position of d_out_partition: *
+                                    * what la_assignment_moves_device / la_cooperative_adjust_device write as d_prev_owner        */
+    int32_t *d_sticky_partition;   /* [N] required when N > 0 */
+    int64_t *d_topic_kept;         /* [T] or NULL */
+    int64_t *d_topic_saved;        /* [T] or NULL */
+    int64_t *d_summary;            /* [4] or NULL */
+} la_sticky_args;
+int la_sticky_ties_device(la_ctx *ctx, const la_device_batch *batch, const la_sticky_args *args, void *stream);
 
 #ifdef __cplusplus
 }

@@ -79,6 +79,7 @@ EXPORTED_SYMBOLS = (
     "la_cooperative_adjust_device",
     "la_cooperative_round_device", "la_cooperative_round",
     "la_assign_batch_cooperative",
+    "la_sticky_ties_device",
 )
 
 _i64p = ctypes.POINTER(ctypes.c_int64)
@@ -158,6 +159,15 @@ class CoopArgs(ctypes.Structure):
         ("d_prev_owner", ctypes.c_void_p), ("d_coop_member_rank", ctypes.c_void_p),
         ("d_member_kept", ctypes.c_void_p), ("d_member_fresh", ctypes.c_void_p), ("d_member_pending", ctypes.c_void_p),
         ("d_member_release", ctypes.c_void_p), ("d_topic_withheld", ctypes.c_void_p), ("d_summary", ctypes.c_void_p),
+    ]
+
+
+class StickyArgs(ctypes.Structure):
+    """struct la_sticky_args (device addresses as ints, None / 0 = NULL; struct_size is filled in by sticky_ties_device)"""
+    _fields_ = [
+        ("struct_size", ctypes.c_int32), ("reserved", ctypes.c_int32),
+        ("d_prev_owner", ctypes.c_void_p), ("d_sticky_partition", ctypes.c_void_p),
+        ("d_topic_kept", ctypes.c_void_p), ("d_topic_saved", ctypes.c_void_p), ("d_summary", ctypes.c_void_p),
     ]
 
 
@@ -378,6 +388,13 @@ def load() -> ctypes.CDLL:
     if hasattr(L, "la_assign_batch_cooperative"):
         L.la_assign_batch_cooperative.restype = ctypes.c_int
         L.la_assign_batch_cooperative.argtypes = [ctypes.c_void_p, ctypes.POINTER(AssignCoopArgs)]
+    if hasattr(L, "la_sticky_ties_device"):
+        L.la_sticky_ties_device.restype = ctypes.c_int
+        L.la_sticky_ties_device.argtypes = [ctypes.c_void_p, ctypes.POINTER(DeviceBatch), ctypes.POINTER(StickyArgs), ctypes.c_void_p]
+    if hasattr(L, "la_sticky_ties_device_on"):
+        L.la_sticky_ties_device_on.restype = ctypes.c_int
+        L.la_sticky_ties_device_on.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(DeviceBatch), ctypes.POINTER(StickyArgs),
+                                               ctypes.c_void_p]
     _lib = L
     return L
 
@@ -851,6 +868,25 @@ class Context:
         if not args.struct_size:
             args.struct_size = ctypes.sizeof(CoopArgs)
         self._check(fn(self._h, ctypes.byref(args), ctypes.c_void_p(stream)))
+
+    def sticky_ties_device(self, batch: DeviceBatch, args: StickyArgs, stream: int = 0, shard: int = 0) -> None:
+        """la_sticky_ties_device: the assignment `batch` points at (the struct an assign call took, inputs and results) with the
+        partitions of every run of equal lag re-matched to their previous owners, args.d_prev_owner (int32[N]: what
+        assignment_moves_device / cooperative_adjust_device write) -- args.d_sticky_partition (int32[N]) takes the place of
+        batch.d_out_partition, the ranks and totals stay as they are; d_topic_kept / d_topic_saved (int64[T]) and d_summary
+        (int64[4]: kept before, kept after, topics changed, topics passed through) may be left out.  Enqueued on `stream`, at most
+        one kernel; sync() reports duplicate or foreign ids (LA_EINVAL), a topic over its hint and offsets that leave the arrays
+        (LA_ESHAPE).  A topic of more than VERIFY_MAX_PARTITIONS partitions is passed through.  The C ABI has the call on shard 0
+        only: another shard needs a library that exports la_sticky_ties_device_on.  sharding.sticky_ties_numpy is the same on
+        the host."""
+        name = "la_sticky_ties_device" if not shard else "la_sticky_ties_device_on"
+        fn = getattr(self._lib, name, None)
+        if fn is None:
+            raise LagAssignError(LA_EINVAL, "this liblagassign.so has no %s" % name)
+        if not args.struct_size:
+            args.struct_size = ctypes.sizeof(StickyArgs)
+        head = (self._h,) if not shard else (self._h, int(shard))
+        self._check(fn(*head, ctypes.byref(batch) if batch is not None else None, ctypes.byref(args), ctypes.c_void_p(stream)))
 
     def cooperative_round_device(self, args: CoopRoundArgs, stream: int = 0) -> None:
         """la_cooperative_round_device (shard 0 of the context): cooperative_adjust_device on args.adjust -- every one of its

@@ -1116,6 +1116,54 @@ LA_API int la_verify_assignment_device_on(la_ctx* ctx, int shard, const la_devic
     });
 }
 
+// Sticky ties (la_sticky.hip), on shard 0.  Owns no scratch: everything lives in the workgroups' LDS and the caller's outputs, so
+// the call can be captured and the results kept for la_group_last_by_member stay as they are.
+LA_API int la_sticky_ties_device(la_ctx* ctx, const la_device_batch* batch, const la_sticky_args* args, void* stream) {
+    return shard_entry<true>(ctx, 0, "exception in la_sticky_ties_device", [&](Shard& sh) -> int {
+        if (!batch) return fail(ctx, LA_EINVAL, "batch is NULL");
+        if (!args) return fail(ctx, LA_EINVAL, "args is NULL");
+        if (args->struct_size < (int32_t)sizeof(la_sticky_args))
+            return fail(ctx, LA_EINVAL, "la_sticky_args.struct_size is %d, this library takes %d and above", (int)args->struct_size, (int)sizeof(la_sticky_args));
+        const la_device_batch& b = *batch;
+        const la_sticky_args& g = *args;
+        if (g.reserved != 0) return fail(ctx, LA_EINVAL, "la_sticky_args.reserved must be 0");
+        if (b.n_topics < 0 || b.n_partitions < 0) return fail(ctx, LA_EINVAL, "negative size");
+        if (b.flags & LA_FLAG_WIRE_OUT)
+            return fail(ctx, LA_EINVAL, "LA_FLAG_WIRE_OUT: unpack the results with la_unpack_results_on before re-matching them");
+        if (b.n_topics == 0 && b.n_partitions != 0) return fail(ctx, LA_EINVAL, "partitions without topics");
+        if (b.n_topics > 0 && !b.d_part_off) return fail(ctx, LA_EINVAL, "null offsets");
+        if (b.n_partitions > 0 && (!b.d_out_partition || !b.d_out_member_rank)) return fail(ctx, LA_EINVAL, "null results");
+        if (b.n_partitions > 0 && (!b.d_partition_id || (!b.d_lag && (!b.d_end_off || !b.d_committed_off))))
+            return fail(ctx, LA_EINVAL, "null per-partition input");
+        if (!b.d_lag && b.reset_mode != LA_RESET_LATEST && !b.d_begin_off && b.n_partitions > 0)
+            return fail(ctx, LA_EINVAL, "begin_off is required unless reset_mode is LA_RESET_LATEST");
+        if (b.n_partitions > 0 && !g.d_prev_owner) return fail(ctx, LA_EINVAL, "d_prev_owner is NULL");
+        if (b.n_partitions > 0 && !g.d_sticky_partition) return fail(ctx, LA_EINVAL, "d_sticky_partition is NULL");
+        if (b.n_partitions > 0 && g.d_sticky_partition == b.d_out_partition)
+            return fail(ctx, LA_EINVAL, "d_sticky_partition must not be d_out_partition: the call does not work in place");
+        la::StickyCall c{};
+        c.n_topics = b.n_topics;
+        c.reset_latest = b.reset_mode == LA_RESET_LATEST ? 1 : 0;
+        c.n_partitions = b.n_partitions;
+        c.max_partitions_per_topic = b.max_partitions_per_topic;
+        c.part_off = b.d_part_off;
+        c.pid = b.d_partition_id;
+        c.begin = b.d_begin_off;
+        c.end = b.d_end_off;
+        c.committed = b.d_committed_off;
+        c.lag = b.d_lag;
+        c.out_pid = b.d_out_partition;
+        c.out_rank = b.d_out_member_rank;
+        c.prev_owner = g.d_prev_owner;
+        c.sticky = g.d_sticky_partition;
+        c.topic_kept = g.d_topic_kept;
+        c.topic_saved = g.d_topic_saved;
+        c.summary = g.d_summary;
+        hipError_t e = la::sticky_ties_launch(c, sh.lanes[0].d_status, (hipStream_t)stream);
+        return e != hipSuccess ? hip_fail(ctx, e, "sticky_ties: %s") : LA_OK;
+    });
+}
+
 // What la_cooperative_adjust_device and the two round calls check of a la_coop_args, and the validated call.  need_output: the
 // eight outputs are all a call has (the round calls have the lists beside them).
 static int coop_call_of(la_ctx* ctx, const la_coop_args& g, bool need_output, la::CoopCall* out) {

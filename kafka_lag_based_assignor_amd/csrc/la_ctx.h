@@ -306,6 +306,8 @@ inline int status_error(la_ctx* ctx, uint32_t st) {
         return fail(ctx, LA_EINVAL, "la_assignment_moves_device: a duplicate partition id inside a topic, a current id without a previous one (one layout), or a rank or d_prev_topic entry out of range");
     if (st & la::kStatusCoop)
         return fail(ctx, LA_EINVAL, "la_cooperative_adjust_device: a target rank outside [-1, n_members), an owned topic outside [-1, n_topics), or a (topic, partition id) claimed twice");
+    if (st & la::kStatusSticky)
+        return fail(ctx, LA_EINVAL, "la_sticky_ties_device: a duplicate partition id in a topic's input segment, or an output id that is no input id of its topic or appears twice");
     return fail(ctx, LA_ESHAPE, "a topic exceeds the batch's shape hint, or offsets do not ascend inside their arrays");
 }
 

@@ -42,7 +42,18 @@ __device__ __forceinline__ int64_t partition_lag(int64_t begin, int64_t end, int
     return d > 0 ? d : 0;
 }
 
-constexpr uint64_t kLagKeyFlip = 0x7FFFFFFFFFFFFFFFull;   // signed-desc -> unsigned-asc
+// The same of input entry i of a validated call (VerifyCall, StickyCall: lag non-null = precomputed lags, offsets ignored),
+// as the assign call computes it; `begin` only where it is read
+template <typename Call>
+__device__ __forceinline__ int64_t lag_of(const Call& c, int64_t i) {
+    if (c.lag) return c.lag[i];
+    const int64_t end = c.end[i], committed = c.committed[i];
+    int64_t begin = 0;
+    if (committed < 0 && !c.reset_latest && c.begin) begin = c.begin[i];
+    return partition_lag(begin, end, committed, c.reset_latest != 0);
+}
+
+constexpr uint64_t kLagKeyFlip =0x7FFFFFFFFFFFFFFFull;   // signed-desc -> unsigned-asc
 constexpr uint64_t kTotalBias = 0x8000000000000000ull;    // signed-asc  -> unsigned-asc
 constexpr uint32_t kPidBias = 0x80000000u;
 

@@ -1,4 +1,4 @@
-// la_join.h -- the per-topic hash join on a partition id, shared by la_moves.hip, la_moves_layouts.hip and la_verify.hip.
+// la_join.h -- the per-topic hash join on a partition id, shared by la_moves.hip, la_moves_layouts.hip, la_verify.hip and la_sticky.hip.
 //
 // An open-addressing table keyed by the id:
 //

@@ -32,9 +32,12 @@ constexpr uint32_t kStatusMoves = 256u;    // la_assignment_moves_device: a dupl
 constexpr uint32_t kStatusCoop = 2 * kStatusMoves;      // la_cooperative_adjust_device: a target rank outside [-1, M), an owned
                                                         // topic outside [-1, T), or a (topic, partition id) claimed twice
 
+constexpr uint32_t kStatusSticky = 2 * kStatusCoop;     // la_sticky_ties_device: a duplicate id in a topic's input segment, or an
+                                                        // output id that is no input id of its topic or appears twice
+
 // Every status bit is listed here: a new one that repeats a value, or is not a single bit, does not compile.
-constexpr uint32_t kStatusBits[] = {kStatusShape, kStatusUnsorted, kStatusInternal, kStatusOrder,  kStatusWire,
-                                    kStatusSparse, kStatusBounds,  kStatusLoads,    kStatusMoves,  kStatusCoop};
+constexpr uint32_t kStatusBits[] = {kStatusShape, kStatusUnsorted, kStatusInternal, kStatusOrder,  kStatusWire,  kStatusSparse,
+                                    kStatusBounds, kStatusLoads,   kStatusMoves,    kStatusCoop,   kStatusSticky};
 constexpr bool status_bits_distinct() {
     uint32_t seen = 0;
     for (uint32_t b : kStatusBits) {
@@ -365,5 +368,24 @@ struct VerifyCall {             // la_device_batch (lagassign.h) as la_verify_as
 hipError_t verify_assignment_launch(VerifyScratch* large, const VerifyCall& c, const int64_t* h_part_off,
                                     const int64_t* h_cons_off, uint32_t* status, hipStream_t stream);
 void verify_scratch_release(VerifyScratch& s);
+
+// ---- sticky ties: the previous owner decides among partitions of equal lag (la_sticky.hip) ------------------------------------
+// One workgroup re-matches a topic in LDS, up to kVerifyMaxPartitions partitions as the verify call: the id join, the topic's
+// lags, both rank arrays and two arrays of sort keys -- 136 KiB at the limit.  A larger topic is passed through.
+struct StickyCall {             // la_device_batch + la_sticky_args (lagassign.h) as la_sticky_ties_device reads them, validated
+    int32_t n_topics, reset_latest;
+    int64_t n_partitions, max_partitions_per_topic;
+    const int64_t* part_off;
+    const int32_t* pid;
+    const int64_t *begin, *end, *committed, *lag;      // lag non-null: precomputed lags, offsets ignored; begin may be null
+    const int32_t *out_pid, *out_rank;                 // the assign call's results
+    const int32_t* prev_owner;
+    int32_t* sticky;            // [N]
+    int64_t *topic_kept, *topic_saved;                 // [T] or null
+    int64_t* summary;           // [4] or null
+};
+
+// Zeroes the summary on `stream`, then at most ONE launch.  Sets kStatusSticky / kStatusShape / kStatusInternal.
+hipError_t sticky_ties_launch(const StickyCall& c, uint32_t* status, hipStream_t stream);
 
 }  // namespace la

@@ -1,5 +1,5 @@
 // la_launch.h -- how the library launches a kernel and keeps its scratch: the launch counter, the per-device opt-in to large
-// dynamic LDS, the resident-grid launcher of the report kernels (la_loads / la_moves / la_moves_layouts / la_verify / la_coop),
+// dynamic LDS, the resident-grid launcher of the report kernels (la_loads / la_moves / la_moves_layouts / la_verify / la_coop / la_sticky),
 // their growable device buffer and staged list, and the launchers' host arithmetic.  Host code only: no kernel lives here.
 #pragma once
 #include <hip/hip_runtime.h>

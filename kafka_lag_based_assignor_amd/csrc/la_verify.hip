@@ -116,15 +116,6 @@ static_assert((kVerifyMaxPartitions & (kVerifyMaxPartitions - 1)) == 0, "2 x the
 static_assert(kVerifyMaxConsumers <= kVerifyMaxPartitions, "before | tot_last fit the largest table");
 static_assert(kVerifyMaxLdsBytes <= 160 * 1024, "one workgroup's LDS on gfx950");
 
-// computePartitionLag (Main.java:376-404) of input entry i, as the assign call computes it; `begin` only where it is read
-__device__ __forceinline__ int64_t lag_of(const VerifyCall& c, int64_t i) {
-    if (c.lag) return c.lag[i];
-    const int64_t end = c.end[i], committed = c.committed[i];
-    int64_t begin = 0;
-    if (committed < 0 && !c.reset_latest && c.begin) begin = c.begin[i];
-    return partition_lag(begin, end, committed, c.reset_latest != 0);
-}
-
 struct VerifyTally {            // thread 0: what this workgroup's topics add to the summary
     uint64_t failed = 0, unchecked = 0;
     uint64_t first_failed = ~0ull, first_unchecked = ~0ull;

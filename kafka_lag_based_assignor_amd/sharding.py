@@ -422,6 +422,99 @@ def verify_assignment_numpy(part_off, partition_id, cons_off, cons_rank, out_par
     return verdict, np.array([int(failed.sum()), int(unchecked.sum()), first(failed), first(unchecked)], dtype=np.int64)
 
 
+STICKY_MAX_PARTITIONS = 4096      # topics beyond it are passed through by la_sticky_ties_device (kVerifyMaxPartitions of csrc/la_kernels.h)
+
+
+def sticky_ties_numpy(part_off, partition_id, lag, out_partition, out_member_rank, prev_owner, *,
+                      max_partitions: int = STICKY_MAX_PARTITIONS, strict: bool = True):
+    """la_sticky_ties_device restated on the host -> (sticky_partition int32[N], topic_kept int64[T], topic_saved int64[T],
+    summary int64[4]).  Per topic, lag_i is the lag of the input partition whose id is out_partition[i] (a join on the id); a run
+    is a maximal range of consecutive positions of equal lag_i; c_i = out_member_rank[i], q_i = prev_owner[i].  Inside one run:
+      1  for every c >= 0, S_c = the run's positions with c_i == c, ascending
+      2  for every c >= 0, W_c = the run's positions with q_i == c, ascending
+      3  for k < min(|S_c|, |W_c|) the partition at W_c[k] goes to S_c[k]
+      4  the partitions not placed by 3 go, in ascending position, to the positions not filled by 3, in ascending position
+      5  sticky_partition[dest] = out_partition[src]
+    A position is kept when the partition placed there has q >= 0 and q equals the position's c.  topic_kept counts them after,
+    topic_saved = after - before, summary = kept before, kept after, topics whose order changed, topics passed through.  A topic
+    of more than max_partitions partitions is passed through: copied, saved 0, kept the count before.  ValueError for what the
+    device reports as LA_EINVAL -- a duplicate id in a topic's input segment, an output id that is no input id of the topic or
+    appears twice -- unless strict is False: such a topic is then passed through as the device passes it.  Offsets that leave
+    the arrays raise ValueError.  Plain loops, rule by rule: the yardstick of tests/test_sticky_gpu.py, not a fast path."""
+    po = np.asarray(part_off, dtype=np.int64).ravel()
+    pid = np.asarray(partition_id, dtype=np.int32).ravel()
+    lag = np.asarray(lag, dtype=np.int64).ravel()
+    o_pid = np.asarray(out_partition, dtype=np.int32).ravel()
+    o_own = np.asarray(out_member_rank, dtype=np.int32).ravel()
+    o_prev = np.asarray(prev_owner, dtype=np.int32).ravel()
+    n, t_all = pid.size, po.size - 1
+    if t_all < 0 or not (lag.size == o_pid.size == o_own.size == o_prev.size == n):
+        raise ValueError("array sizes do not fit one layout")
+    sticky = o_pid.copy()
+    topic_kept = np.zeros(t_all, dtype=np.int64)
+    topic_saved = np.zeros(t_all, dtype=np.int64)
+    kept_before = changed = passed = 0
+    for t in range(t_all):
+        a, z = int(po[t]), int(po[t + 1])
+        if not 0 <= a <= z <= n:
+            raise ValueError("the offsets of topic %d leave the arrays" % t)
+        p = z - a
+        ids, oid = pid[a:z], o_pid[a:z]
+        c, q = [int(x) for x in o_own[a:z]], [int(x) for x in o_prev[a:z]]
+        before = sum(1 for i in range(p) if q[i] >= 0 and q[i] == c[i])
+        kept_before += before
+        topic_kept[t] = before
+        if p > max_partitions:
+            passed += 1
+            continue
+        by_id = np.argsort(ids, kind="stable")
+        sorted_ids = ids[by_id]
+        at = np.minimum(np.searchsorted(sorted_ids, oid), max(p - 1, 0))
+        problem = None
+        if np.unique(ids).size != p:
+            problem = "a partition id appears twice in the input segment of topic %d" % t
+        elif p and ((sorted_ids[at] != oid).any() or np.unique(oid).size != p):
+            problem = "an output id of topic %d is no input id of the topic, or appears twice" % t
+        if problem:
+            if strict:
+                raise ValueError(problem)
+            passed += 1
+            continue
+        l = [int(x) for x in lag[a:z][by_id[at]]] if p else []
+        src_of = list(range(p))                     # position -> the position its partition comes from
+        r0 = 0
+        while r0 < p:
+            r1 = r0 + 1
+            while r1 < p and l[r1] == l[r0]:
+                r1 += 1
+            s_of, w_of = {}, {}
+            for i in range(r0, r1):
+                if c[i] >= 0:
+                    s_of.setdefault(c[i], []).append(i)             # 1
+                if q[i] >= 0:
+                    w_of.setdefault(q[i], []).append(i)             # 2
+            placed, filled = set(), set()
+            for member, s in s_of.items():
+                w = w_of.get(member, [])
+                for k in range(min(len(s), len(w))):                # 3
+                    src_of[s[k]] = w[k]
+                    placed.add(w[k])
+                    filled.add(s[k])
+            rest = [i for i in range(r0, r1) if i not in placed]
+            holes = [i for i in range(r0, r1) if i not in filled]
+            for src, dst in zip(rest, holes):                       # 4
+                src_of[dst] = src
+            r0 = r1
+        for d in range(p):
+            sticky[a + d] = oid[src_of[d]]                          # 5
+        after = sum(1 for d in range(p) if q[src_of[d]] >= 0 and q[src_of[d]] == c[d])
+        topic_kept[t] = after
+        topic_saved[t] = after - before
+        changed += 1 if any(src_of[d] != d for d in range(p)) else 0
+    summary = np.array([kept_before, int(topic_kept.sum()), changed, passed], dtype=np.int64)
+    return sticky, topic_kept, topic_saved, summary
+
+
 def group_by_member_numpy(part_off, out_partition, member_rank, n_members: int):
     """la_group_by_member restated on the host -> (member_off int64[M+1], grouped_topic int32[N], grouped_partition int32[N]):
     the entries stably grouped by rank, those with rank -1 first (before member_off[0]).  The body of owned_after_round, and the
