@@ -1,7 +1,7 @@
 // la_block.hip -- the block path: one workgroup per topic, for topics beyond a wave tile (more than 1 024
 // partitions or more than 64 consumers) up to 8 192 partitions x 2 048 consumers, or 16 384 x 1 024.  All such
 // topics of a batch run side by side (one launch per size class over a topic list), where the large path
-// (la_large.hip) would take them one after another through a dozen device-wide kernels each.
+// (la_radix.hip, la_large.hip) would take them one after another through a dozen device-wide kernels each.
 //
 // Per topic:
 //   1. loads, lag fused in (computePartitionLag, Main.java:376-404), straight into the sort's registers;

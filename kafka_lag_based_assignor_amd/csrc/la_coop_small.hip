@@ -308,7 +308,7 @@ __global__ __launch_bounds__(NT) void coop_round_small_kernel(std::conditional_t
                                              misc + kWsum, misc + kTurn, l, l + E, l + 2 * E, l + 3 * E, l + 4 * E,
                                              reinterpret_cast<uint32_t*>(l + 5 * E), reinterpret_cast<uint32_t*>(l + 6 * E));
     if constexpr (kFinish) {
-        // The call ends here, in the order of the finishing form of group_small_kernel (la_large.hip): every thread releases
+        // The call ends here, in the order of the finishing form of group_small_kernel (la_group.hip): every thread releases
         // what it stored into the host's memory, the workgroup meets, ONE thread stores `done | status` where the calling thread
         // spins.  The status is what the assignment kernels left in the lane's device word plus this round's own bits (kept in
         // LDS: the list builder leaves the misc words below kWsum alone but for its turn counter); the device word goes back to

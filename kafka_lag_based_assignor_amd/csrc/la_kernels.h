@@ -184,7 +184,7 @@ inline int block_class(int64_t p, int64_t c) {
 }
 hipError_t block_launch(BlockArgs a, int cls, hipStream_t stream);
 
-// ---- large-topic path (device-wide radix sort + one-workgroup greedy) ---------------------
+// ---- large-topic path (device-wide radix sort, la_radix.hip + one-workgroup greedy, la_large.hip) ---------------------
 // LA_FLAG_PROFILE: HIP events around the phases of the first large topic of a call (la_last_phase_times)
 struct LargeProfile {
     hipEvent_t ev[4] = {};      // before the keys kernel, after the plan, after the last pass, after the greedy
@@ -234,7 +234,8 @@ struct LargeArgs {
                                 // the rounds' lags and results (rounds_io, la_large.hip)
 };
 
-// Once per device at context creation (synchronous): checks the hardware property the radix sort's atomic ranking relies on.
+// Once per device at context creation (synchronous): checks the hardware property the radix sort's atomic ranking relies on
+// (la_radix.hip, as large_atomic_rank_supported; the launchers below are la_large.hip's).
 hipError_t large_init_device();
 int large_atomic_rank_supported();      // of the current device: 1 = ranks come from returning LDS atomics, 0 = match form
 hipError_t large_topic_launch(LargeScratch& scratch, const LargeArgs& a, bool argmin, hipStream_t stream);
@@ -252,6 +253,7 @@ void large_scratch_release(LargeScratch& scratch);
 // passes, active key passes, 1 if the sort went keys first, 1 if it had to be redone in full.
 hipError_t large_profile_read(LargeScratch& scratch, float* ms, int* passes, int64_t* n);
 
+// ---- grouping by member (la_group.hip) ------------------------------------------------------------------------------------
 // Stable grouping of the n assignment entries by member rank (see la_group_by_member in lagassign.h).
 hipError_t group_by_member_launch(LargeScratch& scratch, int64_t n, int32_t n_members, int64_t n_topics,
                                   const int64_t* part_off, const int32_t* out_partition, const int32_t* member_rank,

@@ -1,6 +1,7 @@
 // la_launch.h -- how the library launches a kernel and keeps its scratch: the launch counter, the per-device opt-in to large
 // dynamic LDS, the resident-grid launcher of the report kernels (la_loads / la_moves / la_moves_layouts / la_verify / la_coop / la_sticky),
-// their growable device buffer and staged list, and the launchers' host arithmetic.  Host code only: no kernel lives here.
+// their growable device buffer and staged list, the launchers' host arithmetic, and the read-out of a lab build's counters
+// (la_radix / la_large / la_group).  Host code only: no kernel lives here.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -117,6 +118,7 @@ hipError_t launch_resident_lds(int64_t want, int threads, size_t lds, hipStream_
 // a x b and a + b in size_t; false: the result does not fit
 inline bool mul_ok(size_t a, size_t b, size_t* out) { return !__builtin_mul_overflow(a, b, out); }
 inline bool add_ok(size_t a, size_t b, size_t* out) { return !__builtin_add_overflow(a, b, out); }
+inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 inline int ceil_log2(int64_t x) {                  // smallest b with 2^b >= x, at least 1
     int b = 1;
@@ -197,5 +199,18 @@ struct StagedList {
         *this = StagedList{};
     }
 };
+
+// ---- lab builds: the kernels' instrumentation arrays (tools/*_probe.py find the exports with hasattr) -------------------------
+// Reads a __device__ array of counters into `out` and, with `reset`, zeroes it.
+template <typename T>
+int debug_read(const T& symbol, unsigned long long* out, int reset) {
+    hipError_t e = hipMemcpyFromSymbol(out, HIP_SYMBOL(symbol), sizeof(T));
+    if (e == hipSuccess && reset) {
+        const T zero{};
+        e = hipMemcpyToSymbol(HIP_SYMBOL(symbol), &zero, sizeof(T));
+    }
+    return e == hipSuccess ? 0 : -3;
+}
+#define LA_DEBUG_EXPORT extern "C" __attribute__((visibility("default"))) int
 
 }  // namespace la

@@ -333,6 +333,68 @@ __device__ __forceinline__ void bitonic_sort_tile_p64(P64 (&rec)[E]) {
     else merge_p64<L, E, 2, false, VO>(rec);
 }
 
+// ---- the same network over a whole workgroup ---------------------------------------------------------------------------
+// Element i = tid*EC + r.  Strides inside a wavefront run through the instruction-level networks above (registers, DPP);
+// strides across wavefronts go through LDS: 10 exchanges per sort of 8 192 records.  Used by the large path's greedy rounds
+// (all bins, or the samples of the sample sort; la_large.hip) and by the tie repair of a keys-first sort (la_radix.hip).
+template <int EC>
+__device__ __forceinline__ void dpp_fence(P64 (&rec)[EC]) {
+    // the next instruction-level block reads these registers through DPP: 2 wait states after their last
+    // (compiler-generated) write
+#pragma unroll
+    for (int r = 0; r < EC; ++r) asm volatile("s_nop 1" : "+v"(rec[r].lo), "+v"(rec[r].hi));
+}
+
+// LDS layout is register-major (slot r of thread t at r * blockDim + t): consecutive lanes touch consecutive
+// 8-byte words, where element order (t * EC + r) would put a 64-byte stride between lanes (16-way conflicts).
+// One barrier per step: consecutive steps ALTERNATE between two exchange buffers (ExchangeBufs::next), so a thread
+// that runs ahead writes the other buffer while slower threads still read this one; by the time a buffer comes
+// round again every thread has passed the barrier of the step in between, i.e. has finished reading it.
+// (Base + offset, not an array of two pointers: indexed dynamically the array lands in scratch memory, the pointers
+// come back from there as generic ones, and every LDS access of the exchange turns into a flat_load / flat_store.)
+struct ExchangeBufs {
+    uint64_t* base;
+    int stride;                                     // words between the two buffers
+    int at = 0;
+    __device__ __forceinline__ uint64_t* next() { at ^= 1; return base + (at ? stride : 0); }
+};
+
+template <int EC>
+__device__ __forceinline__ void cross_wave_step(P64 (&rec)[EC], ExchangeBufs& xb, int tid, int mask, int min_bit) {
+    const int nt = blockDim.x;
+    uint64_t* s_bin = xb.next();
+#pragma unroll
+    for (int r = 0; r < EC; ++r) s_bin[r * nt + tid] = p64_value(rec[r]);
+    lds_barrier();
+#pragma unroll
+    for (int r = 0; r < EC; ++r) {
+        const int i = tid * EC + r;
+        const int pi = i ^ mask;                                     // partner element: thread pi / EC, register pi % EC
+        const uint64_t o = s_bin[(pi % EC) * nt + pi / EC], x = p64_value(rec[r]);
+        const bool keep_min = (i & min_bit) == 0;
+        const uint64_t lo = o < x ? o : x, hi = o < x ? x : o;
+        rec[r] = p64_from(keep_min ? lo : hi);
+    }
+}
+
+// The n = EC * blockDim.x records of a workgroup ascending (n a power of two; a single wavefront needs no LDS): every
+// wavefront sorts its 64 * EC records, then merges across wavefronts.  buf: two exchange buffers of n words each.  The last
+// step's reads of buf may still be in flight in slower threads on return: the caller puts a barrier before anything else
+// goes over it.
+template <int EC>
+__device__ __forceinline__ void workgroup_sort_p64(P64 (&rec)[EC], uint64_t* buf, int n, int tid) {
+    constexpr int kSpan = 64 * EC;                       // elements of one wavefront
+    dpp_fence<EC>(rec);
+    bitonic_sort_tile_p64<64, EC>(rec);
+    ExchangeBufs xb{buf, n};
+    for (int K = 2 * kSpan; K <= n; K <<= 1) {
+        cross_wave_step<EC>(rec, xb, tid, K - 1, K >> 1);                        // mirror: i <-> i ^ (K-1)
+        for (int j = K >> 2; j >= kSpan; j >>= 1) cross_wave_step<EC>(rec, xb, tid, j, j);
+        dpp_fence<EC>(rec);
+        clean_p64<64, EC, kSpan / 2, false>(rec);                                 // i <-> i ^ j, j < span
+    }
+}
+
 // ---- bins that are in order already ------------------------------------------------------------------------------
 // Between greedy rounds the bins are (ascending totals) + (descending lags): often still ascending (few consumers, a Zipf
 // tail, equal lags).  `gl` = lane inside its group, one record per lane; lanes beyond the live bins hold equal all-ones

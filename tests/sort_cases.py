@@ -1,4 +1,4 @@
-"""The large path's radix sort (csrc/la_large.hip) at its tile, digit, id-descent, tie-run and bound edges.  Not a test module:
+"""The large path's radix sort (csrc/la_radix.hip) at its tile, digit, id-descent, tie-run and bound edges.  Not a test module:
 test_sort_cases_cpu.py (the table holds what it says, proved on each case's own data) and test_large_sort_gpu.py (every case
 through the C ABI against independent references) import it by name, so both run the same cases.
 

@@ -367,7 +367,7 @@ print("ok")
         assert out.returncode == 0 and "ok" in out.stdout, (env_add, out.stdout[-1500:], out.stderr[-1500:])
 
 
-# ---- member lists of a mid-size rebalance: the two-launch counting sort (la_group_small.h, group_mid_*) ---------------------------
+# ---- member lists of a mid-size rebalance: the two-launch counting sort (la_group.hip, group_mid_*) ---------------------------
 @pytest.mark.parametrize("n_topics,max_p,members", [(300, 256, 32), (40, 3000, 5), (5000, 9, 3), (2, 70000, 510), (700, 700, 509),
                                                    (1, 2561, 1), (9, 4096, 64), (60000, 4, 2), (3, 100000, 511)])
 def test_member_lists_of_a_mid_size_rebalance(ctx, n_topics, max_p, members):

@@ -18,7 +18,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "kafka_lag_based_assignor_amd", "csrc")
-UNITS = ["la_block.hip", "la_large.hip", "la_wave_tile_l32.hip", "la_wave_tile_l8.hip"]
+UNITS = ["la_block.hip", "la_large.hip", "la_radix.hip", "la_group.hip", "la_wave_tile_l32.hip", "la_wave_tile_l8.hip"]
 
 
 def _hipcc():

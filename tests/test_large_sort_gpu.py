@@ -1,4 +1,4 @@
-"""The large path's device-wide radix sort (csrc/la_large.hip) at its tile, digit, id-descent, tie-run and bound edges: every
+"""The large path's device-wide radix sort (csrc/la_radix.hip) at its tile, digit, id-descent, tie-run and bound edges: every
 case of sort_cases.py through the C ABI -- alone, side by side with a second large topic of another tile count (the launches
 over items) and with the four-kernel passes -- exactly against the comparator's order and the round-form oracle, and the
 decisions the sort reports (la_last_phase_times, la_last_launches) against the model written from the source.  That the cases

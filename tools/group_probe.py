@@ -36,7 +36,7 @@ def main():
             call()
         e1.record()
         ctx.sync(stream)
-        if hasattr(ctx._lib, "la_debug_group_clocks"):      # lab build (-DLA_GROUP_CLOCKS on la_large): phase times of the one-workgroup form
+        if hasattr(ctx._lib, "la_debug_group_clocks"):      # lab build (-DLA_GROUP_CLOCKS on la_group): phase times of the one-workgroup form
             import ctypes
             clk = (ctypes.c_ulonglong * 12)()
             ctx._lib.la_debug_group_clocks(clk, 1)

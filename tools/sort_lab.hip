@@ -1,32 +1,22 @@
-// tools/sort_lab.hip -- developer check (NOT product): the multi-wavefront 64-bit bin sort of la_large.hip in isolation.
+// tools/sort_lab.hip -- developer check (NOT product): the multi-wavefront 64-bit bin sort (workgroup_sort_p64, la_sort64.h) in isolation.
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
 #include <algorithm>
-#include "../kafka_lag_based_assignor_amd/csrc/la_large.hip"
+#include "../kafka_lag_based_assignor_amd/csrc/la_sort64.h"
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("%s: %s\n", #x, hipGetErrorString(e_)); exit(1); } } while (0)
 namespace la { namespace {
 template <int EC>
-__global__ __launch_bounds__(1024) void sort_test_kernel(const uint64_t* in, uint64_t* out, int stop_after) {
+__global__ __launch_bounds__(1024) void sort_test_kernel(const uint64_t* in, uint64_t* out) {
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
     uint64_t* s_bin = reinterpret_cast<uint64_t*>(smem);
     const int tid = threadIdx.x;
     const int n = EC * blockDim.x;
-    constexpr int kSpan = 64 * EC;
     P64 rec[EC];
 #pragma unroll
     for (int r = 0; r < EC; ++r) rec[r] = p64_from(in[tid * EC + r]);
-    dpp_fence<EC>(rec);
-    bitonic_sort_tile_p64<64, EC>(rec);
-    int step = 0;
-    for (int K = 2 * kSpan; K <= n && step < stop_after; K <<= 1) {
-        cross_wave_step<EC>(rec, s_bin, tid, K - 1, K >> 1);
-        for (int j = K >> 2; j >= kSpan; j >>= 1) cross_wave_step<EC>(rec, s_bin, tid, j, j);
-        dpp_fence<EC>(rec);
-        clean_p64<64, EC, kSpan / 2, false>(rec);
-        ++step;
-    }
+    workgroup_sort_p64<EC>(rec, s_bin, n, tid);
 #pragma unroll
     for (int r = 0; r < EC; ++r) out[tid * EC + r] = p64_value(rec[r]);
 }
@@ -45,7 +35,7 @@ void run(int threads, int kind) {
     CK(hipMalloc(&din, n * 8)); CK(hipMalloc(&dout, n * 8));
     CK(hipMemcpy(din, h.data(), n * 8, hipMemcpyHostToDevice));
     CK(hipFuncSetAttribute((const void*)la::sort_test_kernel<EC>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    hipLaunchKernelGGL((la::sort_test_kernel<EC>), dim3(1), dim3(threads), (size_t)n * 12, 0, din, dout, 100);
+    hipLaunchKernelGGL((la::sort_test_kernel<EC>), dim3(1), dim3(threads), (size_t)n * 16, 0, din, dout);
     CK(hipDeviceSynchronize());
     CK(hipMemcpy(got.data(), dout, n * 8, hipMemcpyDeviceToHost));
     int bad = 0, first = -1;
@@ -55,7 +45,7 @@ void run(int threads, int kind) {
     if (bad && n == 128 && kind == 1) {
         std::vector<uint64_t> g2 = got; std::sort(g2.begin(), g2.end());
         printf("  multiset preserved: %d\n", (int)(g2 == ref));
-        bool lo_ok = true; uint64_t mx = 0, mn = ~0ull;
+        uint64_t mx = 0, mn = ~0ull;
         for (int i = 0; i < 64; ++i) mx = std::max(mx, got[i]);
         for (int i = 64; i < 128; ++i) mn = std::min(mn, got[i]);
         printf("  max(lower half) <= min(upper half): %d\n", (int)(mx <= mn));
