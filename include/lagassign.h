@@ -39,6 +39,9 @@
  *                           returns -- every partition that changes hands between two live members withheld for this round
  *   la_sticky_ties_device   nothing in the reference, which orders partitions of equal lag by id: the same assignment with the
  *                           partitions of each run of equal lag re-matched to their previous owners
+ *   la_cooperative_round_sticky_device  nothing in the reference: la_cooperative_adjust_device, la_sticky_ties_device and
+ *                           la_cooperative_round_device on the sticky order, chained by hand until now, in one call
+ *   la_assign_batch_cooperative_sticky  nothing in the reference: la_assign_batch_cooperative with the round on the sticky order
  *   la_hint_next_call       nothing in the reference's arithmetic: what the marshalling loop of readTopicPartitionLags
  *                           (Main.java:344-356) knows for free -- the largest end offset and partition id it walked past
  *   la_last_phase_times     nothing: measurement hook (radix-sort phase against the HBM roofline)
@@ -267,6 +270,8 @@ const char *la_last_error(const la_ctx *ctx);
  *                la_cooperative_round_device / la_cooperative_round (that form and every member's list of it in one call);
  *                la_assign_batch_cooperative (a cooperative rebalance from host buffers in one call);
  *                la_sticky_ties_device (among partitions of equal lag the previous owner keeps its own);
+ *                la_cooperative_round_sticky_device (the cooperative round on the sticky order in one call);
+ *                la_assign_batch_cooperative_sticky (a cooperative rebalance on the sticky order from host buffers);
  *                a shim detects them by symbol lookup (dlsym / getattr) instead of by version */
 #define LA_VERSION 500
 int la_version(void);
@@ -976,6 +981,84 @@ typedef struct la_sticky_args {
     int64_t *d_summary;            /* [4] or NULL */
 } la_sticky_args;
 int la_sticky_ties_device(la_ctx *ctx, const la_device_batch *batch, const la_sticky_args *args, void *stream);
+
+/* The cooperative round WITH sticky ties in one call.  `batch` is the struct an assign call took, inputs and results, read
+ * exactly as la_sticky_ties_device reads it: the lag from d_lag, or from begin / end / committed with reset_mode; the hint rules
+ * of that call apply; LA_FLAG_WIRE_OUT is LA_EINVAL.  The TARGET comes from `batch`: n_topics, n_partitions, d_part_off,
+ * d_out_partition, d_out_member_rank -- the same five fields of round.adjust are not looked at, and neither are
+ * round.struct_size and round.flags.  Everything else of `round` (the owned lists, n_members, the eight adjust outputs, the
+ * three lists) is as for la_cooperative_round_device.
+ * DEFINITION: every output is, bit for bit, what this chain writes on one stream:
+ *   1  la_cooperative_adjust_device on the target, wanting only d_prev_owner;
+ *   2  la_sticky_ties_device(batch, {that d_prev_owner, d_sticky_partition, d_topic_kept, d_topic_saved, d_sticky_summary});
+ *   3  la_cooperative_round_device with d_sticky_partition in place of d_out_partition: the eight adjust outputs and the lists.
+ * So the round's outputs describe the STICKY order: d_prev_owner[i] is the previous owner of the partition at position i of
+ * d_sticky_partition, and the lists are the owned arrays of the next round as they lie.  d_out_member_rank and d_out_total_lag
+ * of the batch stay valid for the sticky order as they are.
+ * Errors are the union of the three calls' errors, reported by la_sync under the same conditions and with the same guarantees:
+ * a bad entry is never stored through, nothing is read through an offset, outputs of a failing call are unspecified but stay
+ * inside the arrays; a topic that step 2 passes through (a duplicate input id, a foreign or repeated output id, a topic over
+ * the hint or over 4096 partitions) keeps the reference's order.  T == 0, N == 0 and n_owned == 0 are valid; with n_owned == 0
+ * d_sticky_partition equals d_out_partition.  Buffer contract as everywhere in this header.  The call runs on shard 0.
+ * Two forms, the same results:
+ *   ONE WORKGROUP  N <= LA_COOP_STICKY_ENTRIES (2048), n_owned <= LA_COOP_STICKY_OWNED (2048), M <= LA_COOP_STICKY_MEMBERS
+ *                  (2046) and T <= LA_COOP_STICKY_TOPICS (2048), without LA_COOP_FORCE_TABLE.  EXACTLY ONE kernel launch
+ *                  (la_last_launches == 1): both joins, the re-matching, every counter and the lists live in that workgroup's
+ *                  LDS.  No memset, no allocation, no scratch: the call can be captured into a graph and the results kept for
+ *                  la_group_last_by_member stay valid.  A topic over the batch's hint is found by the kernel itself: LA_ESHAPE
+ *                  from la_sync, the topic passed through, as in step 2.
+ *   GENERAL        anything else: the chain above through the same launchers; la_last_launches is their sum.  The intermediate
+ *                  d_prev_owner (and the adjusted ranks when d_coop_member_rank is NULL) live in buffers of shard 0's own; these
+ *                  intermediates of the call's own and the (topic, id) table are grown before anything is enqueued (LA_ENOMEM
+ *                  from them leaves nothing enqueued; the grouping at the end may still grow its scratch behind the first two
+ *                  steps, as in la_cooperative_round_device).  What la_cooperative_round_device says
+ *                  of its general form holds: the call may allocate, must not be captured, and the cooperative calls of a shard
+ *                  must be ordered among themselves.
+ * struct_size: sizeof(la_coop_sticky_args) of the caller's header; less than this library's is LA_EINVAL.  flags:
+ * LA_COOP_FORCE_TABLE or 0, any other bit is LA_EINVAL.  round.adjust.reserved must be 0.  round.member_off NULL, or
+ * round.grouped_partition NULL with N > 0, is LA_EINVAL. */
+#define LA_COOP_STICKY_ENTRIES 2048
+#define LA_COOP_STICKY_OWNED 2048
+#define LA_COOP_STICKY_MEMBERS 2046
+#define LA_COOP_STICKY_TOPICS 2048
+typedef struct la_coop_sticky_args {
+    int32_t struct_size;            /* sizeof(la_coop_sticky_args) of the caller's header */
+    int32_t flags;                  /* LA_COOP_FORCE_TABLE or 0 */
+    la_coop_round_args round;       /* as for la_cooperative_round_device, but for the target (see above) */
+    int32_t *d_sticky_partition;    /* [N] required when N > 0; must not overlap an input */
+    int64_t *d_topic_kept;          /* [T] or NULL */
+    int64_t *d_topic_saved;         /* [T] or NULL */
+    int64_t *d_sticky_summary;      /* [4] or NULL */
+} la_coop_sticky_args;
+int la_cooperative_round_sticky_device(la_ctx *ctx, const la_device_batch *batch, const la_coop_sticky_args *args, void *stream);
+
+/* A COOPERATIVE rebalance on the STICKY order in one host call: la_assign_batch_cooperative with the round replaced by the
+ * sticky round above.  Every pointer is HOST memory.
+ *   coop             exactly as for la_assign_batch_cooperative: the rebalance's inputs, the owned lists, the outputs.
+ *                    coop.struct_size is not looked at; coop.flags is LA_COOP_FORCE_TABLE or 0, any other bit LA_EINVAL;
+ *                    coop.reserved must be 0.
+ *   out_partition, out_member_rank, out_total_lag (of coop)   describe the TARGET, in the reference's order, bit for bit what the
+ *                    assign call returns for these inputs.
+ *   sticky_partition, the eight adjust outputs and the three lists   describe the STICKY order: what
+ *                    la_cooperative_round_sticky_device writes for that target, these lags and these owned lists.
+ *   topic_kept, topic_saved, sticky_summary   as d_topic_kept / d_topic_saved / d_sticky_summary of that call.
+ * Every error condition of the assign call and of the sticky round applies; on any error the caller's outputs are left as they
+ * were.  A pending la_hint_next_call is consumed.  The call makes NO promise about la_group_last_by_member afterwards.
+ * GENERAL form only: the assign call runs into buffers of the context's own; then the target, the owned arrays, partition_id and
+ * the lag source (`lag`, or end and committed plus a dense begin -- for the sparse form the host scatters none_begin over zeros
+ * while packing, LA_RESET_LATEST stages no begin; the lag itself is computed on the device) travel as ONE H2D copy through the
+ * cooperative staging buffers of shard 0, la_cooperative_round_sticky_device runs on la_stream(ctx) with the largest topic as its
+ * hint -- the one-workgroup kernel when the call is within its limits -- and the outputs come back as ONE D2H copy.
+ * la_last_launches is the sum of the assign call's and the round's.  There is no fused zero-copy form yet.
+ * struct_size: sizeof(la_assign_sticky_args) of the caller's header; less than this library's is LA_EINVAL.  reserved must be 0. */
+typedef struct la_assign_sticky_args {
+    int32_t struct_size, reserved;          /* sizeof(la_assign_sticky_args) of the caller's header; 0 */
+    la_assign_coop_args coop;               /* exactly as for la_assign_batch_cooperative */
+    int32_t *sticky_partition;              /* [N] or NULL */
+    int64_t *topic_kept, *topic_saved;      /* [T] or NULL */
+    int64_t *sticky_summary;                /* [4] or NULL */
+} la_assign_sticky_args;
+int la_assign_batch_cooperative_sticky(la_ctx *ctx, const la_assign_sticky_args *args);
 
 #ifdef __cplusplus
 }

@@ -61,6 +61,12 @@ COOP_SMALL_OWNED = 2048
 COOP_SMALL_MEMBERS = 2046
 COOP_SMALL_TOPICS = 2048
 LA_COOP_FORCE_TABLE = 1
+# la_cooperative_round_sticky_device: within ALL four limits, and without LA_COOP_FORCE_TABLE, one launch of one workgroup;
+# any other call is the chain of the three calls it replaces (LA_COOP_STICKY_* of lagassign.h, kCoopSticky* of csrc/la_coop.h)
+LA_COOP_STICKY_ENTRIES = COOP_STICKY_ENTRIES = 2048
+LA_COOP_STICKY_OWNED = COOP_STICKY_OWNED = 2048
+LA_COOP_STICKY_MEMBERS = COOP_STICKY_MEMBERS = 2046
+LA_COOP_STICKY_TOPICS = COOP_STICKY_TOPICS = 2048
 
 EXPORTED_SYMBOLS = (
     "la_create", "la_destroy", "la_last_error", "la_version", "la_compute_lag",
@@ -80,6 +86,7 @@ EXPORTED_SYMBOLS = (
     "la_cooperative_round_device", "la_cooperative_round",
     "la_assign_batch_cooperative",
     "la_sticky_ties_device",
+    "la_cooperative_round_sticky_device", "la_assign_batch_cooperative_sticky",
 )
 
 _i64p = ctypes.POINTER(ctypes.c_int64)
@@ -180,6 +187,17 @@ class CoopRoundArgs(ctypes.Structure):
     ]
 
 
+class CoopStickyArgs(ctypes.Structure):
+    """struct la_coop_sticky_args (device addresses as ints, None / 0 = NULL; struct_size is filled in by
+    cooperative_round_sticky_device).  `round` is the CoopRoundArgs of cooperative_round_device; its target fields (n_topics,
+    n_partitions, d_part_off, d_out_partition, d_out_member_rank) are not looked at: the target is the batch's."""
+    _fields_ = [
+        ("struct_size", ctypes.c_int32), ("flags", ctypes.c_int32), ("round", CoopRoundArgs),
+        ("d_sticky_partition", ctypes.c_void_p), ("d_topic_kept", ctypes.c_void_p), ("d_topic_saved", ctypes.c_void_p),
+        ("d_sticky_summary", ctypes.c_void_p),
+    ]
+
+
 class CoopRound(NamedTuple):
     """What Context.cooperative_round returns: the eight outputs of the adjusted assignment, then every member's list of it."""
     prev_owner: np.ndarray
@@ -231,6 +249,25 @@ class AssignCoop(NamedTuple):
     member_off: np.ndarray
     grouped_topic: Optional[np.ndarray]
     grouped_partition: np.ndarray
+
+
+class AssignStickyArgs(ctypes.Structure):
+    """struct la_assign_sticky_args (host addresses as ints, None / 0 = NULL)"""
+    _fields_ = [
+        ("struct_size", ctypes.c_int32), ("reserved", ctypes.c_int32), ("coop", AssignCoopArgs),
+        ("sticky_partition", ctypes.c_void_p), ("topic_kept", ctypes.c_void_p), ("topic_saved", ctypes.c_void_p),
+        ("sticky_summary", ctypes.c_void_p),
+    ]
+
+
+class AssignSticky(NamedTuple):
+    """What Context.assign_batch_cooperative_sticky returns: `coop`, an AssignCoop whose target entries (out_partition,
+    out_member_rank, totals) describe the TARGET and whose other entries describe the STICKY order, and the four sticky outputs."""
+    coop: AssignCoop
+    sticky_partition: np.ndarray
+    topic_kept: np.ndarray
+    topic_saved: np.ndarray
+    sticky_summary: np.ndarray
 
 
 class PhaseTimes(ctypes.Structure):
@@ -391,6 +428,13 @@ def load() -> ctypes.CDLL:
     if hasattr(L, "la_sticky_ties_device"):
         L.la_sticky_ties_device.restype = ctypes.c_int
         L.la_sticky_ties_device.argtypes = [ctypes.c_void_p, ctypes.POINTER(DeviceBatch), ctypes.POINTER(StickyArgs), ctypes.c_void_p]
+    if hasattr(L, "la_cooperative_round_sticky_device"):
+        L.la_cooperative_round_sticky_device.restype = ctypes.c_int
+        L.la_cooperative_round_sticky_device.argtypes = [ctypes.c_void_p, ctypes.POINTER(DeviceBatch), ctypes.POINTER(CoopStickyArgs),
+                                                         ctypes.c_void_p]
+    if hasattr(L, "la_assign_batch_cooperative_sticky"):
+        L.la_assign_batch_cooperative_sticky.restype = ctypes.c_int
+        L.la_assign_batch_cooperative_sticky.argtypes = [ctypes.c_void_p, ctypes.POINTER(AssignStickyArgs)]
     if hasattr(L, "la_sticky_ties_device_on"):
         L.la_sticky_ties_device_on.restype = ctypes.c_int
         L.la_sticky_ties_device_on.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(DeviceBatch), ctypes.POINTER(StickyArgs),
@@ -903,6 +947,23 @@ class Context:
             args.struct_size = ctypes.sizeof(CoopRoundArgs)
         self._check(fn(self._h, ctypes.byref(args), ctypes.c_void_p(stream)))
 
+    def cooperative_round_sticky_device(self, batch: DeviceBatch, args: CoopStickyArgs, stream: int = 0) -> None:
+        """la_cooperative_round_sticky_device (shard 0 of the context): the cooperative round on the STICKY order in one call --
+        bit for bit what cooperative_adjust_device (for d_prev_owner), sticky_ties_device and cooperative_round_device with
+        d_sticky_partition in place of d_out_partition write when chained on one stream.  `batch` is the struct an assign call
+        took, read as sticky_ties_device reads it; the target is the batch's.  args.d_sticky_partition (int32[N]) is required,
+        d_topic_kept / d_topic_saved (int64[T]) and d_sticky_summary (int64[4]) may be left out, and so may each of the eight
+        adjust outputs; the round's outputs describe the sticky order.  Within COOP_STICKY_ENTRIES / _OWNED / _MEMBERS / _TOPICS
+        it is ONE kernel launch without memset, allocation or scratch; otherwise, or with args.flags = LA_COOP_FORCE_TABLE, the
+        chain itself.  Errors are the union of the three calls'.  sharding.cooperative_round_sticky_numpy is the same on the
+        host."""
+        fn = getattr(self._lib, "la_cooperative_round_sticky_device", None)
+        if fn is None:
+            raise LagAssignError(LA_EINVAL, "this liblagassign.so has no la_cooperative_round_sticky_device")
+        if not args.struct_size:
+            args.struct_size = ctypes.sizeof(CoopStickyArgs)
+        self._check(fn(self._h, ctypes.byref(batch) if batch is not None else None, ctypes.byref(args), ctypes.c_void_p(stream)))
+
     def cooperative_round(self, part_off, out_partition, out_member_rank, n_members: int, owned_off, owned_topic, owned_partition,
                           force_table: bool = False) -> CoopRound:
         """la_cooperative_round: the cooperative round on host arrays (numpy in, a CoopRound of numpy arrays out) -- the target
@@ -958,6 +1019,44 @@ class Context:
         fn = getattr(self._lib, "la_assign_batch_cooperative", None)
         if fn is None:
             raise LagAssignError(LA_EINVAL, "this liblagassign.so has no la_assign_batch_cooperative")
+        g = AssignCoopArgs()
+        out = self._fill_assign_coop(g, part_off, partition_id, cons_off, cons_rank, n_members, owned_off, owned_topic, owned_partition,
+                                     lag, begin, end, committed, reset_mode, none_index, none_begin, force_table, out)
+        self._check(fn(self._h, ctypes.byref(g)))
+        return out
+
+    def assign_batch_cooperative_sticky(self, part_off, partition_id, cons_off, cons_rank, n_members: int, owned_off, owned_topic,
+                                        owned_partition, *, lag=None, begin=None, end=None, committed=None, reset_mode: int = 0,
+                                        none_index=None, none_begin=None, force_table: bool = False,
+                                        out: Optional[AssignSticky] = None) -> AssignSticky:
+        """la_assign_batch_cooperative_sticky: assign_batch_cooperative with the round on the STICKY order (partitions of equal
+        lag stay with their previous owner).  Same inputs; returns an AssignSticky: .coop.out_partition / out_member_rank /
+        totals describe the TARGET, every other entry of .coop and sticky_partition / topic_kept / topic_saved / sticky_summary
+        the sticky order; `out` = caller-owned buffers in that shape (None entries of out.coop are not computed).
+        sharding.assign_cooperative_sticky_numpy is the same on the host."""
+        fn = getattr(self._lib, "la_assign_batch_cooperative_sticky", None)
+        if fn is None:
+            raise LagAssignError(LA_EINVAL, "this liblagassign.so has no la_assign_batch_cooperative_sticky")
+        a = AssignStickyArgs()
+        a.struct_size = ctypes.sizeof(AssignStickyArgs)
+        coop = self._fill_assign_coop(a.coop, part_off, partition_id, cons_off, cons_rank, n_members, owned_off, owned_topic,
+                                      owned_partition, lag, begin, end, committed, reset_mode, none_index, none_begin, force_table,
+                                      None if out is None else out.coop)
+        n, t = coop.grouped_partition.size, _a64(part_off).size - 1
+        if out is None:
+            out = AssignSticky(coop, np.empty(n, np.int32), np.empty(t, np.int64), np.empty(t, np.int64), np.empty(4, np.int64))
+        elif (out.sticky_partition.dtype, out.sticky_partition.size) != (np.int32, n) or \
+                any((x.dtype, x.size) != (np.int64, k) for x, k in ((out.topic_kept, t), (out.topic_saved, t), (out.sticky_summary, 4))):
+            raise ValueError("out: sticky_partition int32[N], topic_kept / topic_saved int64[T], sticky_summary int64[4]")
+        p = lambda x: x.ctypes.data if x.size else None
+        a.sticky_partition, a.topic_kept, a.topic_saved = p(out.sticky_partition), p(out.topic_kept), p(out.topic_saved)
+        a.sticky_summary = out.sticky_summary.ctypes.data
+        self._check(fn(self._h, ctypes.byref(a)))
+        return out
+
+    def _fill_assign_coop(self, g, part_off, partition_id, cons_off, cons_rank, n_members, owned_off, owned_topic, owned_partition,
+                          lag, begin, end, committed, reset_mode, none_index, none_begin, force_table, out):
+        """Fills the AssignCoopArgs `g` from numpy arrays (kept alive on self until the next call) -> the AssignCoop of outputs."""
         part_off, cons_off = _a64(part_off), _a64(cons_off)
         partition_id, cons_rank = _a32(partition_id), _a32(cons_rank)
         m, t, n, k = int(n_members), part_off.size - 1, partition_id.size, cons_rank.size
@@ -986,7 +1085,6 @@ class Context:
                              np.empty(m, np.int64), np.empty(m, np.int64), np.empty(t, np.int64), np.empty(6, np.int64),
                              np.empty(m + 1, np.int64), np.empty(n, np.int32), np.empty(n, np.int32))
         p = lambda a: a.ctypes.data if a is not None and a.size else None
-        g = AssignCoopArgs()
         g.struct_size, g.flags = ctypes.sizeof(AssignCoopArgs), LA_COOP_FORCE_TABLE if force_table else 0
         g.n_topics, g.reset_mode = t, reset_mode
         g.part_off, g.partition_id, g.lag = part_off.ctypes.data, p(partition_id), p(lag)
@@ -1004,7 +1102,8 @@ class Context:
         g.member_kept, g.member_fresh, g.member_pending = p(out.kept), p(out.fresh), p(out.pending)
         g.member_release, g.topic_withheld = p(out.release), p(out.topic_withheld)
         g.summary = None if out.summary is None else out.summary.ctypes.data
-        self._check(fn(self._h, ctypes.byref(g)))
+        self._inputs = (part_off, partition_id, cons_off, cons_rank, lag, begin, end, committed, none_index, none_begin, owned_off,
+                        owned_topic, owned_partition)
         return out
 
     # -- device-resident entry point ------------------------------------------------

@@ -46,8 +46,13 @@ class LagBasedPartitionAssignor:
 
     # -- plugin surface -------------------------------------------------------------
     def configure(self, configs: Mapping[str, object]) -> None:
-        """Main.java:97-130.  Raises ValueError (IllegalArgumentException) without group.id."""
+        """Main.java:97-130.  Raises ValueError (IllegalArgumentException) without group.id.  ``lag.assignor.sticky.ties``
+        (a boolean, default false): assign_cooperative() keeps partitions of equal lag with their previous owner."""
         self._impl.configure({str(k): str(v) for k, v in configs.items()})
+
+    def sticky_ties(self) -> bool:
+        """``lag.assignor.sticky.ties`` as configure() read it."""
+        return bool(self._impl.sticky_ties())
 
     def name(self) -> str:
         return self._impl.name()
@@ -86,7 +91,8 @@ class LagBasedPartitionAssignor:
     def last_cooperative_round() -> Dict[str, object]:
         """What the last assign_cooperative() on this thread did: ``per_member`` memberId -> (kept, fresh, pending, release),
         ``topic_withheld`` topic -> count, the totals ``kept`` / ``fresh`` / ``withheld`` / ``dropped`` / ``stale`` and
-        ``followup`` (another rebalance is needed).  last_topic_totals / last_member_loads / last_native_call describe the
+        ``followup`` (another rebalance is needed), ``sticky_kept_before`` / ``sticky_kept_after`` /
+        ``sticky_topics_passed_through`` (0 unless ``lag.assignor.sticky.ties`` is on).  last_topic_totals / last_member_loads / last_native_call describe the
         TARGET of that call, as after assign()."""
         d = dict(_host().LagBasedPartitionAssignor.last_cooperative_round())
         d["per_member"] = {m: tuple(int(x) for x in v) for m, v in d["per_member"].items()}

@@ -2,6 +2,8 @@
 // all arithmetic goes through the C ABI (include/lagassign.h) to the HIP kernels.
 #include "lag_based_partition_assignor.hpp"
 
+#include <cctype>
+
 #include <algorithm>
 #include <functional>
 #include <mutex>
@@ -157,7 +159,8 @@ void hint_bounds(la_ctx* ctx, const Flat& f) {
 
 Assignment run_native(const Plan& plan, const std::vector<const TopicData*>& data, bool offsets_mode,
                       int32_t reset_mode, std::map<std::string, std::map<std::string, int64_t>>* totals_out,
-                      const std::function<void(const std::string&)>* debug = nullptr, const OwnedArrays* owned = nullptr) {
+                      const std::function<void(const std::string&)>* debug = nullptr, const OwnedArrays* owned = nullptr,
+                      bool sticky = false) {
     Flat f;
     for (size_t t = 0; t < plan.topics.size(); ++t) {
         const TopicData* d = data[t];
@@ -233,7 +236,16 @@ Assignment run_native(const Plan& plan, const std::vector<const TopicData*>& dat
         a.member_release = counts.data() + 3 * M;
         a.topic_withheld = withheld.data();
         a.summary = summary.data();
-        check(ctx, la_assign_batch_cooperative(ctx, &a));
+        std::vector<int64_t> sticky_summary(4, 0);
+        if (sticky) {                                            // lag.assignor.sticky.ties: the lists are those of the sticky order
+            la_assign_sticky_args sa{};
+            sa.struct_size = (int32_t)sizeof sa;
+            sa.coop = a;
+            sa.sticky_summary = sticky_summary.data();
+            check(ctx, la_assign_batch_cooperative_sticky(ctx, &sa));
+        } else {
+            check(ctx, la_assign_batch_cooperative(ctx, &a));
+        }
         t_last_native.pipeline = la_last_pipeline(ctx);
         t_last_native.launches = la_last_launches(ctx);
         if (debug && *debug) {                                   // (only then: the target's eager lists, still on the device)
@@ -247,6 +259,8 @@ Assignment run_native(const Plan& plan, const std::vector<const TopicData*>& dat
         for (size_t t = 0; t < T; ++t) t_last_coop.topic_withheld[plan.topics[t]] = withheld[t];
         t_last_coop.kept = summary[0]; t_last_coop.fresh = summary[1]; t_last_coop.withheld = summary[2];
         t_last_coop.dropped = summary[3]; t_last_coop.stale = summary[4]; t_last_coop.followup = summary[5] != 0;
+        t_last_coop.sticky_kept_before = sticky_summary[0]; t_last_coop.sticky_kept_after = sticky_summary[1];
+        t_last_coop.sticky_topics_passed_through = sticky_summary[3];
     } else if (!plan.topics.empty()) {
         std::lock_guard<std::mutex> lock(g_ctx_mutex);       // one lock over both calls: the second reads the first's results
         la_ctx* ctx = shared_ctx_locked();
@@ -374,6 +388,15 @@ void LagBasedPartitionAssignor::configure(const std::map<std::string, std::strin
     metadata_consumer_props_ = consumer_group_props_;                            // :116-120
     metadata_consumer_props_["enable.auto.commit"] = "false";
     metadata_consumer_props_["client.id"] = gid->second + ".assignor";
+    // lag.assignor.sticky.ties: a boolean as Boolean.parseBoolean reads it ("true" in any case), default false -- whether
+    // assignCooperative keeps partitions of equal lag with their previous owner (la_assign_batch_cooperative_sticky)
+    auto sticky = consumer_group_props_.find("lag.assignor.sticky.ties");
+    sticky_ties_ = false;
+    if (sticky != consumer_group_props_.end()) {
+        std::string v = sticky->second;
+        for (char& ch : v) ch = (char)std::tolower((unsigned char)ch);
+        sticky_ties_ = v == "true";
+    }
 }
 
 int64_t LagBasedPartitionAssignor::computePartitionLag(const std::optional<OffsetAndMetadata>& partitionMetadata,
@@ -535,7 +558,7 @@ Assignment LagBasedPartitionAssignor::assignImpl(const Cluster& metadata, const 
         std::vector<std::vector<TopicPartition>> per_member;
         for (const std::string& m : plan.members) per_member.push_back(*of.at(m));
         const OwnedArrays arrays = cooperativeOwnedArrays(plan.members, plan.topics, per_member);
-        return run_native(plan, data, true, reset, &last_totals_, &debug, &arrays);
+        return run_native(plan, data, true, reset, &last_totals_, &debug, &arrays, sticky_ties_);
     }
     return run_native(plan, data, true, reset, &last_totals_, &debug);           // wrap: :152-156
 }

@@ -114,6 +114,9 @@ class LagBasedPartitionAssignor {
         std::map<std::string, int64_t> topic_withheld;
         int64_t kept = 0, fresh = 0, withheld = 0, dropped = 0, stale = 0;
         bool followup = false;
+        // lag.assignor.sticky.ties: kept before / after the re-matching of equal-lag partitions (0 / 0 with the key off) and the
+        // topics that kept the reference's order although the key is on
+        int64_t sticky_kept_before = 0, sticky_kept_after = 0, sticky_topics_passed_through = 0;
     };
     static CooperativeRound lastCooperativeRound();
 
@@ -128,6 +131,8 @@ class LagBasedPartitionAssignor {
 
     // Properties the side consumer would get (Main.java:116-120), for inspection/tests.
     const std::map<std::string, std::string>& metadataConsumerProps() const { return metadata_consumer_props_; }
+    // lag.assignor.sticky.ties as configure() read it (default false)
+    bool stickyTies() const { return sticky_ties_; }
 
     // The accessors below describe the TARGET (the eager assignment) after assignCooperative, exactly as after assign().
     // Per-topic consumer totals of the last instance-level assign (the debug summary's
@@ -179,6 +184,7 @@ class LagBasedPartitionAssignor {
                           const OrderedMap<std::vector<TopicPartition>>* owned);
     std::map<std::string, std::string> consumer_group_props_;
     std::map<std::string, std::string> metadata_consumer_props_;
+    bool sticky_ties_ = false;                                           // lag.assignor.sticky.ties
     std::map<std::string, std::map<std::string, int64_t>> last_totals_;
     bool last_order_exact_ = true;
 };

@@ -110,6 +110,7 @@ PYBIND11_MODULE(_host, m) {
     py::class_<LagBasedPartitionAssignor>(m, "LagBasedPartitionAssignor")
         .def(py::init<>())
         .def("configure", &LagBasedPartitionAssignor::configure)
+        .def("sticky_ties", &LagBasedPartitionAssignor::stickyTies)
         .def("name", &LagBasedPartitionAssignor::name)
         .def("metadata_consumer_props", &LagBasedPartitionAssignor::metadataConsumerProps)
         .def("last_topic_totals", &LagBasedPartitionAssignor::lastTopicTotals)
@@ -159,6 +160,9 @@ PYBIND11_MODULE(_host, m) {
             d["dropped"] = c.dropped;
             d["stale"] = c.stale;
             d["followup"] = c.followup;
+            d["sticky_kept_before"] = c.sticky_kept_before;
+            d["sticky_kept_after"] = c.sticky_kept_after;
+            d["sticky_topics_passed_through"] = c.sticky_topics_passed_through;
             return d;
         })
         .def_static("assign_static",

@@ -1246,7 +1246,114 @@ LA_API int la_cooperative_round_device(la_ctx* ctx, const la_coop_round_args* ar
     });
 }
 
-// The same on host buffers: the inputs packed into the shard's own staging buffer (pinned + device, both grown before anything
+// [a, a + na) and [b, b + nb) share a byte (null or empty: they do not)
+static bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
+    if (!a || !b || !na || !nb) return false;
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + nb && y < x + na;
+}
+
+// la_device_batch + la_coop_sticky_args, checked: the batch as la_sticky_ties_device checks it, the round as
+// la_cooperative_round_device checks it with the target taken from the batch, the sticky outputs.
+static int coop_sticky_call_of(la_ctx* ctx, const la_device_batch* batch, const la_coop_sticky_args* args, la::CoopStickyCall* out) {
+    if (!batch) return fail(ctx, LA_EINVAL, "batch is NULL");
+    if (!args) return fail(ctx, LA_EINVAL, "args is NULL");
+    if (args->struct_size < (int32_t)sizeof(la_coop_sticky_args))
+        return fail(ctx, LA_EINVAL, "la_coop_sticky_args.struct_size is %d, this library takes %d and above", (int)args->struct_size, (int)sizeof(la_coop_sticky_args));
+    if (args->flags & ~LA_COOP_FORCE_TABLE) return fail(ctx, LA_EINVAL, "la_coop_sticky_args.flags holds a bit this library does not know");
+    const la_device_batch& b = *batch;
+    if (b.n_topics < 0 || b.n_partitions < 0) return fail(ctx, LA_EINVAL, "negative size");
+    if (b.flags & LA_FLAG_WIRE_OUT)
+        return fail(ctx, LA_EINVAL, "LA_FLAG_WIRE_OUT: unpack the results with la_unpack_results_on before re-matching them");
+    if (b.n_topics == 0 && b.n_partitions != 0) return fail(ctx, LA_EINVAL, "partitions without topics");
+    if (b.n_topics > 0 && !b.d_part_off) return fail(ctx, LA_EINVAL, "null offsets");
+    if (b.n_partitions > 0 && (!b.d_out_partition || !b.d_out_member_rank)) return fail(ctx, LA_EINVAL, "null results");
+    if (b.n_partitions > 0 && (!b.d_partition_id || (!b.d_lag && (!b.d_end_off || !b.d_committed_off))))
+        return fail(ctx, LA_EINVAL, "null per-partition input");
+    if (!b.d_lag && b.reset_mode != LA_RESET_LATEST && !b.d_begin_off && b.n_partitions > 0)
+        return fail(ctx, LA_EINVAL, "begin_off is required unless reset_mode is LA_RESET_LATEST");
+    const size_t n4 = (size_t)b.n_partitions * 4, n8 = (size_t)b.n_partitions * 8;
+    if (b.n_partitions > 0 && !args->d_sticky_partition) return fail(ctx, LA_EINVAL, "d_sticky_partition is NULL");
+    for (const void* in : {(const void*)b.d_out_partition, (const void*)b.d_out_member_rank, (const void*)b.d_partition_id})
+        if (ranges_overlap(args->d_sticky_partition, n4, in, n4))
+            return fail(ctx, LA_EINVAL, "d_sticky_partition overlaps an input: the call does not work in place");
+    for (const void* in : {(const void*)b.d_lag, (const void*)b.d_begin_off, (const void*)b.d_end_off, (const void*)b.d_committed_off})
+        if (ranges_overlap(args->d_sticky_partition, n4, in, n8))
+            return fail(ctx, LA_EINVAL, "d_sticky_partition overlaps an input: the call does not work in place");
+    const la_coop_args& ra = args->round.adjust;
+    const size_t o4 = ra.n_owned > 0 ? (size_t)ra.n_owned * 4 : 0;
+    if (ranges_overlap(args->d_sticky_partition, n4, b.d_part_off, ((size_t)b.n_topics + 1) * 8) ||
+        ranges_overlap(args->d_sticky_partition, n4, ra.d_owned_member_off, ra.n_members >= 0 ? ((size_t)ra.n_members + 1) * 8 : 0) ||
+        ranges_overlap(args->d_sticky_partition, n4, ra.d_owned_topic, o4) || ranges_overlap(args->d_sticky_partition, n4, ra.d_owned_partition, o4))
+        return fail(ctx, LA_EINVAL, "d_sticky_partition overlaps an input: the call does not work in place");
+    la_coop_args adjust = args->round.adjust;       // the target is the batch's
+    adjust.n_topics = b.n_topics;
+    adjust.n_partitions = b.n_partitions;
+    adjust.d_part_off = b.d_part_off;
+    adjust.d_out_partition = b.d_out_partition;
+    adjust.d_out_member_rank = b.d_out_member_rank;
+    la::CoopStickyCall k{};
+    if (int rc = coop_call_of(ctx, adjust, false, &k.r.c)) return rc;
+    if (!args->round.member_off) return fail(ctx, LA_EINVAL, "member_off is NULL");
+    if (b.n_partitions > 0 && !args->round.grouped_partition) return fail(ctx, LA_EINVAL, "grouped_partition is NULL");
+    if (b.n_partitions > 0x7FFFFFFF) return fail(ctx, LA_ESHAPE, "at most 2^31-1 entries are supported");
+    k.r.member_off = args->round.member_off;
+    k.r.grouped_topic = args->round.grouped_topic;
+    k.r.grouped_partition = args->round.grouped_partition;
+    la::StickyCall& c = k.s;
+    c.n_topics = b.n_topics;
+    c.reset_latest = b.reset_mode == LA_RESET_LATEST ? 1 : 0;
+    c.n_partitions = b.n_partitions;
+    c.max_partitions_per_topic = b.max_partitions_per_topic;
+    c.part_off = b.d_part_off;
+    c.pid = b.d_partition_id;
+    c.begin = b.d_begin_off;
+    c.end = b.d_end_off;
+    c.committed = b.d_committed_off;
+    c.lag = b.d_lag;
+    c.out_pid = b.d_out_partition;
+    c.out_rank = b.d_out_member_rank;
+    c.sticky = args->d_sticky_partition;
+    c.topic_kept = args->d_topic_kept;
+    c.topic_saved = args->d_topic_saved;
+    c.summary = args->d_sticky_summary;
+    *out = k;
+    return LA_OK;
+}
+
+// The cooperative round with sticky ties in one call (la_coop_sticky_small.hip), on shard 0: one launch of one workgroup within
+// the limits of la_coop.h, otherwise the three launchers in turn.  Neither touches the assign scratch or a kept result.
+LA_API int la_cooperative_round_sticky_device(la_ctx* ctx, const la_device_batch* batch, const la_coop_sticky_args* args, void* stream) {
+    return shard_entry<true>(ctx, 0, "exception in la_cooperative_round_sticky_device", [&](Shard& sh) -> int {
+        la::CoopStickyCall k{};
+        if (int rc = coop_sticky_call_of(ctx, batch, args, &k)) return rc;
+        hipError_t e = la::cooperative_round_sticky_launch(sh.coop, sh.lanes[0].large, k, (args->flags & LA_COOP_FORCE_TABLE) != 0,
+                                                           sh.lanes[0].d_status, (hipStream_t)stream);
+        return e != hipSuccess ? hip_fail(ctx, e, "cooperative_round_sticky: %s") : LA_OK;
+    });
+}
+
+// The cooperative staging buffers of a shard (pinned host memory and device memory) hold `total` bytes: both grown before anything
+// is enqueued, so a failure leaves nothing behind.
+static int coop_stage_reserve(la_ctx* ctx, la::CoopScratch& s, size_t total) {
+    if (total > s.stage_h_cap) {
+        if (s.stage_h) { (void)hipHostFree(s.stage_h); s.stage_h = nullptr; s.stage_h_cap = 0; }
+        const size_t want = total + total / 4 + 256;
+        const hipError_t e = hipHostMalloc(&s.stage_h, want, hipHostMallocDefault);
+        if (e != hipSuccess) { s.stage_h = nullptr; return hip_fail(ctx, e, "cooperative_round staging (host): %s"); }
+        s.stage_h_cap = want;
+    }
+    if (total > s.stage_d_cap) {
+        if (s.stage_d) { (void)hipFree(s.stage_d); s.stage_d = nullptr; s.stage_d_cap = 0; }
+        const size_t want = total + total / 4 + 256;
+        const hipError_t e = hipMalloc(&s.stage_d, want);
+        if (e != hipSuccess) { s.stage_d = nullptr; return hip_fail(ctx, e, "cooperative_round staging (device): %s"); }
+        s.stage_d_cap = want;
+    }
+    return LA_OK;
+}
+
+// la_cooperative_round_device on host buffers: the inputs packed into the shard's own staging buffer (pinned + device, both grown before anything
 // is enqueued), ONE copy in, the device call on lane 0's stream, ONE copy out, one wait.  8-byte arrays first, so every array
 // is aligned for its element.  It neither takes nor spends a pending la_hint_next_call.
 static int coop_round_host(la_ctx* ctx, Shard& sh, const la_coop_round_args* args) {
@@ -1273,20 +1380,7 @@ static int coop_round_host(la_ctx* ctx, Shard& sh, const la_coop_round_args* arg
         const size_t total = at, out_bytes = total - in_bytes;
         // both halves of the staging buffer before anything is enqueued
         la::CoopScratch& s = sh.coop;
-        if (total > s.stage_h_cap) {
-            if (s.stage_h) { (void)hipHostFree(s.stage_h); s.stage_h = nullptr; s.stage_h_cap = 0; }
-            const size_t want = total + total / 4 + 256;
-            const hipError_t e = hipHostMalloc(&s.stage_h, want, hipHostMallocDefault);
-            if (e != hipSuccess) { s.stage_h = nullptr; return hip_fail(ctx, e, "cooperative_round staging (host): %s"); }
-            s.stage_h_cap = want;
-        }
-        if (total > s.stage_d_cap) {
-            if (s.stage_d) { (void)hipFree(s.stage_d); s.stage_d = nullptr; s.stage_d_cap = 0; }
-            const size_t want = total + total / 4 + 256;
-            const hipError_t e = hipMalloc(&s.stage_d, want);
-            if (e != hipSuccess) { s.stage_d = nullptr; return hip_fail(ctx, e, "cooperative_round staging (device): %s"); }
-            s.stage_d_cap = want;
-        }
+        if (int rc = coop_stage_reserve(ctx, s, total)) return rc;
         char* const hp = static_cast<char*>(s.stage_h);
         char* const dp = static_cast<char*>(s.stage_d);
         if (use_part_off) memcpy(hp + i_part_off, h.part_off, (T + 1) * 8);
@@ -1440,6 +1534,184 @@ LA_API int la_assign_batch_cooperative(la_ctx* ctx, const la_assign_coop_args* g
         return LA_OK;
     } catch (...) {
         return fail(ctx, LA_ENOMEM, "exception in la_assign_batch_cooperative");
+    }
+}
+
+// A cooperative rebalance on the STICKY order from host buffers in one call.  GENERAL form only: the assign call into buffers of
+// the context's own (as coop_take_general arranges it), then target, owned arrays, partition ids and the lag source through the
+// cooperative staging buffers -- one copy in, la_cooperative_round_sticky_device on lane 0's stream, one copy out, one wait.  The
+// caller's arrays are written only after everything has succeeded.
+LA_API int la_assign_batch_cooperative_sticky(la_ctx* ctx, const la_assign_sticky_args* args) {
+    DeviceGuard restore_device;
+    LaunchSpan span(ctx);
+    HintSpender spend_hints(ctx);
+    if (!ctx) return LA_EINVAL;
+    try {
+        if (!args) return fail(ctx, LA_EINVAL, "args is NULL");
+        if (args->struct_size < (int32_t)sizeof(la_assign_sticky_args))
+            return fail(ctx, LA_EINVAL, "la_assign_sticky_args.struct_size is %d, this library takes %d and above", (int)args->struct_size, (int)sizeof(la_assign_sticky_args));
+        if (args->reserved != 0) return fail(ctx, LA_EINVAL, "la_assign_sticky_args.reserved must be 0");
+        const la_assign_coop_args* g = &args->coop;
+        if (g->flags & ~LA_COOP_FORCE_TABLE) return fail(ctx, LA_EINVAL, "la_assign_sticky_args.coop.flags holds a bit this library does not know");
+        if (g->reserved != 0) return fail(ctx, LA_EINVAL, "la_assign_coop_args.reserved must be 0");
+        if (g->n_topics < 0 || g->n_members < 0 || g->n_owned < 0) return fail(ctx, LA_EINVAL, "negative size");
+        if (g->n_members > la::kMovesMaxMembers) return fail(ctx, LA_EINVAL, "n_members must be below 2^30");
+        if (g->n_owned > 0 && (!g->owned_member_off || !g->owned_topic || !g->owned_partition))
+            return fail(ctx, LA_EINVAL, "null owned buffer");
+        if (!g->member_off) return fail(ctx, LA_EINVAL, "member_off is NULL");
+        const int32_t T = g->n_topics;
+        if (T > 0 && g->part_off && g->part_off[T] > 0 && !g->grouped_partition) return fail(ctx, LA_EINVAL, "grouped_partition is NULL");
+        if ((g->out_partition == nullptr) != (g->out_member_rank == nullptr)) return fail(ctx, LA_EINVAL, "out_partition and out_member_rank: both or neither");
+        // the assign call, into the context's own buffers (totals | ids | ranks); offsets it would refuse get no buffer and are
+        // refused by it
+        HostCall c;
+        c.T = T; c.part_off = g->part_off; c.pid = g->partition_id; c.cons_off = g->cons_off; c.cons_rank = g->cons_rank;
+        const bool sized = T > 0 && g->part_off && g->cons_off && g->part_off[T] >= 0 && g->cons_off[T] >= 0 &&
+                           g->part_off[T] <= 0x7FFFFFFF && g->cons_off[T] <= 0x7FFFFFFF;
+        if (T > 0 && !sized) return fail(ctx, LA_EINVAL, "part_off / cons_off are NULL, or end below 0 or beyond 2^31-1 entries");
+        const int64_t N = sized ? g->part_off[T] : 0, K = sized ? g->cons_off[T] : 0;
+        if (sized) {
+            ctx->coop_target.resize((size_t)K + (size_t)N + 1);
+            c.out_total = ctx->coop_target.data();
+            c.out_pid = (int32_t*)(ctx->coop_target.data() + K);
+            c.out_rank = c.out_pid + N;
+        }
+        const bool latest = g->lag != nullptr || g->reset_mode == LA_RESET_LATEST;
+        if (g->lag) {                                            // la_assign_batch_lags
+            c.reset_mode = LA_RESET_LATEST;
+            c.lag = g->lag;
+        } else {                                                 // la_assign_batch, or la_assign_batch_sparse without a dense begin
+            c.reset_mode = g->reset_mode; c.end = g->end_off; c.committed = g->committed_off; c.begin = g->begin_off;
+            if (!g->begin_off) { c.sparse = true; c.n_none = g->n_none; c.none_index = g->none_index; c.none_begin = g->none_begin; }
+        }
+        if (int rc = assign_host(ctx, c)) return rc;
+        const int64_t* const t_total = sized ? ctx->coop_target.data() : nullptr;
+        const int32_t* const t_pid = sized ? (const int32_t*)(t_total + K) : nullptr;
+        const int32_t* const t_rank = sized ? t_pid + N : nullptr;
+        int64_t hint = 0;                                        // the host knows the topics: the hint is the largest of them
+        for (int32_t t = 0; t < T; ++t) hint = std::max<int64_t>(hint, g->part_off[t + 1] - g->part_off[t]);
+
+        // staging: 8-byte arrays first, so every array is aligned for its element
+        Shard& sh = ctx->shards[0];
+        LA_HIP(ctx, hipSetDevice(sh.device));
+        const size_t n = (size_t)g->n_owned, M = (size_t)g->n_members, Ts = (size_t)T, Ns = (size_t)N;
+        const bool use_begin = !g->lag && !latest;
+        size_t at = 0;
+        auto take = [&](size_t bytes) { const size_t o = at; at += (bytes + 7) & ~(size_t)7; return o; };
+        const size_t i_part_off = take(T > 0 ? (Ts + 1) * 8 : 0), i_owned_off = take(n ? (M + 1) * 8 : 0);
+        const size_t i_lag = take(g->lag ? Ns * 8 : 0), i_end = take(g->lag ? 0 : Ns * 8), i_committed = take(g->lag ? 0 : Ns * 8);
+        const size_t i_begin = take(use_begin ? Ns * 8 : 0);
+        const size_t i_pid = take(Ns * 4), i_rank = take(Ns * 4), i_input_id = take(Ns * 4), i_otopic = take(n * 4), i_opid = take(n * 4);
+        const size_t in_bytes = at;
+        const size_t o_member_off = take((M + 1) * 8);
+        size_t o_count[4];
+        for (int w = 0; w < 4; ++w) o_count[w] = take(M * 8);
+        const size_t o_withheld = take(Ts * 8), o_summary = take(6 * 8), o_kept = take(Ts * 8), o_saved = take(Ts * 8), o_ssum = take(4 * 8);
+        const size_t o_prev = take(Ns * 4), o_coop = take(Ns * 4), o_gtopic = take(Ns * 4), o_gpart = take(Ns * 4), o_sticky = take(Ns * 4);
+        const size_t total = at, out_bytes = total - in_bytes;
+        la::CoopScratch& s = sh.coop;
+        if (int rc = coop_stage_reserve(ctx, s, total)) return rc;
+        char* const hp = static_cast<char*>(s.stage_h);
+        char* const dp = static_cast<char*>(s.stage_d);
+        if (T > 0) memcpy(hp + i_part_off, g->part_off, (Ts + 1) * 8);
+        if (n) {
+            memcpy(hp + i_owned_off, g->owned_member_off, (M + 1) * 8);
+            memcpy(hp + i_otopic, g->owned_topic, n * 4);
+            memcpy(hp + i_opid, g->owned_partition, n * 4);
+        }
+        if (Ns) {
+            memcpy(hp + i_pid, t_pid, Ns * 4);
+            memcpy(hp + i_rank, t_rank, Ns * 4);
+            memcpy(hp + i_input_id, g->partition_id, Ns * 4);
+            if (g->lag) {
+                memcpy(hp + i_lag, g->lag, Ns * 8);
+            } else {
+                memcpy(hp + i_end, g->end_off, Ns * 8);
+                memcpy(hp + i_committed, g->committed_off, Ns * 8);
+                if (use_begin && g->begin_off) {
+                    memcpy(hp + i_begin, g->begin_off, Ns * 8);
+                } else if (use_begin) {                          // the sparse list over zeros: marshalling, the lag itself is lag_of's
+                    int64_t* const begin = (int64_t*)(hp + i_begin);
+                    memset(begin, 0, Ns * 8);
+                    for (int64_t i = 0; i < g->n_none; ++i)
+                        if (g->none_index[i] >= 0 && g->none_index[i] < N) begin[g->none_index[i]] = g->none_begin[i];
+                }
+            }
+        }
+        la_device_batch b{};
+        b.n_topics = T;
+        b.reset_mode = latest ? LA_RESET_LATEST : g->reset_mode;
+        b.n_partitions = N;
+        b.max_partitions_per_topic = hint;
+        b.d_part_off = T > 0 ? (int64_t*)(dp + i_part_off) : nullptr;
+        b.d_partition_id = Ns ? (int32_t*)(dp + i_input_id) : nullptr;
+        b.d_lag = g->lag && Ns ? (int64_t*)(dp + i_lag) : nullptr;
+        b.d_end_off = !g->lag && Ns ? (int64_t*)(dp + i_end) : nullptr;
+        b.d_committed_off = !g->lag && Ns ? (int64_t*)(dp + i_committed) : nullptr;
+        b.d_begin_off = use_begin && Ns ? (int64_t*)(dp + i_begin) : nullptr;
+        b.d_out_partition = Ns ? (int32_t*)(dp + i_pid) : nullptr;
+        b.d_out_member_rank = Ns ? (int32_t*)(dp + i_rank) : nullptr;
+        la_coop_sticky_args a{};
+        a.struct_size = (int32_t)sizeof a;
+        a.flags = g->flags;
+        la_coop_args& adj = a.round.adjust;
+        adj.n_members = g->n_members;
+        adj.n_owned = g->n_owned;
+        adj.d_owned_member_off = n ? (int64_t*)(dp + i_owned_off) : nullptr;
+        adj.d_owned_topic = n ? (int32_t*)(dp + i_otopic) : nullptr;
+        adj.d_owned_partition = n ? (int32_t*)(dp + i_opid) : nullptr;
+        adj.d_prev_owner = (int32_t*)(dp + o_prev);
+        adj.d_coop_member_rank = (int32_t*)(dp + o_coop);
+        adj.d_member_kept = (int64_t*)(dp + o_count[0]);
+        adj.d_member_fresh = (int64_t*)(dp + o_count[1]);
+        adj.d_member_pending = (int64_t*)(dp + o_count[2]);
+        adj.d_member_release = (int64_t*)(dp + o_count[3]);
+        adj.d_topic_withheld = (int64_t*)(dp + o_withheld);
+        adj.d_summary = (int64_t*)(dp + o_summary);
+        a.round.member_off = (int64_t*)(dp + o_member_off);
+        a.round.grouped_topic = (int32_t*)(dp + o_gtopic);
+        a.round.grouped_partition = (int32_t*)(dp + o_gpart);
+        a.d_sticky_partition = (int32_t*)(dp + o_sticky);
+        a.d_topic_kept = (int64_t*)(dp + o_kept);
+        a.d_topic_saved = (int64_t*)(dp + o_saved);
+        a.d_sticky_summary = (int64_t*)(dp + o_ssum);
+        la::CoopStickyCall k{};
+        if (int rc = coop_sticky_call_of(ctx, &b, &a, &k)) return rc;
+        Lane& ln = sh.lanes[0];
+        hipStream_t st = ln.stream;
+        if (in_bytes) LA_HIP(ctx, hipMemcpyAsync(dp, hp, in_bytes, hipMemcpyHostToDevice, st));
+        hipError_t e = la::cooperative_round_sticky_launch(s, ln.large, k, (g->flags & LA_COOP_FORCE_TABLE) != 0, ln.d_status, st);
+        if (e != hipSuccess) {
+            (void)hipStreamSynchronize(st);
+            return hip_fail(ctx, e, "cooperative_round_sticky: %s");
+        }
+        LA_HIP(ctx, hipMemcpyAsync(hp + in_bytes, dp + in_bytes, out_bytes, hipMemcpyDeviceToHost, st));
+        if (int rc = sync_status(ctx, ln, st)) return rc;
+        // everything has succeeded: the caller's arrays
+        memcpy(g->member_off, hp + o_member_off, (M + 1) * 8);
+        int64_t* const h_count[4] = {g->member_kept, g->member_fresh, g->member_pending, g->member_release};
+        for (int w = 0; w < 4; ++w)
+            if (h_count[w] && M) memcpy(h_count[w], hp + o_count[w], M * 8);
+        if (g->topic_withheld && Ts) memcpy(g->topic_withheld, hp + o_withheld, Ts * 8);
+        if (g->summary) memcpy(g->summary, hp + o_summary, 6 * 8);
+        if (args->topic_kept && Ts) memcpy(args->topic_kept, hp + o_kept, Ts * 8);
+        if (args->topic_saved && Ts) memcpy(args->topic_saved, hp + o_saved, Ts * 8);
+        if (args->sticky_summary) memcpy(args->sticky_summary, hp + o_ssum, 4 * 8);
+        if (Ns) {
+            if (g->prev_owner) memcpy(g->prev_owner, hp + o_prev, Ns * 4);
+            if (g->coop_member_rank) memcpy(g->coop_member_rank, hp + o_coop, Ns * 4);
+            if (g->grouped_topic) memcpy(g->grouped_topic, hp + o_gtopic, Ns * 4);
+            memcpy(g->grouped_partition, hp + o_gpart, Ns * 4);
+            if (args->sticky_partition) memcpy(args->sticky_partition, hp + o_sticky, Ns * 4);
+            if (g->out_partition) {
+                memcpy(g->out_partition, t_pid, Ns * 4);
+                memcpy(g->out_member_rank, t_rank, Ns * 4);
+            }
+        }
+        if (g->out_total_lag && K > 0) memcpy(g->out_total_lag, t_total, (size_t)K * 8);
+        return LA_OK;
+    } catch (...) {
+        return fail(ctx, LA_ENOMEM, "exception in la_assign_batch_cooperative_sticky");
     }
 }
 

@@ -38,6 +38,8 @@ struct CoopScratch {            // of one shard, grown lazily: never the assign 
     size_t table_cap = 0;
     void* ranks = nullptr;      // la_cooperative_round_device, general form, without d_coop_member_rank: the adjusted ranks
     size_t ranks_cap = 0;
+    void* prev = nullptr;       // la_cooperative_round_sticky_device, general form: the previous owners of the TARGET order
+    size_t prev_cap = 0;
     void* stage_h = nullptr;    // la_cooperative_round (host buffers): inputs and outputs of a call, pinned ...
     size_t stage_h_cap = 0;
     void* stage_d = nullptr;    // ... and on the device: one copy each way
@@ -97,5 +99,32 @@ hipError_t cooperative_round_launch(CoopScratch& s, LargeScratch& large, const C
 // Exactly one launch; hipErrorInvalidValue, with nothing enqueued, for a call outside the limits.
 hipError_t cooperative_round_finish_launch(const CoopRoundCall& r, int32_t* target_partition, int32_t* target_rank,
                                            uint32_t* status, uint32_t* fin_flag, hipStream_t stream);
+
+// ---- the round with sticky ties in one call (la_coop_sticky_small.hip) -----------------------------------------------------------
+// la_cooperative_round_sticky_device: cooperative_adjust_launch for the previous owners, sticky_ties_launch, then
+// cooperative_round_launch on the sticky order -- or, within ALL four limits below and without force_table, ONE launch of ONE
+// workgroup that does the three in its LDS (coop_sticky_small_kernel; the LDS budget of every phase is proved by the
+// static_asserts of la_coop_sticky_small.hip).  The limits are the round's.
+constexpr int kCoopStickyEntries = kCoopSmallEntries;   // N: positions in 12 bits of a sort key, two key arrays of N in the table's LDS
+constexpr int kCoopStickyOwned = kCoopSmallOwned;       // n_owned
+constexpr int kCoopStickyMembers = kCoopSmallMembers;   // M
+constexpr int kCoopStickyTopics = kCoopSmallTopics;     // T: T + 1 part offsets, four counters per topic
+
+struct CoopStickyCall {         // la_device_batch + la_coop_sticky_args (lagassign.h), validated
+    StickyCall s;               // the batch as la_sticky_ties_device reads it and its four outputs; prev_owner is not looked at
+    CoopRoundCall r;            // the round; r.c's target (n_topics, n_partitions, part_off, out_partition, out_member_rank) is s's
+};
+
+inline bool coop_sticky_is_small(const CoopCall& c) {
+    return c.n_partitions <= kCoopStickyEntries && c.n_owned <= kCoopStickyOwned && c.n_members <= kCoopStickyMembers &&
+           c.n_topics <= kCoopStickyTopics;
+}
+
+// The one-workgroup form (coop_sticky_is_small) unless force_table: exactly one launch, a topic over the batch's hint is passed
+// through by the kernel itself (kStatusShape).  Otherwise the three launchers in turn, the previous owners in s.prev and, when
+// the caller wants no adjusted ranks, s.ranks -- both grown before anything is enqueued (hipErrorOutOfMemory then).  Sets
+// kStatusCoop / kStatusSticky / kStatusShape / kStatusInternal.
+hipError_t cooperative_round_sticky_launch(CoopScratch& s, LargeScratch& large, const CoopStickyCall& k, bool force_table,
+                                           uint32_t* status, hipStream_t stream);
 
 }  // namespace la

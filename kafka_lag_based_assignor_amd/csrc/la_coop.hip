@@ -232,6 +232,7 @@ __global__ __launch_bounds__(kMovesThreads) void coop_lookup_kernel(CoopArgs a) 
 void coop_scratch_release(CoopScratch& s) {
     if (s.table) (void)hipFree(s.table);
     if (s.ranks) (void)hipFree(s.ranks);
+    if (s.prev) (void)hipFree(s.prev);
     if (s.stage_d) (void)hipFree(s.stage_d);
     if (s.stage_h) (void)hipHostFree(s.stage_h);
     s = CoopScratch{};

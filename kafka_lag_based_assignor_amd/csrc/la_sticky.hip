@@ -31,6 +31,7 @@
 #include "la_kernels.h"
 #include "la_device.h"
 #include "la_join.h"
+#include "la_sticky_match.h"
 
 namespace la {
 
@@ -40,13 +41,8 @@ constexpr int kStickyThreads = 256;
 constexpr int kStickyFewThreads = 64;               // topics up to kStickyFewPartitions: one wavefront, barriers cost nothing
 constexpr int64_t kStickyFewPartitions = 256;
 constexpr int64_t kStickyMaxPartitions = kVerifyMaxPartitions;
-constexpr uint16_t kNoPos = 0xFFFF;
-constexpr uint64_t kNoKey = ~0ull;
-constexpr int kKeyRunShift = 44, kKeyMemberShift = 12;
-constexpr uint64_t kKeyPosMask = (1ull << kKeyMemberShift) - 1;
 constexpr uint32_t kTopicBad = 1u, kTopicTies = 2u, kTopicChanged = 4u;
-static_assert(kStickyMaxPartitions <= (int64_t)kKeyPosMask + 1 && kStickyMaxPartitions < kNoPos, "positions in 12 bits of a key, 16-bit indices");
-static_assert(kKeyRunShift == kKeyMemberShift + 32 && kKeyRunShift + kKeyMemberShift < 64, "run | member | position, the top bits free: no key is kNoKey");
+static_assert(kStickyMaxPartitions <= (int64_t)kKeyPosMask + 1 && kStickyMaxPartitions < kNoPos, "positions in 12 bits of a key (la_sticky_match.h), 16-bit indices");
 
 inline size_t up16(size_t x) { return (x + 15) & ~(size_t)15; }
 
@@ -80,43 +76,6 @@ constexpr size_t kStickyMaxLdsBytes = 8 * 2 * (size_t)kStickyMaxPartitions + 8 *
 static_assert((kStickyMaxPartitions & (kStickyMaxPartitions - 1)) == 0, "2 x the limit is the table of the largest topic");
 static_assert(kStickyMaxLdsBytes <= 160 * 1024, "one workgroup's LDS on gfx950");
 static_assert(kStickyThreads / kWave <= 4, "wave totals of a scan");
-
-// Exclusive scan of one value per thread over the workgroup, every thread calling: MAX = the maximum (of unsigned values, so 0
-// is the identity), otherwise the sum.  *total <- over all threads.  wave_tot: one LDS word per wavefront, free on return.
-template <bool MAX>
-__device__ __forceinline__ uint32_t workgroup_excl_scan(uint32_t v, uint32_t* wave_tot, int tid, int nt, uint32_t* total) {
-    const int lane = tid & (kWave - 1), wave = tid / kWave, n_waves = nt / kWave;
-    uint32_t incl = v;
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1) {
-        const uint32_t o = (uint32_t)__shfl_up((int)incl, d);
-        if (lane >= d) incl = MAX ? (o > incl ? o : incl) : incl + o;
-    }
-    if (lane == kWave - 1) wave_tot[wave] = incl;
-    __syncthreads();
-    uint32_t before = 0, all = 0;
-    for (int w = 0; w < n_waves; ++w) {
-        const uint32_t x = wave_tot[w];
-        if (w < wave) before = MAX ? (x > before ? x : before) : before + x;
-        all = MAX ? (x > all ? x : all) : all + x;
-    }
-    __syncthreads();
-    uint32_t excl = (uint32_t)__shfl_up((int)incl, 1);
-    if (lane == 0) excl = 0;
-    *total = all;
-    return MAX ? (excl > before ? excl : before) : before + excl;
-}
-
-// first index in [0, n) whose key is not below x (n when there is none); the interval shrinks whatever the keys hold
-__device__ __forceinline__ int first_not_below(const uint64_t* keys, int n, uint64_t x) {
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (keys[mid] < x) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
 
 struct StickyTally {            // thread 0: what this workgroup's topics add to the summary
     uint64_t before = 0, after = 0, changed = 0, passed = 0;

@@ -612,6 +612,20 @@ def cooperative_round_numpy(part_off, out_partition, out_member_rank, n_members:
     return adjusted + owned_after_round(part_off, out_partition, adjusted[1], n_members)
 
 
+def cooperative_round_sticky_numpy(part_off, partition_id, lag, out_partition, out_member_rank, n_members: int, owned_off, owned_topic,
+                                   owned_partition, *, max_partitions: int = STICKY_MAX_PARTITIONS):
+    """la_cooperative_round_sticky_device restated on the host, as the composition its header defines and nothing else:
+    cooperative_adjust_numpy on the target for prev_owner; sticky_ties_numpy with strict=False (a topic the device passes
+    through is passed through) and max_partitions (the batch's hint, where it lies below the limit); cooperative_round_numpy
+    with the sticky order in place of out_partition -> (sticky_partition int32[N], topic_kept int64[T], topic_saved int64[T],
+    sticky_summary int64[4]) followed by the eleven outputs of cooperative_round_numpy, which describe the STICKY order.
+    ValueError as cooperative_adjust_numpy.  The yardstick of tests/test_coop_sticky_gpu.py."""
+    prev_owner = cooperative_adjust_numpy(part_off, out_partition, out_member_rank, n_members, owned_off, owned_topic, owned_partition)[0]
+    sticky = sticky_ties_numpy(part_off, partition_id, lag, out_partition, out_member_rank, prev_owner,
+                               max_partitions=max_partitions, strict=False)
+    return sticky + cooperative_round_numpy(part_off, sticky[0], out_member_rank, n_members, owned_off, owned_topic, owned_partition)
+
+
 def assign_cooperative_numpy(part_off, partition_id, lag, cons_off, cons_rank, n_members: int, owned_off, owned_topic,
                              owned_partition, *, assign):
     """la_assign_batch_cooperative restated on the host: cooperative_round_numpy over the target that
@@ -621,6 +635,17 @@ def assign_cooperative_numpy(part_off, partition_id, lag, cons_off, cons_rank, n
     out_partition, out_member_rank, totals = assign(part_off, partition_id, lag, cons_off, cons_rank)
     return (out_partition, out_member_rank, totals) + cooperative_round_numpy(
         part_off, out_partition, out_member_rank, n_members, owned_off, owned_topic, owned_partition)
+
+
+def assign_cooperative_sticky_numpy(part_off, partition_id, lag, cons_off, cons_rank, n_members: int, owned_off, owned_topic,
+                                    owned_partition, *, assign):
+    """la_assign_batch_cooperative_sticky restated on the host: cooperative_round_sticky_numpy over the target that
+    assign(part_off, partition_id, lag, cons_off, cons_rank) -> (out_partition, out_member_rank, totals) produced -> those three
+    (the TARGET) followed by the fifteen outputs of cooperative_round_sticky_numpy (the sticky order).  `assign` is the caller's
+    restatement of the assign call; ValueError as cooperative_adjust_numpy."""
+    out_partition, out_member_rank, totals = assign(part_off, partition_id, lag, cons_off, cons_rank)
+    return (out_partition, out_member_rank, totals) + cooperative_round_sticky_numpy(
+        part_off, partition_id, lag, out_partition, out_member_rank, n_members, owned_off, owned_topic, owned_partition)
 
 
 def reduce_member_loads(partitions, lag, unassigned, group=None):
