@@ -39,6 +39,8 @@
  *                           returns -- every partition that changes hands between two live members withheld for this round
  *   la_sticky_ties_device   nothing in the reference, which orders partitions of equal lag by id: the same assignment with the
  *                           partitions of each run of equal lag re-matched to their previous owners
+ *   LA_FLAG_STICKY_LARGE / LA_COOP_STICKY_LARGE  nothing in the reference: la_sticky_ties_device for topics of more than 4096
+ *                           partitions too, re-matched through tables in device memory
  *   la_cooperative_round_sticky_device  nothing in the reference: la_cooperative_adjust_device, la_sticky_ties_device and
  *                           la_cooperative_round_device on the sticky order, chained by hand until now, in one call
  *   la_assign_batch_cooperative_sticky  nothing in the reference: la_assign_batch_cooperative with the round on the sticky order
@@ -166,6 +168,10 @@ extern "C" {
 #define LA_FLAG_VERIFY_LARGE 8192 /* la_verify_assignment_device[_on] only (every other entry ignores it): topics of more than 4096 partitions or  *
                                   * consumers are found from h_part_off / h_cons_off (then required) and verified through tables in device memory  *
                                   * instead of reading LA_VERDICT_UNCHECKED -- see that call.  It reads host memory and may allocate: not capturable */
+#define LA_FLAG_STICKY_LARGE 16384 /* la_sticky_ties_device and la_cooperative_round_sticky_device only      (every other entry ignores it): topics *
+                                   * of more than 4096 partitions are found from h_part_off (then required) and re-matched through tables in device *
+                                   * memory instead of being passed through -- see la_sticky_ties_device.  It reads host memory and may allocate:    *
+                                   * not capturable                                                                                              */
 #define LA_FLAG_SERIAL_LARGE 512 /* large path: the batch's large topics one after another (round 3's form) instead of side by   *
                                  * side in shared launches (test hook / A-B)                                            */
 
@@ -272,6 +278,7 @@ const char *la_last_error(const la_ctx *ctx);
  *                la_sticky_ties_device (among partitions of equal lag the previous owner keeps its own);
  *                la_cooperative_round_sticky_device (the cooperative round on the sticky order in one call);
  *                la_assign_batch_cooperative_sticky (a cooperative rebalance on the sticky order from host buffers);
+ *                LA_FLAG_STICKY_LARGE, LA_COOP_STICKY_LARGE (sticky ties for topics of any size);
  *                a shim detects them by symbol lookup (dlsym / getattr) instead of by version */
 #define LA_VERSION 500
 int la_version(void);
@@ -969,7 +976,34 @@ int la_assign_batch_cooperative(la_ctx *ctx, const la_assign_coop_args *args);
  * header: element alignment only, no write outside [0, N) / [0, T) / [0, 4), inputs never written.
  * The call runs on shard 0 of the context (buffers and stream on that shard's device, la_sync reports the errors); a form with a
  * shard argument is not part of this ABI yet.
+ * LA_FLAG_STICKY_LARGE (batch->flags): topics of ANY size.  Without the flag nothing above changes: no host array is read,
+ * nothing is allocated, large topics are passed through.  With it h_part_off is required and must ascend inside [0, N]
+ * (LA_EINVAL at the call otherwise, as LA_FLAG_VERIFY_LARGE checks it).  Topics within 4096 partitions behave exactly as without
+ * the flag, hint rules included.  Every topic of more than 4096 and at most LA_STICKY_GLOBAL_MAX_PARTITIONS (2^30 - 2)
+ * partitions is re-matched by the GLOBAL FORM, whatever the hint says: all of them side by side through tables in device
+ * memory -- the id join, the runs by a device-wide max-scan, the ranks inside (run, member) groups by the library's stable radix
+ * sort, the leftovers by a device-wide scan -- with results bit for bit those of rules 1-5; d_summary[3] then counts only the
+ * topics still passed through (a topic beyond 2^30 - 2 partitions: data, as before).  A BAD large topic (a duplicate input id, a
+ * foreign or repeated output id) is LA_EINVAL from la_sync and passed through exactly -- copied, kept after = kept before, saved
+ * 0, counted in d_summary[3] -- while every other topic of the call, large ones included, stays exact.  Every output word of a
+ * call that ends in LA_OK or LA_EINVAL is written exactly once.  Large topics are read through the HOST's offsets alone: where
+ * d_part_off[t] or d_part_off[t+1] differs from the host's for a large topic, or a topic is over the limit by the device's offsets
+ * but not by the host's, la_sync returns LA_ESHAPE and the outputs of that call are unspecified but stay inside the arrays.
+ * Launches (la_last_launches): at most 1 + LA_STICKY_GLOBAL_LAUNCHES (43), whatever the number and size of the large topics --
+ * ten phases of the global form's own, the sort's plan and at most eight digit passes (one launch each while the call's large
+ * topics hold fewer than 2^29 partitions together: 19 then; four each beyond).  A flagged call WITHOUT a large topic enqueues
+ * exactly what the unflagged call does and touches no scratch.  Working memory is a buffer of the shard's own, never the assign
+ * scratch (the results kept for la_group_last_by_member stay valid): 89 to 105 bytes per large-topic partition -- the table 16 to
+ * 32, the lag 8, four 32-bit words of matching state, two sort elements of 24 and their look-back granules -- plus 12 per 1024
+ * partitions and 32 per topic.  It is grown before anything is enqueued: LA_ENOMEM leaves nothing enqueued.  A limit of the CALL,
+ * beside the per-topic one: the sort takes two elements per large-topic partition and at most 2^31 - 1 elements, so the large
+ * topics of one call may hold 2^30 - 1 partitions TOGETHER (one topic of the largest size fits); a call beyond that is LA_ENOMEM
+ * with nothing enqueued -- its working memory would exceed 100 GiB -- not a pass-through: split it.  With large topics the flagged call reads host memory and may allocate:
+ * it must not be captured, and the flagged calls of one shard must be ordered among themselves (one stream, or events), as the
+ * calls with LA_FLAG_VERIFY_LARGE.
  * struct_size: sizeof(la_sticky_args) of the caller's header; less than this library's is LA_EINVAL.  reserved must be 0. */
+#define LA_STICKY_GLOBAL_LAUNCHES 43
+#define LA_STICKY_GLOBAL_MAX_PARTITIONS ((1 << 30) - 2)
 typedef struct la_sticky_args {
     int32_t struct_size;           /* sizeof(la_sticky_args) of the caller's header */
     int32_t reserved;              /* 0 */
@@ -1000,6 +1034,10 @@ int la_sticky_ties_device(la_ctx *ctx, const la_device_batch *batch, const la_st
  * inside the arrays; a topic that step 2 passes through (a duplicate input id, a foreign or repeated output id, a topic over
  * the hint or over 4096 partitions) keeps the reference's order.  T == 0, N == 0 and n_owned == 0 are valid; with n_owned == 0
  * d_sticky_partition equals d_out_partition.  Buffer contract as everywhere in this header.  The call runs on shard 0.
+ * LA_FLAG_STICKY_LARGE in batch->flags (h_part_off then required, checked at the call as in la_sticky_ties_device) reaches step 2
+ * of the GENERAL form: topics of more than 4096 partitions are re-matched there as that call describes, its launches added to
+ * the chain's; the sticky scratch is reserved together with the chain's other buffers, before the first launch.  The ONE
+ * WORKGROUP form holds N <= 2048 and so no large topic: the flag changes nothing there.
  * Two forms, the same results:
  *   ONE WORKGROUP  N <= LA_COOP_STICKY_ENTRIES (2048), n_owned <= LA_COOP_STICKY_OWNED (2048), M <= LA_COOP_STICKY_MEMBERS
  *                  (2046) and T <= LA_COOP_STICKY_TOPICS (2048), without LA_COOP_FORCE_TABLE.  EXACTLY ONE kernel launch
@@ -1017,6 +1055,7 @@ int la_sticky_ties_device(la_ctx *ctx, const la_device_batch *batch, const la_st
  * struct_size: sizeof(la_coop_sticky_args) of the caller's header; less than this library's is LA_EINVAL.  flags:
  * LA_COOP_FORCE_TABLE or 0, any other bit is LA_EINVAL.  round.adjust.reserved must be 0.  round.member_off NULL, or
  * round.grouped_partition NULL with N > 0, is LA_EINVAL. */
+#define LA_COOP_STICKY_LARGE 2   /* la_assign_batch_cooperative_sticky only: sticky ties for topics of any size (see that call) */
 #define LA_COOP_STICKY_ENTRIES 2048
 #define LA_COOP_STICKY_OWNED 2048
 #define LA_COOP_STICKY_MEMBERS 2046
@@ -1035,8 +1074,10 @@ int la_cooperative_round_sticky_device(la_ctx *ctx, const la_device_batch *batch
 /* A COOPERATIVE rebalance on the STICKY order in one host call: la_assign_batch_cooperative with the round replaced by the
  * sticky round above.  Every pointer is HOST memory.
  *   coop             exactly as for la_assign_batch_cooperative: the rebalance's inputs, the owned lists, the outputs.
- *                    coop.struct_size is not looked at; coop.flags is LA_COOP_FORCE_TABLE or 0, any other bit LA_EINVAL;
- *                    coop.reserved must be 0.
+ *                    coop.struct_size is not looked at; coop.flags holds LA_COOP_FORCE_TABLE and / or LA_COOP_STICKY_LARGE, any
+ *                    other bit LA_EINVAL; coop.reserved must be 0.  LA_COOP_STICKY_LARGE (this call alone takes it, every
+ *                    other call rejects it): the round runs with LA_FLAG_STICKY_LARGE and h_part_off = part_off, so topics
+ *                    of more than 4096 partitions are re-matched too; without it, they are passed through.
  *   out_partition, out_member_rank, out_total_lag (of coop)   describe the TARGET, in the reference's order, bit for bit what the
  *                    assign call returns for these inputs.
  *   sticky_partition, the eight adjust outputs and the three lists   describe the STICKY order: what

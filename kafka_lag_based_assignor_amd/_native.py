@@ -67,6 +67,15 @@ LA_COOP_STICKY_ENTRIES = COOP_STICKY_ENTRIES = 2048
 LA_COOP_STICKY_OWNED = COOP_STICKY_OWNED = 2048
 LA_COOP_STICKY_MEMBERS = COOP_STICKY_MEMBERS = 2046
 LA_COOP_STICKY_TOPICS = COOP_STICKY_TOPICS = 2048
+# la_sticky_ties_device / la_cooperative_round_sticky_device with LA_FLAG_STICKY_LARGE in the batch's flags (h_part_off then
+# required), la_assign_batch_cooperative_sticky with LA_COOP_STICKY_LARGE in coop.flags: topics of more than VERIFY_MAX_PARTITIONS
+# and up to STICKY_GLOBAL_MAX_PARTITIONS partitions are re-matched through tables in device memory instead of being passed
+# through, in at most STICKY_GLOBAL_LAUNCHES more kernel launches per call whatever their number and size (kStickyGlobalLaunches /
+# kStickyGlobalMaxPartitions of csrc/la_kernels.h; 19 while the call's large topics hold fewer than 2^29 partitions together)
+LA_FLAG_STICKY_LARGE = 16384
+LA_COOP_STICKY_LARGE = 2
+STICKY_GLOBAL_LAUNCHES = 43
+STICKY_GLOBAL_MAX_PARTITIONS = (1 << 30) - 2
 
 EXPORTED_SYMBOLS = (
     "la_create", "la_destroy", "la_last_error", "la_version", "la_compute_lag",
@@ -920,9 +929,12 @@ class Context:
         batch.d_out_partition, the ranks and totals stay as they are; d_topic_kept / d_topic_saved (int64[T]) and d_summary
         (int64[4]: kept before, kept after, topics changed, topics passed through) may be left out.  Enqueued on `stream`, at most
         one kernel; sync() reports duplicate or foreign ids (LA_EINVAL), a topic over its hint and offsets that leave the arrays
-        (LA_ESHAPE).  A topic of more than VERIFY_MAX_PARTITIONS partitions is passed through.  The C ABI has the call on shard 0
-        only: another shard needs a library that exports la_sticky_ties_device_on.  sharding.sticky_ties_numpy is the same on
-        the host."""
+        (LA_ESHAPE).  A topic of more than VERIFY_MAX_PARTITIONS partitions is passed through -- unless batch.flags carries
+        LA_FLAG_STICKY_LARGE (batch.h_part_off then required): such topics, up to STICKY_GLOBAL_MAX_PARTITIONS partitions, are
+        re-matched through tables in device memory in at most STICKY_GLOBAL_LAUNCHES more launches; that call reads host memory
+        and may allocate.  The C ABI has the call on shard 0 only: another shard needs a library that exports
+        la_sticky_ties_device_on.  sharding.sticky_ties_numpy, with max_partitions=STICKY_ANY_SIZE for the flagged call, is the
+        same on the host."""
         name = "la_sticky_ties_device" if not shard else "la_sticky_ties_device_on"
         fn = getattr(self._lib, name, None)
         if fn is None:
@@ -955,8 +967,10 @@ class Context:
         d_topic_kept / d_topic_saved (int64[T]) and d_sticky_summary (int64[4]) may be left out, and so may each of the eight
         adjust outputs; the round's outputs describe the sticky order.  Within COOP_STICKY_ENTRIES / _OWNED / _MEMBERS / _TOPICS
         it is ONE kernel launch without memset, allocation or scratch; otherwise, or with args.flags = LA_COOP_FORCE_TABLE, the
-        chain itself.  Errors are the union of the three calls'.  sharding.cooperative_round_sticky_numpy is the same on the
-        host."""
+        chain itself.  Errors are the union of the three calls'.  LA_FLAG_STICKY_LARGE in batch.flags (with batch.h_part_off)
+        reaches the chain's sticky step: topics of more than VERIFY_MAX_PARTITIONS partitions are re-matched as sticky_ties_device
+        describes.  sharding.cooperative_round_sticky_numpy (max_partitions=STICKY_ANY_SIZE for the flagged call) is the same on
+        the host."""
         fn = getattr(self._lib, "la_cooperative_round_sticky_device", None)
         if fn is None:
             raise LagAssignError(LA_EINVAL, "this liblagassign.so has no la_cooperative_round_sticky_device")
@@ -1028,12 +1042,14 @@ class Context:
     def assign_batch_cooperative_sticky(self, part_off, partition_id, cons_off, cons_rank, n_members: int, owned_off, owned_topic,
                                         owned_partition, *, lag=None, begin=None, end=None, committed=None, reset_mode: int = 0,
                                         none_index=None, none_begin=None, force_table: bool = False,
-                                        out: Optional[AssignSticky] = None) -> AssignSticky:
+                                        out: Optional[AssignSticky] = None, large: bool = False) -> AssignSticky:
         """la_assign_batch_cooperative_sticky: assign_batch_cooperative with the round on the STICKY order (partitions of equal
         lag stay with their previous owner).  Same inputs; returns an AssignSticky: .coop.out_partition / out_member_rank /
         totals describe the TARGET, every other entry of .coop and sticky_partition / topic_kept / topic_saved / sticky_summary
         the sticky order; `out` = caller-owned buffers in that shape (None entries of out.coop are not computed).
-        sharding.assign_cooperative_sticky_numpy is the same on the host."""
+        large: LA_COOP_STICKY_LARGE -- topics of more than VERIFY_MAX_PARTITIONS partitions are re-matched too instead of being
+        passed through.  sharding.assign_cooperative_sticky_numpy (max_partitions=STICKY_ANY_SIZE for large) is the same on the
+        host."""
         fn = getattr(self._lib, "la_assign_batch_cooperative_sticky", None)
         if fn is None:
             raise LagAssignError(LA_EINVAL, "this liblagassign.so has no la_assign_batch_cooperative_sticky")
@@ -1042,6 +1058,8 @@ class Context:
         coop = self._fill_assign_coop(a.coop, part_off, partition_id, cons_off, cons_rank, n_members, owned_off, owned_topic,
                                       owned_partition, lag, begin, end, committed, reset_mode, none_index, none_begin, force_table,
                                       None if out is None else out.coop)
+        if large:
+            a.coop.flags |= LA_COOP_STICKY_LARGE
         n, t = coop.grouped_partition.size, _a64(part_off).size - 1
         if out is None:
             out = AssignSticky(coop, np.empty(n, np.int32), np.empty(t, np.int64), np.empty(t, np.int64), np.empty(4, np.int64))

@@ -47,12 +47,18 @@ class LagBasedPartitionAssignor:
     # -- plugin surface -------------------------------------------------------------
     def configure(self, configs: Mapping[str, object]) -> None:
         """Main.java:97-130.  Raises ValueError (IllegalArgumentException) without group.id.  ``lag.assignor.sticky.ties``
-        (a boolean, default false): assign_cooperative() keeps partitions of equal lag with their previous owner."""
+        (a boolean, default false): assign_cooperative() keeps partitions of equal lag with their previous owner.
+        ``lag.assignor.sticky.ties.large`` (a boolean, default false, no effect unless the former is on): topics of more than
+        4096 partitions are re-matched too instead of keeping the reference's order."""
         self._impl.configure({str(k): str(v) for k, v in configs.items()})
 
     def sticky_ties(self) -> bool:
         """``lag.assignor.sticky.ties`` as configure() read it."""
         return bool(self._impl.sticky_ties())
+
+    def sticky_ties_large(self) -> bool:
+        """``lag.assignor.sticky.ties.large`` as configure() read it."""
+        return bool(self._impl.sticky_ties_large())
 
     def name(self) -> str:
         return self._impl.name()

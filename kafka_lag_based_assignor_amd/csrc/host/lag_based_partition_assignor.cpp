@@ -160,7 +160,7 @@ void hint_bounds(la_ctx* ctx, const Flat& f) {
 Assignment run_native(const Plan& plan, const std::vector<const TopicData*>& data, bool offsets_mode,
                       int32_t reset_mode, std::map<std::string, std::map<std::string, int64_t>>* totals_out,
                       const std::function<void(const std::string&)>* debug = nullptr, const OwnedArrays* owned = nullptr,
-                      bool sticky = false) {
+                      bool sticky = false, bool sticky_large = false) {
     Flat f;
     for (size_t t = 0; t < plan.topics.size(); ++t) {
         const TopicData* d = data[t];
@@ -241,6 +241,7 @@ Assignment run_native(const Plan& plan, const std::vector<const TopicData*>& dat
             la_assign_sticky_args sa{};
             sa.struct_size = (int32_t)sizeof sa;
             sa.coop = a;
+            if (sticky_large) sa.coop.flags |= LA_COOP_STICKY_LARGE;      // lag.assignor.sticky.ties.large: topics of any size
             sa.sticky_summary = sticky_summary.data();
             check(ctx, la_assign_batch_cooperative_sticky(ctx, &sa));
         } else {
@@ -396,6 +397,15 @@ void LagBasedPartitionAssignor::configure(const std::map<std::string, std::strin
         std::string v = sticky->second;
         for (char& ch : v) ch = (char)std::tolower((unsigned char)ch);
         sticky_ties_ = v == "true";
+    }
+    // lag.assignor.sticky.ties.large: read the same way, default false, no effect unless the key above is on -- topics of more
+    // than 4096 partitions are re-matched too (LA_COOP_STICKY_LARGE) instead of keeping the reference's order
+    auto sticky_large = consumer_group_props_.find("lag.assignor.sticky.ties.large");
+    sticky_ties_large_ = false;
+    if (sticky_large != consumer_group_props_.end()) {
+        std::string v = sticky_large->second;
+        for (char& ch : v) ch = (char)std::tolower((unsigned char)ch);
+        sticky_ties_large_ = v == "true";
     }
 }
 
@@ -558,7 +568,7 @@ Assignment LagBasedPartitionAssignor::assignImpl(const Cluster& metadata, const 
         std::vector<std::vector<TopicPartition>> per_member;
         for (const std::string& m : plan.members) per_member.push_back(*of.at(m));
         const OwnedArrays arrays = cooperativeOwnedArrays(plan.members, plan.topics, per_member);
-        return run_native(plan, data, true, reset, &last_totals_, &debug, &arrays, sticky_ties_);
+        return run_native(plan, data, true, reset, &last_totals_, &debug, &arrays, sticky_ties_, sticky_ties_ && sticky_ties_large_);
     }
     return run_native(plan, data, true, reset, &last_totals_, &debug);           // wrap: :152-156
 }

@@ -133,6 +133,8 @@ class LagBasedPartitionAssignor {
     const std::map<std::string, std::string>& metadataConsumerProps() const { return metadata_consumer_props_; }
     // lag.assignor.sticky.ties as configure() read it (default false)
     bool stickyTies() const { return sticky_ties_; }
+    // lag.assignor.sticky.ties.large as configure() read it (default false; it has no effect unless stickyTies())
+    bool stickyTiesLarge() const { return sticky_ties_large_; }
 
     // The accessors below describe the TARGET (the eager assignment) after assignCooperative, exactly as after assign().
     // Per-topic consumer totals of the last instance-level assign (the debug summary's
@@ -185,6 +187,7 @@ class LagBasedPartitionAssignor {
     std::map<std::string, std::string> consumer_group_props_;
     std::map<std::string, std::string> metadata_consumer_props_;
     bool sticky_ties_ = false;                                           // lag.assignor.sticky.ties
+    bool sticky_ties_large_ = false;                                     // lag.assignor.sticky.ties.large
     std::map<std::string, std::map<std::string, int64_t>> last_totals_;
     bool last_order_exact_ = true;
 };

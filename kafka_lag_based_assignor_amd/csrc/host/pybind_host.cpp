@@ -111,6 +111,7 @@ PYBIND11_MODULE(_host, m) {
         .def(py::init<>())
         .def("configure", &LagBasedPartitionAssignor::configure)
         .def("sticky_ties", &LagBasedPartitionAssignor::stickyTies)
+        .def("sticky_ties_large", &LagBasedPartitionAssignor::stickyTiesLarge)
         .def("name", &LagBasedPartitionAssignor::name)
         .def("metadata_consumer_props", &LagBasedPartitionAssignor::metadataConsumerProps)
         .def("last_topic_totals", &LagBasedPartitionAssignor::lastTopicTotals)

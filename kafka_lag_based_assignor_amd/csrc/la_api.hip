@@ -599,6 +599,7 @@ LA_API void la_destroy(la_ctx* ctx) {
             if (h->p) (void)hipHostFree(h->p);
         la::moves_scratch_release(sh.moves);
         la::verify_scratch_release(sh.verify);
+        la::sticky_scratch_release(sh.sticky);
         la::coop_scratch_release(sh.coop);
         if (sh.ready) (void)hipEventDestroy(sh.ready);
         for (hipEvent_t e : sh.chunk_ev) (void)hipEventDestroy(e);
@@ -1116,8 +1117,21 @@ LA_API int la_verify_assignment_device_on(la_ctx* ctx, int shard, const la_devic
     });
 }
 
-// Sticky ties (la_sticky.hip), on shard 0.  Owns no scratch: everything lives in the workgroups' LDS and the caller's outputs, so
-// the call can be captured and the results kept for la_group_last_by_member stay as they are.
+// The host offsets a flagged call reads its large topics through: they ascend inside [0, n_partitions] (as verify checks them)
+static int sticky_large_offsets_ok(la_ctx* ctx, const la_device_batch& b) {
+    if (!b.h_part_off) return fail(ctx, LA_EINVAL, "LA_FLAG_STICKY_LARGE: h_part_off is required");
+    for (int32_t t = 0; t <= b.n_topics; ++t) {
+        const int64_t p = b.h_part_off[t];
+        if (p < 0 || p > b.n_partitions || (t > 0 && p < b.h_part_off[t - 1]))
+            return fail(ctx, LA_EINVAL, "LA_FLAG_STICKY_LARGE: h_part_off must ascend inside [0, n_partitions] (topic %d)", t < b.n_topics ? t : t - 1);
+    }
+    return LA_OK;
+}
+
+// Sticky ties (la_sticky.hip).  Without LA_FLAG_STICKY_LARGE it owns no scratch: everything lives in the workgroups' LDS and the
+// caller's outputs, so the call can be captured.  With the flag the topics over the LDS limit go through tables in device memory
+// (la_sticky_large.hip) -- the shard's own buffer, not the assign scratch.  Either way the results kept for
+// la_group_last_by_member stay as they are.  On shard 0, like the cooperative calls.
 LA_API int la_sticky_ties_device(la_ctx* ctx, const la_device_batch* batch, const la_sticky_args* args, void* stream) {
     return shard_entry<true>(ctx, 0, "exception in la_sticky_ties_device", [&](Shard& sh) -> int {
         if (!batch) return fail(ctx, LA_EINVAL, "batch is NULL");
@@ -1159,7 +1173,10 @@ LA_API int la_sticky_ties_device(la_ctx* ctx, const la_device_batch* batch, cons
         c.topic_kept = g.d_topic_kept;
         c.topic_saved = g.d_topic_saved;
         c.summary = g.d_summary;
-        hipError_t e = la::sticky_ties_launch(c, sh.lanes[0].d_status, (hipStream_t)stream);
+        const bool large = (b.flags & LA_FLAG_STICKY_LARGE) != 0;
+        if (large)
+            if (int rc = sticky_large_offsets_ok(ctx, b)) return rc;
+        hipError_t e = la::sticky_ties_launch(c, sh.lanes[0].d_status, (hipStream_t)stream, large ? &sh.sticky : nullptr, b.h_part_off);
         return e != hipSuccess ? hip_fail(ctx, e, "sticky_ties: %s") : LA_OK;
     });
 }
@@ -1214,7 +1231,8 @@ LA_API int la_cooperative_adjust_device(la_ctx* ctx, const la_coop_args* args, v
     });
 }
 
-static_assert(LA_COOP_FORCE_TABLE == 1, "lagassign.h");
+static_assert(LA_COOP_FORCE_TABLE == 1 && LA_COOP_STICKY_LARGE == 2, "lagassign.h");
+static_assert(LA_STICKY_GLOBAL_LAUNCHES == la::kStickyGlobalLaunches && LA_STICKY_GLOBAL_MAX_PARTITIONS == la::kStickyGlobalMaxPartitions, "lagassign.h");
 
 // a la_coop_round_args, checked: the adjust part as above, the lists' own pointers, the flags
 static int coop_round_call_of(la_ctx* ctx, const la_coop_round_args* args, la::CoopRoundCall* out) {
@@ -1317,6 +1335,10 @@ static int coop_sticky_call_of(la_ctx* ctx, const la_device_batch* batch, const 
     c.topic_kept = args->d_topic_kept;
     c.topic_saved = args->d_topic_saved;
     c.summary = args->d_sticky_summary;
+    if (b.flags & LA_FLAG_STICKY_LARGE) {            // step 2 of the chain re-matches the large topics too
+        if (int rc = sticky_large_offsets_ok(ctx, b)) return rc;
+        k.h_part_off = b.h_part_off;
+    }
     *out = k;
     return LA_OK;
 }
@@ -1327,7 +1349,7 @@ LA_API int la_cooperative_round_sticky_device(la_ctx* ctx, const la_device_batch
     return shard_entry<true>(ctx, 0, "exception in la_cooperative_round_sticky_device", [&](Shard& sh) -> int {
         la::CoopStickyCall k{};
         if (int rc = coop_sticky_call_of(ctx, batch, args, &k)) return rc;
-        hipError_t e = la::cooperative_round_sticky_launch(sh.coop, sh.lanes[0].large, k, (args->flags & LA_COOP_FORCE_TABLE) != 0,
+        hipError_t e = la::cooperative_round_sticky_launch(sh.coop, sh.sticky, sh.lanes[0].large, k, (args->flags & LA_COOP_FORCE_TABLE) != 0,
                                                            sh.lanes[0].d_status, (hipStream_t)stream);
         return e != hipSuccess ? hip_fail(ctx, e, "cooperative_round_sticky: %s") : LA_OK;
     });
@@ -1552,7 +1574,7 @@ LA_API int la_assign_batch_cooperative_sticky(la_ctx* ctx, const la_assign_stick
             return fail(ctx, LA_EINVAL, "la_assign_sticky_args.struct_size is %d, this library takes %d and above", (int)args->struct_size, (int)sizeof(la_assign_sticky_args));
         if (args->reserved != 0) return fail(ctx, LA_EINVAL, "la_assign_sticky_args.reserved must be 0");
         const la_assign_coop_args* g = &args->coop;
-        if (g->flags & ~LA_COOP_FORCE_TABLE) return fail(ctx, LA_EINVAL, "la_assign_sticky_args.coop.flags holds a bit this library does not know");
+        if (g->flags & ~(LA_COOP_FORCE_TABLE | LA_COOP_STICKY_LARGE)) return fail(ctx, LA_EINVAL, "la_assign_sticky_args.coop.flags holds a bit this library does not know");
         if (g->reserved != 0) return fail(ctx, LA_EINVAL, "la_assign_coop_args.reserved must be 0");
         if (g->n_topics < 0 || g->n_members < 0 || g->n_owned < 0) return fail(ctx, LA_EINVAL, "negative size");
         if (g->n_members > la::kMovesMaxMembers) return fail(ctx, LA_EINVAL, "n_members must be below 2^30");
@@ -1643,6 +1665,10 @@ LA_API int la_assign_batch_cooperative_sticky(la_ctx* ctx, const la_assign_stick
         b.reset_mode = latest ? LA_RESET_LATEST : g->reset_mode;
         b.n_partitions = N;
         b.max_partitions_per_topic = hint;
+        if ((g->flags & LA_COOP_STICKY_LARGE) && T > 0) {
+            b.flags |= LA_FLAG_STICKY_LARGE;
+            b.h_part_off = g->part_off;
+        }
         b.d_part_off = T > 0 ? (int64_t*)(dp + i_part_off) : nullptr;
         b.d_partition_id = Ns ? (int32_t*)(dp + i_input_id) : nullptr;
         b.d_lag = g->lag && Ns ? (int64_t*)(dp + i_lag) : nullptr;
@@ -1653,7 +1679,7 @@ LA_API int la_assign_batch_cooperative_sticky(la_ctx* ctx, const la_assign_stick
         b.d_out_member_rank = Ns ? (int32_t*)(dp + i_rank) : nullptr;
         la_coop_sticky_args a{};
         a.struct_size = (int32_t)sizeof a;
-        a.flags = g->flags;
+        a.flags = g->flags & LA_COOP_FORCE_TABLE;
         la_coop_args& adj = a.round.adjust;
         adj.n_members = g->n_members;
         adj.n_owned = g->n_owned;
@@ -1680,7 +1706,7 @@ LA_API int la_assign_batch_cooperative_sticky(la_ctx* ctx, const la_assign_stick
         Lane& ln = sh.lanes[0];
         hipStream_t st = ln.stream;
         if (in_bytes) LA_HIP(ctx, hipMemcpyAsync(dp, hp, in_bytes, hipMemcpyHostToDevice, st));
-        hipError_t e = la::cooperative_round_sticky_launch(s, ln.large, k, (g->flags & LA_COOP_FORCE_TABLE) != 0, ln.d_status, st);
+        hipError_t e = la::cooperative_round_sticky_launch(s, sh.sticky, ln.large, k, (g->flags & LA_COOP_FORCE_TABLE) != 0, ln.d_status, st);
         if (e != hipSuccess) {
             (void)hipStreamSynchronize(st);
             return hip_fail(ctx, e, "cooperative_round_sticky: %s");

@@ -113,6 +113,7 @@ constexpr int kCoopStickyTopics = kCoopSmallTopics;     // T: T + 1 part offsets
 struct CoopStickyCall {         // la_device_batch + la_coop_sticky_args (lagassign.h), validated
     StickyCall s;               // the batch as la_sticky_ties_device reads it and its four outputs; prev_owner is not looked at
     CoopRoundCall r;            // the round; r.c's target (n_topics, n_partitions, part_off, out_partition, out_member_rank) is s's
+    const int64_t* h_part_off = nullptr;      // non-null: LA_FLAG_STICKY_LARGE, the host's offsets (validated) for sticky_ties_launch
 };
 
 inline bool coop_sticky_is_small(const CoopCall& c) {
@@ -122,9 +123,9 @@ inline bool coop_sticky_is_small(const CoopCall& c) {
 
 // The one-workgroup form (coop_sticky_is_small) unless force_table: exactly one launch, a topic over the batch's hint is passed
 // through by the kernel itself (kStatusShape).  Otherwise the three launchers in turn, the previous owners in s.prev and, when
-// the caller wants no adjusted ranks, s.ranks -- both grown before anything is enqueued (hipErrorOutOfMemory then).  Sets
-// kStatusCoop / kStatusSticky / kStatusShape / kStatusInternal.
-hipError_t cooperative_round_sticky_launch(CoopScratch& s, LargeScratch& large, const CoopStickyCall& k, bool force_table,
+// the caller wants no adjusted ranks, s.ranks -- both, and with k.h_part_off the sticky scratch of the large topics, grown before
+// anything is enqueued (hipErrorOutOfMemory then).  Sets kStatusCoop / kStatusSticky / kStatusShape / kStatusInternal.
+hipError_t cooperative_round_sticky_launch(CoopScratch& s, StickyScratch& sticky, LargeScratch& large, const CoopStickyCall& k, bool force_table,
                                            uint32_t* status, hipStream_t stream);
 
 }  // namespace la

@@ -538,7 +538,7 @@ __global__ __launch_bounds__(NT) void coop_sticky_small_kernel(CoopStickySmallAr
 
 }  // namespace
 
-hipError_t cooperative_round_sticky_launch(CoopScratch& sc, LargeScratch& large, const CoopStickyCall& k, bool force_table,
+hipError_t cooperative_round_sticky_launch(CoopScratch& sc, StickyScratch& sticky, LargeScratch& large, const CoopStickyCall& k, bool force_table,
                                            uint32_t* status, hipStream_t stream) {
     hipError_t e;
     const CoopCall& c = k.r.c;
@@ -559,6 +559,8 @@ hipError_t cooperative_round_sticky_launch(CoopScratch& sc, LargeScratch& large,
         if ((e = grow_device(&sc.prev, &sc.prev_cap, (size_t)N * 4)) != hipSuccess) return e;
         if (!c.coop_rank && (e = grow_device(&sc.ranks, &sc.ranks_cap, (size_t)N * 4)) != hipSuccess) return e;
     }
+    const bool sticky_large = k.h_part_off != nullptr && k.s.n_topics > 0;
+    if (sticky_large && (e = sticky_large_reserve(sticky, k.s, k.h_part_off)) != hipSuccess) return e;
     CoopCall first = c;                             // the target against the owned lists, wanting only the previous owners
     first.prev_owner = static_cast<int32_t*>(sc.prev);
     first.coop_rank = nullptr;
@@ -566,7 +568,7 @@ hipError_t cooperative_round_sticky_launch(CoopScratch& sc, LargeScratch& large,
     if ((e = cooperative_adjust_launch(sc, first, status, stream)) != hipSuccess) return e;
     StickyCall s = k.s;
     s.prev_owner = static_cast<const int32_t*>(sc.prev);
-    if ((e = sticky_ties_launch(s, status, stream)) != hipSuccess) return e;
+    if ((e = sticky_ties_launch(s, status, stream, sticky_large ? &sticky : nullptr, k.h_part_off, true)) != hipSuccess) return e;
     CoopRoundCall r = k.r;                          // the round on the sticky order
     r.c.out_partition = s.sticky;
     return cooperative_round_launch(sc, large, r, force_table, status, stream);

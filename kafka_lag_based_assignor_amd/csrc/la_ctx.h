@@ -98,6 +98,7 @@ struct Shard {
     HostBuf small_h, small_gh;
     la::MovesScratch moves;              // la_assignment_moves_device: the global form's table and topic list
     la::VerifyScratch verify;            // la_verify_assignment_device with LA_FLAG_VERIFY_LARGE: the global form's tables and topic list
+    la::StickyScratch sticky;            // la_sticky_ties_device with LA_FLAG_STICKY_LARGE: the global form's tables, sort buffers and topic list
     la::CoopScratch coop;                // la_cooperative_adjust_device: the (topic, id) table of the owned lists
     HostBuf zc_h;                        // zero-copy small calls: coherent, device-mapped staging the kernels read and write in place
     // pinned caller arrays (la_host_alloc): one host thread, three streams -- every H2D of the call in order on copy_in,

@@ -1,4 +1,5 @@
-// la_join.h -- the per-topic hash join on a partition id, shared by la_moves.hip, la_moves_layouts.hip, la_verify.hip and la_sticky.hip.
+// la_join.h -- the per-topic hash join on a partition id, shared by la_moves.hip, la_moves_layouts.hip, la_verify.hip, la_sticky.hip and
+// la_sticky_large.hip.
 //
 // An open-addressing table keyed by the id:
 //

@@ -373,7 +373,8 @@ void verify_scratch_release(VerifyScratch& s);
 
 // ---- sticky ties: the previous owner decides among partitions of equal lag (la_sticky.hip) ------------------------------------
 // One workgroup re-matches a topic in LDS, up to kVerifyMaxPartitions partitions as the verify call: the id join, the topic's
-// lags, both rank arrays and two arrays of sort keys -- 136 KiB at the limit.  A larger topic is passed through.
+// lags, both rank arrays and two arrays of sort keys -- 136 KiB at the limit.  A larger topic is passed through, or, with
+// LA_FLAG_STICKY_LARGE, re-matched by the global form below.
 struct StickyCall {             // la_device_batch + la_sticky_args (lagassign.h) as la_sticky_ties_device reads them, validated
     int32_t n_topics, reset_latest;
     int64_t n_partitions, max_partitions_per_topic;
@@ -387,7 +388,65 @@ struct StickyCall {             // la_device_batch + la_sticky_args (lagassign.h
     int64_t* summary;           // [4] or null
 };
 
+// ---- sticky ties of topics beyond the LDS limit (la_sticky_large.hip, LA_FLAG_STICKY_LARGE) -------------------------------------
+// The global form: all topics of a call with more than kVerifyMaxPartitions partitions side by side, the phases of the LDS kernel
+// as launches over tables in device memory, the (run, member) ranks from the radix sort of la_radix.h.
+constexpr int64_t kStickyGlobalMaxPartitions = kVerifyGlobalMaxPartitions;      // the join's payload, as in verify
+// The sort takes two elements per partition and 2^31 - 1 elements: the large topics of ONE call hold at most this many partitions
+// together (beyond it: hipErrorOutOfMemory, nothing enqueued -- the working memory would be ~100 GiB)
+constexpr int64_t kStickyGlobalMaxTotal = (1 << 30) - 1;
+// insert | lookup | run heads: chunk maxima | their scan | run starts + sort keys  (5)
+// the sort's plan + 8 digit passes: 4 member digits, 4 run-start digits; a pass is ONE launch below 2^30 sort elements, else 4  (1 + 8 x 4)
+// match | leftovers: chunk sums | their scan | leftover ranks | emit  (5)
+constexpr int kStickyOwnLaunches = 10;
+constexpr int kStickyGlobalLaunches = kStickyOwnLaunches + 1 + 8 * 4;      // 43; 19 while a call's large topics stay below 2^29 partitions
+constexpr int kStickyMaxLaunches = 1 + kStickyGlobalLaunches;             // what la_last_launches reports at most (lagassign.h)
+constexpr uint32_t kStickyBigBad = 1u, kStickyBigChanged = 2u;            // StickyWork::ctr[4 j + 2]
+
+struct StickyBig {              // one topic of the global form; every offset and size is the HOST's, inside [0, N]
+    int64_t p0, np;             // its segment of the batch
+    int64_t q0;                 // its first position in the concatenated list of all large topics' positions
+    int64_t table0;             // its table region, in slots
+    int64_t step0;              // its first workgroup step (kStickyStep positions each), numbered through the topics
+    int32_t topic, bits;        // the table region has 1 << bits slots
+};
+
+struct StickyWork {             // the global form's device memory, as the kernels see it (every pointer a kernel argument)
+    uint64_t* table;
+    int64_t* lag;               // [L] the lag at every position of the concatenated list
+    unsigned long long* ctr;    // [4 n_big] kept before | kept after | kStickyBig* bits | unused, of every large topic
+    unsigned long long* tot;    // [2] partitions not placed | positions not filled, over the whole list
+    uint32_t *placed, *src_of, *hole_rank, *loose;      // [L] each
+    uint32_t *cmax, *csum_loose, *csum_hole;            // [n_steps] each: one word per chunk (= step) of the two-level scans
+    const StickyBig* big;       // ascending in topic
+    int32_t n_big;
+    int64_t n_pos, n_steps;     // L; workgroup steps
+};
+
+struct StickyScratch {          // of one shard, grown lazily: never the assign scratch (results kept on the device stay valid)
+    void* work = nullptr;       // tables, per-position arrays and the sort's buffers, one allocation carved into regions
+    size_t work_cap = 0;
+    StagedList list;            // its topic list
+    // what sticky_large_reserve found for the call it was made for (host arithmetic only)
+    int64_t n_big = 0, n_pos = 0, n_steps = 0;
+    size_t n_table = 0;
+};
+
+// Lists the topics of more than kVerifyMaxPartitions (and at most kStickyGlobalMaxPartitions) partitions from the host's offsets
+// (validated by the caller: ascending inside [0, N]) into s.list and grows s.work for them.  Enqueues nothing; s.n_big == 0
+// afterwards: the batch holds no such topic and nothing was touched.  hipErrorOutOfMemory when the memory cannot be had.
+hipError_t sticky_large_reserve(StickyScratch& s, const StickyCall& c, const int64_t* h_part_off);
+// The global form behind a reserve for the same call: at most kStickyGlobalLaunches launches.  *out: what the LDS kernel, which
+// runs last, needs to record these topics' counts.
+hipError_t sticky_large_enqueue(StickyScratch& s, const StickyCall& c, uint32_t* status, hipStream_t stream, StickyWork* out);
+void sticky_scratch_release(StickyScratch& s);
+
 // Zeroes the summary on `stream`, then at most ONE launch.  Sets kStatusSticky / kStatusShape / kStatusInternal.
-hipError_t sticky_ties_launch(const StickyCall& c, uint32_t* status, hipStream_t stream);
+// With `large` (LA_FLAG_STICKY_LARGE; h_part_off validated by the caller) the topics over the limit are re-matched by the global
+// form in front of that launch: at most kStickyGlobalLaunches more, whatever their number and size; `reserved`: the caller has
+// called sticky_large_reserve for this call already.  Without a large topic the flagged call enqueues what the unflagged one
+// does and touches no scratch.
+hipError_t sticky_ties_launch(const StickyCall& c, uint32_t* status, hipStream_t stream, StickyScratch* large = nullptr,
+                              const int64_t* h_part_off = nullptr, bool reserved = false);
 
 }  // namespace la

@@ -23,6 +23,8 @@
 //   7  sticky[d] = out_partition[src_of[d], or loose[hole_rank[d]]]; count kept after
 //   8  per-topic counts by plain stores (thread 0), the summary once per workgroup
 // A BAD topic, one over the limit and one over the hint are PASSED THROUGH: sticky = a copy, kept after = kept before.
+// With LA_FLAG_STICKY_LARGE the topics over the limit that the host listed have been re-matched by the global form
+// (la_sticky_large.hip) in front of this kernel: for those it only stores the counts that form left and adds them to the summary.
 // Every phase is safe on any content: an index comes from the join's own payload, a bisection or a scan, never from an id or a
 // rank; a topic leaves nothing behind -- every word a later topic reads it has written itself behind a barrier.  Accesses are
 // one element wide.  No thread waits for another except at a barrier; every loop is bounded.
@@ -49,6 +51,8 @@ inline size_t up16(size_t x) { return (x + 15) & ~(size_t)15; }
 struct StickyArgs {
     StickyCall c;
     uint32_t* status;
+    StickyWork g;               // n_big == 0: no topic went through the global form (la_sticky_large.hip)
+    int32_t large;              // LA_FLAG_STICKY_LARGE: a topic the global form takes that is not in its list is a shape error
     int32_t cap_p;              // partitions of a topic the LDS request holds
     uint32_t off_lag, off_own, off_prev, off_src, off_ctl;      // byte offsets of the regions behind A
 };
@@ -145,8 +149,32 @@ __global__ __launch_bounds__(kStickyThreads) void sticky_kernel(StickyArgs a) {
             bad |= kStatusShape;
             continue;
         }
+        if (a.g.n_big > 0) {                        // a topic of the host's list: the global form has written its order and left its counts
+            int lo = 0, hi = a.g.n_big;
+            while (hi - lo > 1) {
+                const int mid = (lo + hi) >> 1;
+                if ((int64_t)a.g.big[mid].topic <= t) lo = mid;
+                else hi = mid;
+            }
+            if ((int64_t)a.g.big[lo].topic == t) {
+                if (a.g.big[lo].p0 != p0 || a.g.big[lo].np != np) {      // it worked from the host's offsets, these are others
+                    bad |= kStatusShape;
+                    continue;
+                }
+                if (tid == 0) {
+                    const uint32_t bits = (uint32_t)a.g.ctr[4 * lo + 2];
+                    kept[0] = a.g.ctr[4 * lo + 0];
+                    kept[1] = a.g.ctr[4 * lo + 1];
+                    if (bits & kStickyBigChanged) *topic_flags = kTopicChanged;
+                    if (bits & kStickyBigBad) bad |= kStatusSticky;
+                }
+                const bool big_bad = (a.g.ctr[4 * lo + 2] & kStickyBigBad) != 0;
+                finish(t, big_bad, big_bad);
+                continue;
+            }
+        }
         if (np > a.cap_p) {                         // over the limit: data; within the limit but over the hint: an error as well
-            if (np <= kStickyMaxPartitions) bad |= kStatusShape;
+            if (np <= kStickyMaxPartitions || (a.large && np <= kStickyGlobalMaxPartitions)) bad |= kStatusShape;      // (the host's list would have held it)
             copy_topic(p0, np, true);
             finish(t, true, true);
             continue;
@@ -319,8 +347,15 @@ __global__ __launch_bounds__(kStickyThreads) void sticky_kernel(StickyArgs a) {
 
 }  // namespace
 
-hipError_t sticky_ties_launch(const StickyCall& c, uint32_t* status, hipStream_t stream) {
+hipError_t sticky_ties_launch(const StickyCall& c, uint32_t* status, hipStream_t stream, StickyScratch* large,
+                              const int64_t* h_part_off, bool reserved) {
     hipError_t e;
+    StickyWork g{};
+    // the global form first: the LDS kernel behind it stores and counts its topics' results too
+    if (large && c.n_topics > 0) {
+        if (!reserved && (e = sticky_large_reserve(*large, c, h_part_off)) != hipSuccess) return e;
+        if ((e = sticky_large_enqueue(*large, c, status, stream, &g)) != hipSuccess) return e;
+    }
     if (c.summary && (e = hipMemsetAsync(c.summary, 0, 32, stream)) != hipSuccess) return e;
     if (c.n_topics <= 0) return hipSuccess;
 
@@ -329,6 +364,8 @@ hipError_t sticky_ties_launch(const StickyCall& c, uint32_t* status, hipStream_t
     StickyArgs a{};
     a.c = c;
     a.status = status;
+    a.g = g;
+    a.large = large ? 1 : 0;
     a.cap_p = (int32_t)(hint <= 0 || hint > kStickyMaxPartitions ? kStickyMaxPartitions : hint);
     const StickyLayout l = layout_for(a.cap_p);
     a.off_lag = l.off_lag;

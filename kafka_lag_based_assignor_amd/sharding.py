@@ -423,6 +423,9 @@ def verify_assignment_numpy(part_off, partition_id, cons_off, cons_rank, out_par
 
 
 STICKY_MAX_PARTITIONS = 4096      # topics beyond it are passed through by la_sticky_ties_device (kVerifyMaxPartitions of csrc/la_kernels.h)
+# max_partitions of the functions below for a call with LA_FLAG_STICKY_LARGE / LA_COOP_STICKY_LARGE: no limit -- what the device
+# re-matches then (kStickyGlobalMaxPartitions of csrc/la_kernels.h; nothing a host array holds reaches it)
+STICKY_ANY_SIZE = (1 << 30) - 2
 
 
 def sticky_ties_numpy(part_off, partition_id, lag, out_partition, out_member_rank, prev_owner, *,
@@ -638,14 +641,16 @@ def assign_cooperative_numpy(part_off, partition_id, lag, cons_off, cons_rank, n
 
 
 def assign_cooperative_sticky_numpy(part_off, partition_id, lag, cons_off, cons_rank, n_members: int, owned_off, owned_topic,
-                                    owned_partition, *, assign):
+                                    owned_partition, *, assign, max_partitions: int = STICKY_MAX_PARTITIONS):
     """la_assign_batch_cooperative_sticky restated on the host: cooperative_round_sticky_numpy over the target that
     assign(part_off, partition_id, lag, cons_off, cons_rank) -> (out_partition, out_member_rank, totals) produced -> those three
     (the TARGET) followed by the fifteen outputs of cooperative_round_sticky_numpy (the sticky order).  `assign` is the caller's
-    restatement of the assign call; ValueError as cooperative_adjust_numpy."""
+    restatement of the assign call; max_partitions goes to cooperative_round_sticky_numpy (STICKY_ANY_SIZE: the call with
+    LA_COOP_STICKY_LARGE); ValueError as cooperative_adjust_numpy."""
     out_partition, out_member_rank, totals = assign(part_off, partition_id, lag, cons_off, cons_rank)
     return (out_partition, out_member_rank, totals) + cooperative_round_sticky_numpy(
-        part_off, partition_id, lag, out_partition, out_member_rank, n_members, owned_off, owned_topic, owned_partition)
+        part_off, partition_id, lag, out_partition, out_member_rank, n_members, owned_off, owned_topic, owned_partition,
+        max_partitions=max_partitions)
 
 
 def reduce_member_loads(partitions, lag, unassigned, group=None):
