@@ -383,6 +383,8 @@ int enqueue_batch(la_ctx* ctx, Lane& ln, const la_device_batch* b, hipStream_t s
     a.n_total = b->n_partitions;
     a.flags = b->flags & (LA_FLAG_INDEX64 | LA_FLAG_DEFER_WIDE);
     if (getenv("LA_TILE_ALWAYS_STAGE2")) a.flags |= la::kTileAlwaysStage2;       // (A/B hook, read at every call)
+    a.begin_sparse_max = -1;                                                     // the launcher's choice (launch_one)
+    if (const char* env = getenv("LA_TILE_BEGIN_SPARSE_MAX")) a.begin_sparse_max = atoi(env) < 0 ? 0 : atoi(env);   // (A/B hook, read at every call)
     if (wire_out) {
         a.flags |= la::kTileWireOut;
         a.out_wire = b->d_out_wire;

@@ -53,6 +53,9 @@ constexpr int32_t kTileNoDefer = 8;       // TileArgs::flags: the bounds prove t
 constexpr int32_t kTileWireOut = 16;      // TileArgs::flags: out_wire instead of out_pid / out_rank (needs kTileNoDefer)
 constexpr int32_t kTileSkipOversize = 4;  // TileArgs::flags: topics beyond the tile belong to another path, no error
 constexpr int32_t kTileAlwaysStage2 = 32; // TileArgs::flags: (lab hook, LA_TILE_ALWAYS_STAGE2) never skip the second-stage `begin` loads
+// TileArgs::begin_sparse_max unless LA_TILE_BEGIN_SPARSE_MAX says otherwise (lab hook; 0: always the vector form).  At the
+// target's 1 % of partitions without a committed offset a 512-partition wavefront holds 5.1 of them on average.
+constexpr int32_t kTileBeginSparseMax = 16;
 
 constexpr int64_t kTileMaxPartitions = 1024;   // 64 lanes x 16 records
 constexpr int64_t kTileMaxConsumers = 64;      // one consumer bin per lane
@@ -109,6 +112,10 @@ struct TileArgs {
     // two int32 arrays; only with kTileNoDefer (one launch of the packed-record kernel, 32-bit indexing)
     void* out_wire;
     int32_t wire_bytes, wire_id_bits;
+    // stage 2 of a wavefront in which at most this many elements lack a committed offset fetches exactly those `begin` words
+    // through scalar loads; more than that (or 0 here) take the vector form.  Negative: the launcher decides (kTileBeginSparseMax
+    // in a launch that fills the chip, 0 in one round of wavefronts)
+    int32_t begin_sparse_max;
 };
 
 // bytes of defer_list a launch over n_topics topics may need (one tile holds >= 1 topic)

@@ -12,7 +12,9 @@
 //   0. topics    the wavefront's 64/L + 1 words of part_off and of cons_off: scalar loads at a wave-uniform address for a plain
 //                batch's full wavefront (fetch_desc_uniform), indexed per-lane loads for topic lists and the last wavefront.
 //   1. load      committed / end / partition id, 16 B per lane per array, unconditional and clamped, all
-//                issued back to back; `begin` only where there is no committed offset; lag in registers.
+//                issued back to back; `begin` only where there is no committed offset: a wavefront with no such element
+//                skips the stage, one with a few (at most TileArgs::begin_sparse_max) fetches exactly those words through
+//                scalar loads and v_writelane (fetch_begin_sparse), the rest run 16-byte vector loads; lag in registers.
 //   2. format    per wavefront: packed 64-bit records if ids and lags are narrow enough (kernel 1), else
 //                the tile is deferred to the wide-record kernel (kernel 2).  The widths are those of the OR of all ids / all
 //                lags, reduced in DPP + v_readlane (la_device.h): the packed path makes no LDS round trip to agree on anything.
@@ -211,7 +213,84 @@ __device__ __forceinline__ bool second_stage_needed(const TileArgs& a) {
     return !a.lag && !a.reset_latest && a.begin;                        // wave-uniform
 }
 
-template <int L, int E, bool FULL = false, typename D>
+// a value of one lane (wave-uniform lane index) as a scalar, and a scalar put into one lane of a register
+__device__ __forceinline__ uint32_t lane_value(uint32_t v, int ln) { return (uint32_t)__builtin_amdgcn_readlane((int)v, ln); }
+__device__ __forceinline__ int64_t lane_value(int64_t v, int ln) {
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, ln);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)((uint64_t)v >> 32), ln);
+    return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+// (v_writelane_b32 has no __builtin_amdgcn_ spelling in hipcc: this declares the compiler's own intrinsic by its name, so the
+// compiler -- not inline assembly -- places it and keeps its hazards)
+extern "C" __device__ int la_writelane_i32(int value, int lane, int old) __asm("llvm.amdgcn.writelane.i32");
+__device__ __forceinline__ int64_t with_lane_set(int64_t old, int64_t s, int ln) {
+    const uint32_t lo = (uint32_t)la_writelane_i32((int)(uint32_t)s, ln, (int)(uint32_t)old);
+    const uint32_t hi = (uint32_t)la_writelane_i32((int)(uint32_t)((uint64_t)s >> 32), ln, (int)(uint32_t)((uint64_t)old >> 32));
+    return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+
+// The sparse form of stage 2: a wavefront in which only a few elements lack their committed offset -- 5 of 512 at the target's
+// 1 % -- fetches exactly those `begin` words through scalar loads (s_load_dwordx2) and puts each into its lane (v_writelane).
+// need[2k] / need[2k + 1] are the ballots of "no committed offset" over the .x / .y of pair register k.  The ballots are served
+// kBeginSparseChunk at a time (one pair register): a pass takes the lowest lane of each, whose element index is the one its
+// vector load would have used (clamped_index on that lane's descriptor, as scalars: the physical element at g or g + 1); the
+// loads of a pass are in flight together and are waited for once; a ballot with more than one lane set takes another pass.
+// Nothing goes through the vector memory pipeline, where these few words queued behind every neighbour's streaming loads and
+// pulled whole 128-byte lines; no address select, no merge.  `begin` is only read by this launch (constant address space, like
+// the descriptors in fetch_desc_uniform).
+// What bounds the form is scalar registers.  Each ballot is two of them for the whole stage and each load in flight two more; the
+// target instantiation has 80 VGPRs -- the most at 6 wavefronts per SIMD -- and scalar registers spilled into a VGPR would cost a
+// wavefront.  Hence two ballots per pass (four: 84 VGPRs), and tiles of 16 records per lane (16 ballots), like the wide-record
+// kernel (at its scalar register limit already), keep the vector form at any count.
+#ifndef LA_BEGIN_SPARSE_CHUNK
+#define LA_BEGIN_SPARSE_CHUNK 2
+#endif
+constexpr int kBeginSparseChunk = LA_BEGIN_SPARSE_CHUNK;
+constexpr int kBeginSparseBallots = 8;
+// Where the form is used at all.  It trades one trip through the vector memory pipeline, ~45 VALU instructions and the lines'
+// bytes for about three DEPENDENT scalar trips (one per pair register with a missing element).  That pays where a wavefront's
+// VALU chain is what the kernel waits for -- tiles of 256 partitions and more in a launch that fills the chip: the target,
+// -2.4 % -- and costs where the wavefront's own latency is the figure: the resident single-launch form (one round of wavefronts:
+// cfg3 +2 %, one unloaded tile +0.5 us) and small tiles, whose short chain hides nothing (cfg4, 8 lanes x 8: +1.7 %).  Those
+// keep the vector form (profiles/tile_sparse_begin.txt).
+template <int L, int E, bool INLINE_WIDE>
+constexpr bool kBeginSparseFor = !INLINE_WIDE && L * E >= 256;
+template <int L, int E, bool FULL, int J0, typename D, int NM>
+__device__ __forceinline__ void fetch_begin_sparse(const TileArgs& a, const D& d, Raw<E>& raw, uint64_t (&need)[NM]) {
+    typedef const int64_t __attribute__((address_space(4))) * ConstWords;
+    const ConstWords cb = (ConstWords)(uintptr_t)a.begin;
+    constexpr int CH = NM < kBeginSparseChunk ? NM : kBeginSparseChunk;
+    for (;;) {                                                            // (everything in here is wave-uniform)
+        int64_t got[CH];
+#pragma unroll
+        for (int j = J0; j < J0 + CH; ++j) {
+            if (need[j] != 0) {
+                const int ln = __builtin_ctzll(need[j]);
+                D one;                                                    // the descriptor of that lane's group
+                one.p0 = lane_value(d.p0, ln);
+                got[j - J0] = cb[clamped_index<L, E, FULL>(a, one, j & ~1, ln & (L - 1)) + (E >= 2 ? (j & 1) : 0)];
+            }
+        }
+        // Wait here, once, for all of them.  The compiler would wait at the first use anyway; what it cannot see is that every
+        // load above is consumed below (the same test twice), and without this it drains the scalar loads still in flight
+        // before it issues the next one, so that no two of them ever overlap.
+        __builtin_amdgcn_s_waitcnt(0xC07F);                              // lgkmcnt(0), nothing else
+        uint64_t left = 0;
+#pragma unroll
+        for (int j = J0; j < J0 + CH; ++j) {
+            if (need[j] != 0) {
+                int64_t& cm = (E >= 2 && (j & 1)) ? raw.cm[j >> 1].y : raw.cm[j >> 1].x;
+                cm = with_lane_set(cm, got[j - J0], __builtin_ctzll(need[j]));
+                need[j] &= need[j] - 1;
+                left |= need[j];
+            }
+        }
+        if (left == 0) break;
+    }
+    if constexpr (J0 + CH < NM) fetch_begin_sparse<L, E, FULL, J0 + CH>(a, d, raw, need);
+}
+
+template <int L, int E, bool FULL = false, bool SPARSE = true, typename D>
 __device__ __forceinline__ void issue_begin_loads(const TileArgs& a, const D& d, int gl, Raw<E>& raw) {
     if constexpr (kAblate == 2) return;
     constexpr int NP = (E + 1) / 2;
@@ -220,11 +299,35 @@ __device__ __forceinline__ void issue_begin_loads(const TileArgs& a, const D& d,
     // stage altogether (round 6): ONE wave-uniform branch around all of its loads (they still go out back to back inside it).
     // For a resident batch that is a handful of cached reads of begin[0]; for a zero-copy small call, whose arrays live in host
     // memory, it is a whole PCIe round trip (~1.3 us of a ~20 us rebalance) for a value nobody uses.
-    {
+    // One with a few such partitions fetches exactly those (fetch_begin_sparse); the vector form below is for the rest: a new
+    // consumer group and everything in between.  All three choices are wave-uniform.
+    constexpr int NM = E >= 2 ? 2 * NP : NP;
+    if constexpr (!(SPARSE && NM <= kBeginSparseBallots)) {
         bool any = false;
 #pragma unroll
         for (int k = 0; k < NP; ++k) any |= (raw.cm[k].x < 0) | (E >= 2 && raw.cm[k].y < 0);
         if (__builtin_amdgcn_ballot_w64(any) == 0 && !(a.flags & kTileAlwaysStage2)) return;
+    } else {
+        uint64_t need[NM];
+        int n = 0;
+#pragma unroll
+        for (int k = 0; k < NP; ++k) {
+            if constexpr (E >= 2) {
+                need[2 * k] = __builtin_amdgcn_ballot_w64(raw.cm[k].x < 0);
+                need[2 * k + 1] = __builtin_amdgcn_ballot_w64(raw.cm[k].y < 0);
+                n += __builtin_popcountll(need[2 * k]) + __builtin_popcountll(need[2 * k + 1]);
+            } else {
+                need[k] = __builtin_amdgcn_ballot_w64(raw.cm[k].x < 0);
+                n += __builtin_popcountll(need[k]);
+            }
+        }
+        if (!(a.flags & kTileAlwaysStage2)) {
+            if (n == 0) return;
+            if (n <= a.begin_sparse_max) {
+                fetch_begin_sparse<L, E, FULL, 0>(a, d, raw, need);
+                return;
+            }
+        }
     }
 #pragma unroll
     for (int k = 0; k < NP; ++k) {
@@ -753,7 +856,7 @@ __device__ __forceinline__ void packed_tile(const TileArgs& a, const TopicDescT<
         const IDX want = cur.c0 + (IDX)gl, last = (IDX)(a.k_total > 0 ? a.k_total - 1 : 0);
         if (a.k_total > 0) my_rank = load_at<int32_t>(a.cons_rank, want < last ? want : last);
     }
-    issue_begin_loads<L, E, FULL>(a, cur, gl, raw);
+    issue_begin_loads<L, E, FULL, kBeginSparseFor<L, E, INLINE_WIDE>>(a, cur, gl, raw);
 
     P64 rec[E];
     int sh, lbw;
@@ -902,7 +1005,7 @@ __global__ __launch_bounds__(256) void wave_tile_wide_kernel(TileArgs a, int fro
         const TopicDesc d = load_desc<L, E>(a, tile, n_tiles, grp, gl);
         Raw<E> raw;
         issue_loads<L, E>(a, d, gl, raw);
-        issue_begin_loads<L, E>(a, d, gl, raw);
+        issue_begin_loads<L, E, false, false>(a, d, gl, raw);
         int64_t lag[E];
         int32_t pid[E];
         finish_lags<L, E>(a, d, gl, raw, lag, pid);
@@ -959,6 +1062,9 @@ static hipError_t launch_one(const TileArgs& a_in, int mode, hipStream_t stream,
         printf("resident blocks: inline %d wide %d argmin %d (needed %lld)\n", res_inline, res_wide, res_argmin, (long long)blocks);
 #endif
     }
+    // stage 2's sparse form (kBeginSparseFor) only in a launch that fills the chip: in one round of wavefronts its dependent
+    // scalar trips are the call's own latency (one unloaded tile, bounded form: +0.4 us).  The lab hook's value is taken as it is.
+    if (a.begin_sparse_max < 0) a.begin_sparse_max = blocks > res_inline ? kTileBeginSparseMax : 0;
     const dim3 b(Cfg::kThreads);
     auto grid = [&](int resident) { return dim3((unsigned)(blocks < resident ? blocks : resident)); };
     if (mode == kModeArgmin) {
