@@ -54,8 +54,10 @@ constexpr int32_t kTileWireOut = 16;      // TileArgs::flags: out_wire instead o
 constexpr int32_t kTileSkipOversize = 4;  // TileArgs::flags: topics beyond the tile belong to another path, no error
 constexpr int32_t kTileAlwaysStage2 = 32; // TileArgs::flags: (lab hook, LA_TILE_ALWAYS_STAGE2) never skip the second-stage `begin` loads
 // TileArgs::begin_sparse_max unless LA_TILE_BEGIN_SPARSE_MAX says otherwise (lab hook; 0: always the vector form).  At the
-// target's 1 % of partitions without a committed offset a 512-partition wavefront holds 5.1 of them on average.
-constexpr int32_t kTileBeginSparseMax = 16;
+// target's 1 % of partitions without a committed offset a 512-partition wavefront holds 5.1 of them on average.  32 since a
+// pass serves all eight ballots: 16 and 32 are level at the target, 32 is 0.9 % faster at 5 % (25.6 per wavefront) and level
+// with the vector form at 10 %; 64 is slower than the vector form from 5 % on (profiles/tile_begin_onetrip.txt).
+constexpr int32_t kTileBeginSparseMax = 32;
 
 constexpr int64_t kTileMaxPartitions = 1024;   // 64 lanes x 16 records
 constexpr int64_t kTileMaxConsumers = 64;      // one consumer bin per lane

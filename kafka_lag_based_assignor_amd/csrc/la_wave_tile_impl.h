@@ -231,30 +231,51 @@ __device__ __forceinline__ int64_t with_lane_set(int64_t old, int64_t s, int ln)
 
 // The sparse form of stage 2: a wavefront in which only a few elements lack their committed offset -- 5 of 512 at the target's
 // 1 % -- fetches exactly those `begin` words through scalar loads (s_load_dwordx2) and puts each into its lane (v_writelane).
-// need[2k] / need[2k + 1] are the ballots of "no committed offset" over the .x / .y of pair register k.  The ballots are served
-// kBeginSparseChunk at a time (one pair register): a pass takes the lowest lane of each, whose element index is the one its
-// vector load would have used (clamped_index on that lane's descriptor, as scalars: the physical element at g or g + 1); the
-// loads of a pass are in flight together and are waited for once; a ballot with more than one lane set takes another pass.
+// need[2k] / need[2k + 1] are the ballots of "no committed offset" over the .x / .y of pair register k.  A pass serves
+// kBeginSparseChunk ballots -- all eight of a tile of 8 records per lane: it takes the lowest lane of each, whose element index is
+// the one its vector load would have used (clamped_index on that lane's descriptor, as scalars: the physical element at g or
+// g + 1); the loads of a pass are in flight together and are waited for once; only a ballot with more than one lane set takes
+// another pass (1.9 passes per wavefront at the target, 3.9 with two ballots per pass).  "Missing" is what the ballots said before
+// the first word arrived: a word from `begin` is used as it is and never tested again.
 // Nothing goes through the vector memory pipeline, where these few words queued behind every neighbour's streaming loads and
 // pulled whole 128-byte lines; no address select, no merge.  `begin` is only read by this launch (constant address space, like
 // the descriptors in fetch_desc_uniform).
-// What bounds the form is scalar registers.  Each ballot is two of them for the whole stage and each load in flight two more; the
-// target instantiation has 80 VGPRs -- the most at 6 wavefronts per SIMD -- and scalar registers spilled into a VGPR would cost a
-// wavefront.  Hence two ballots per pass (four: 84 VGPRs), and tiles of 16 records per lane (16 ballots), like the wide-record
-// kernel (at its scalar register limit already), keep the vector form at any count.
+// What bounds the form is registers: each ballot is two scalar registers for the whole stage and each load in flight two more, and
+// the target instantiation must stay at 80 VGPRs, the most at 6 wavefronts per SIMD.  All eight ballots in one pass fit (76 VGPRs,
+// 87 SGPRs) since the stage's three outcomes are two branches one after the other (issue_begin_loads); as three ways out of one
+// block the compiler kept the committed offsets as loaded alive beside their patched copies, and eight ballots per pass came
+// to 85 VGPRs.  Tiles of 16 records per lane (16 ballots), like the wide-record kernel (at its scalar register limit already),
+// keep the vector form at any count.
+// Lab switch (timing only, always 0 in the library; results are WRONG under it): the sparse form reads its words from the first
+// LA_BEGIN_WINDOW elements of `begin` (a power of two) -- the trips, their number and their dependence stay, the lines stay in
+// L2 and their HBM bytes go away.  Splits what the sparse form still costs into trips and bytes (profiles/tile_begin_onetrip.txt).
+#ifndef LA_BEGIN_WINDOW
+#define LA_BEGIN_WINDOW 0
+#endif
+template <typename IDX>
+__device__ __forceinline__ IDX begin_sparse_index(IDX idx) {
+    if constexpr (LA_BEGIN_WINDOW != 0) return idx & (IDX)(LA_BEGIN_WINDOW - 1);
+    else return idx;
+}
 #ifndef LA_BEGIN_SPARSE_CHUNK
-#define LA_BEGIN_SPARSE_CHUNK 2
+#define LA_BEGIN_SPARSE_CHUNK 8
 #endif
 constexpr int kBeginSparseChunk = LA_BEGIN_SPARSE_CHUNK;
 constexpr int kBeginSparseBallots = 8;
 // Where the form is used at all.  It trades one trip through the vector memory pipeline, ~45 VALU instructions and the lines'
-// bytes for about three DEPENDENT scalar trips (one per pair register with a missing element).  That pays where a wavefront's
+// bytes for about two DEPENDENT scalar trips (one per lane set in the fullest ballot; about three when a pass served one pair
+// register, which is the form the figures below were measured with).  That pays where a wavefront's
 // VALU chain is what the kernel waits for -- tiles of 256 partitions and more in a launch that fills the chip: the target,
 // -2.4 % -- and costs where the wavefront's own latency is the figure: the resident single-launch form (one round of wavefronts:
 // cfg3 +2 %, one unloaded tile +0.5 us) and small tiles, whose short chain hides nothing (cfg4, 8 lanes x 8: +1.7 %).  Those
 // keep the vector form (profiles/tile_sparse_begin.txt).
+// (lab switch -DLA_BEGIN_SPARSE_ANYWHERE=1, for re-measuring exactly that: the form in every packed instantiation whose ballots
+// fit and in launches of any size)
+#ifndef LA_BEGIN_SPARSE_ANYWHERE
+#define LA_BEGIN_SPARSE_ANYWHERE 0
+#endif
 template <int L, int E, bool INLINE_WIDE>
-constexpr bool kBeginSparseFor = !INLINE_WIDE && L * E >= 256;
+constexpr bool kBeginSparseFor = LA_BEGIN_SPARSE_ANYWHERE != 0 || (!INLINE_WIDE && L * E >= 256);
 template <int L, int E, bool FULL, int J0, typename D, int NM>
 __device__ __forceinline__ void fetch_begin_sparse(const TileArgs& a, const D& d, Raw<E>& raw, uint64_t (&need)[NM]) {
     typedef const int64_t __attribute__((address_space(4))) * ConstWords;
@@ -268,7 +289,7 @@ __device__ __forceinline__ void fetch_begin_sparse(const TileArgs& a, const D& d
                 const int ln = __builtin_ctzll(need[j]);
                 D one;                                                    // the descriptor of that lane's group
                 one.p0 = lane_value(d.p0, ln);
-                got[j - J0] = cb[clamped_index<L, E, FULL>(a, one, j & ~1, ln & (L - 1)) + (E >= 2 ? (j & 1) : 0)];
+                got[j - J0] = cb[begin_sparse_index(clamped_index<L, E, FULL>(a, one, j & ~1, ln & (L - 1)) + (E >= 2 ? (j & 1) : 0))];
             }
         }
         // Wait here, once, for all of them.  The compiler would wait at the first use anyway; what it cannot see is that every
@@ -321,13 +342,18 @@ __device__ __forceinline__ void issue_begin_loads(const TileArgs& a, const D& d,
                 n += __builtin_popcountll(need[k]);
             }
         }
+        // Two branches one after the other, not three ways out of this block: the vector form below then reads what the sparse
+        // form leaves (it runs only if the sparse form has not), so the registers as loaded are dead once the sparse form starts
+        // and it patches them where they are.  The empty asm keeps the compiler from merging the two branches again.
+        int vector = 1;
         if (!(a.flags & kTileAlwaysStage2)) {
-            if (n == 0) return;
-            if (n <= a.begin_sparse_max) {
-                fetch_begin_sparse<L, E, FULL, 0>(a, d, raw, need);
-                return;
+            if (n <= a.begin_sparse_max) {                                // (n == 0 comes here too: the switch is never negative)
+                if (n != 0) fetch_begin_sparse<L, E, FULL, 0>(a, d, raw, need);
+                vector = 0;
             }
         }
+        asm volatile("" : "+s"(vector));
+        if (!vector) return;
     }
 #pragma unroll
     for (int k = 0; k < NP; ++k) {
@@ -1064,7 +1090,7 @@ static hipError_t launch_one(const TileArgs& a_in, int mode, hipStream_t stream,
     }
     // stage 2's sparse form (kBeginSparseFor) only in a launch that fills the chip: in one round of wavefronts its dependent
     // scalar trips are the call's own latency (one unloaded tile, bounded form: +0.4 us).  The lab hook's value is taken as it is.
-    if (a.begin_sparse_max < 0) a.begin_sparse_max = blocks > res_inline ? kTileBeginSparseMax : 0;
+    if (a.begin_sparse_max < 0) a.begin_sparse_max = (LA_BEGIN_SPARSE_ANYWHERE != 0 || blocks > res_inline) ? kTileBeginSparseMax : 0;
     const dim3 b(Cfg::kThreads);
     auto grid = [&](int resident) { return dim3((unsigned)(blocks < resident ? blocks : resident)); };
     if (mode == kModeArgmin) {
