@@ -1085,12 +1085,27 @@ int la_cooperative_round_sticky_device(la_ctx *ctx, const la_device_batch *batch
  *   topic_kept, topic_saved, sticky_summary   as d_topic_kept / d_topic_saved / d_sticky_summary of that call.
  * Every error condition of the assign call and of the sticky round applies; on any error the caller's outputs are left as they
  * were.  A pending la_hint_next_call is consumed.  The call makes NO promise about la_group_last_by_member afterwards.
- * GENERAL form only: the assign call runs into buffers of the context's own; then the target, the owned arrays, partition_id and
- * the lag source (`lag`, or end and committed plus a dense begin -- for the sparse form the host scatters none_begin over zeros
- * while packing, LA_RESET_LATEST stages no begin; the lag itself is computed on the device) travel as ONE H2D copy through the
- * cooperative staging buffers of shard 0, la_cooperative_round_sticky_device runs on la_stream(ctx) with the largest topic as its
- * hint -- the one-workgroup kernel when the call is within its limits -- and the outputs come back as ONE D2H copy.
- * la_last_launches is the sum of the assign call's and the round's.  There is no fused zero-copy form yet.
+ * Two forms, the same results, bit for bit on every output:
+ *   FUSED    the call is one a zero-copy staged call serves (one shard, staging layout within the zero-copy size), within the
+ *            four ONE WORKGROUP limits of la_cooperative_round_sticky_device, without LA_COOP_FORCE_TABLE (LA_COOP_STICKY_LARGE
+ *            does not matter: a call of that size holds no large topic).  partition_id, the lag source and the owned arrays
+ *            ride in the staging buffer the assignment kernels read in place -- the lags, or end and committed plus a dense
+ *            begin; for the sparse form the host scatters none_begin over zeros while packing, LA_RESET_LATEST stages no begin
+ *            -- the target stays in device memory; ONE launch of the sticky round's workgroup behind them reads the target and,
+ *            once and by index, the lag source, writes every output into the staging buffer and stores the completion word
+ *            the calling thread spins on.  No copy, no memset, no stream synchronize.  la_last_pipeline is
+ *            LA_PIPELINE_ZERO_COPY; la_last_launches is what the assign call reports for the same inputs and hints (the round
+ *            takes the place of its finishing launch): 2 for a one-tile batch with bounds hints.  The target stays kept on
+ *            the device as after la_assign_batch_cooperative.  Measured against the general form in one process
+ *            (profiles/assign_coop_sticky_probe.txt) it is faster at 100, 1 000 and 2 048 partitions, so no size within the
+ *            limits is excluded.
+ *   GENERAL  everything else: the assign call runs into buffers of the context's own; then the target, the owned arrays,
+ *            partition_id and the lag source (packed as above; the lag itself is computed on the device) travel as ONE H2D copy
+ *            through the cooperative staging buffers of shard 0, la_cooperative_round_sticky_device runs on la_stream(ctx) with
+ *            the largest topic as its hint and the outputs come back as ONE D2H copy.  la_last_launches is the sum of the
+ *            assign call's and the round's.
+ * LA_NO_FUSED_STICKY in the environment, read at every call of this entry point, sends every call through the GENERAL form
+ * (an A/B hook for tests and probes).
  * struct_size: sizeof(la_assign_sticky_args) of the caller's header; less than this library's is LA_EINVAL.  reserved must be 0. */
 typedef struct la_assign_sticky_args {
     int32_t struct_size, reserved;          /* sizeof(la_assign_sticky_args) of the caller's header; 0 */

@@ -1048,8 +1048,10 @@ class Context:
         totals describe the TARGET, every other entry of .coop and sticky_partition / topic_kept / topic_saved / sticky_summary
         the sticky order; `out` = caller-owned buffers in that shape (None entries of out.coop are not computed).
         large: LA_COOP_STICKY_LARGE -- topics of more than VERIFY_MAX_PARTITIONS partitions are re-matched too instead of being
-        passed through.  sharding.assign_cooperative_sticky_numpy (max_partitions=STICKY_ANY_SIZE for large) is the same on the
-        host."""
+        passed through.  A small call (within COOP_STICKY_ENTRIES / _OWNED / _MEMBERS / _TOPICS, without force_table) is zero-copy
+        with the sticky round as its last launch, like assign_batch_cooperative; LA_NO_FUSED_STICKY=1 in the environment sends
+        every call through the general form.  sharding.assign_cooperative_sticky_numpy (max_partitions=STICKY_ANY_SIZE for
+        large) is the same on the host."""
         fn = getattr(self._lib, "la_assign_batch_cooperative_sticky", None)
         if fn is None:
             raise LagAssignError(LA_EINVAL, "this liblagassign.so has no la_assign_batch_cooperative_sticky")

@@ -1275,7 +1275,7 @@ static bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
 
 // la_device_batch + la_coop_sticky_args, checked: the batch as la_sticky_ties_device checks it, the round as
 // la_cooperative_round_device checks it with the target taken from the batch, the sticky outputs.
-static int coop_sticky_call_of(la_ctx* ctx, const la_device_batch* batch, const la_coop_sticky_args* args, la::CoopStickyCall* out) {
+int coop_sticky_call_of(la_ctx* ctx, const la_device_batch* batch, const la_coop_sticky_args* args, la::CoopStickyCall* out) {
     if (!batch) return fail(ctx, LA_EINVAL, "batch is NULL");
     if (!args) return fail(ctx, LA_EINVAL, "args is NULL");
     if (args->struct_size < (int32_t)sizeof(la_coop_sticky_args))
@@ -1561,10 +1561,12 @@ LA_API int la_assign_batch_cooperative(la_ctx* ctx, const la_assign_coop_args* g
     }
 }
 
-// A cooperative rebalance on the STICKY order from host buffers in one call.  GENERAL form only: the assign call into buffers of
+// A cooperative rebalance on the STICKY order from host buffers in one call.  FUSED (la_host.hip, assign_small_zc): the sticky
+// round kernel is the zero-copy call's last launch -- one packing, no copy, one wait.  GENERAL: the assign call into buffers of
 // the context's own (as coop_take_general arranges it), then target, owned arrays, partition ids and the lag source through the
 // cooperative staging buffers -- one copy in, la_cooperative_round_sticky_device on lane 0's stream, one copy out, one wait.  The
-// caller's arrays are written only after everything has succeeded.
+// caller's arrays are written only after everything has succeeded.  LA_NO_FUSED_STICKY (environment, read at every call): the
+// GENERAL form as it was before there was a fused one, for every call (A/B: tests, tools/coop_sticky_probe.py).
 LA_API int la_assign_batch_cooperative_sticky(la_ctx* ctx, const la_assign_sticky_args* args) {
     DeviceGuard restore_device;
     LaunchSpan span(ctx);
@@ -1594,7 +1596,38 @@ LA_API int la_assign_batch_cooperative_sticky(la_ctx* ctx, const la_assign_stick
                            g->part_off[T] <= 0x7FFFFFFF && g->cons_off[T] <= 0x7FFFFFFF;
         if (T > 0 && !sized) return fail(ctx, LA_EINVAL, "part_off / cons_off are NULL, or end below 0 or beyond 2^31-1 entries");
         const int64_t N = sized ? g->part_off[T] : 0, K = sized ? g->cons_off[T] : 0;
-        if (sized) {
+        // the A/B hook of this entry point, read at every call (the tests and the probe compare both forms in one process)
+        const bool try_fused = getenv("LA_NO_FUSED_STICKY") == nullptr;
+        la::CoopRoundCall q{};
+        StickyOuts so;
+        bool done = false;
+        if (try_fused) {
+            // assign_host decides: FUSED ends in the sticky round's finishing form and sets `done`; otherwise it has become the plain
+            // assign call into the context's own buffers that the GENERAL form below starts from (coop_take_general)
+            q.c.n_topics = T;
+            q.c.n_members = g->n_members;
+            q.c.n_owned = g->n_owned;
+            q.c.owned_off = g->owned_member_off;
+            q.c.owned_topic = g->owned_topic;
+            q.c.owned_partition = g->owned_partition;
+            q.c.prev_owner = g->prev_owner;
+            q.c.coop_rank = g->coop_member_rank;
+            q.c.member_kept = g->member_kept;
+            q.c.member_fresh = g->member_fresh;
+            q.c.member_pending = g->member_pending;
+            q.c.member_release = g->member_release;
+            q.c.topic_withheld = g->topic_withheld;
+            q.c.summary = g->summary;
+            q.member_off = g->member_off;
+            q.grouped_topic = g->grouped_topic;
+            q.grouped_partition = g->grouped_partition;
+            so.sticky_partition = args->sticky_partition;
+            so.topic_kept = args->topic_kept;
+            so.topic_saved = args->topic_saved;
+            so.sticky_summary = args->sticky_summary;
+            c.out_pid = g->out_partition; c.out_rank = g->out_member_rank; c.out_total = g->out_total_lag;
+            c.coop = &q; c.coop_force_table = (g->flags & LA_COOP_FORCE_TABLE) != 0; c.coop_done = &done; c.sticky = &so;
+        } else if (sized) {
             ctx->coop_target.resize((size_t)K + (size_t)N + 1);
             c.out_total = ctx->coop_target.data();
             c.out_pid = (int32_t*)(ctx->coop_target.data() + K);
@@ -1609,6 +1642,7 @@ LA_API int la_assign_batch_cooperative_sticky(la_ctx* ctx, const la_assign_stick
             if (!g->begin_off) { c.sparse = true; c.n_none = g->n_none; c.none_index = g->none_index; c.none_begin = g->none_begin; }
         }
         if (int rc = assign_host(ctx, c)) return rc;
+        if (done) return LA_OK;
         const int64_t* const t_total = sized ? ctx->coop_target.data() : nullptr;
         const int32_t* const t_pid = sized ? (const int32_t*)(t_total + K) : nullptr;
         const int32_t* const t_rank = sized ? t_pid + N : nullptr;

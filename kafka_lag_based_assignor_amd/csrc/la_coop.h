@@ -128,4 +128,15 @@ inline bool coop_sticky_is_small(const CoopCall& c) {
 hipError_t cooperative_round_sticky_launch(CoopScratch& s, StickyScratch& sticky, LargeScratch& large, const CoopStickyCall& k, bool force_table,
                                            uint32_t* status, hipStream_t stream);
 
+// The sticky round as the LAST launch of a zero-copy host call (la_assign_batch_cooperative_sticky, fused form): the one-workgroup
+// kernel in its finishing form.  `k` must be within coop_sticky_is_small; the target (k.r.c.out_partition / out_member_rank) lies
+// in DEVICE memory, every other pointer of `k` -- part offsets, input ids, the lag source, the owned arrays, every output, each
+// optional one null or not, k.s.sticky included -- target_partition / target_rank (both or neither: the target as the caller wants
+// it) and fin_flag lie in the call's mapped staging buffer.  The lag source is read once, by index; k.h_part_off is not looked at.
+// The kernel reads `status` (the lane's device word), adds the round's own bits, puts the word back to zero and stores
+// `0x80000000 | bits` into fin_flag after everything else.  Exactly one launch; hipErrorInvalidValue, with nothing enqueued, for
+// a call outside the limits, without fin_flag or with one target pointer alone.
+hipError_t cooperative_round_sticky_finish_launch(const CoopStickyCall& k, int32_t* target_partition, int32_t* target_rank,
+                                                  uint32_t* status, uint32_t* fin_flag, hipStream_t stream);
+
 }  // namespace la

@@ -29,8 +29,18 @@
 //
 // Any other call -- or one with LA_COOP_FORCE_TABLE -- is the chain itself through the existing launchers, the intermediate
 // d_prev_owner in a buffer of the shard's own.
+//
+// The kernel has a second, FINISHING form (kFinish: la_assign_batch_cooperative_sticky, fused): the last launch of a
+// zero-copy host call, as coop_round_small_kernel<true> is of la_assign_batch_cooperative.  The target comes from device memory
+// and is handed on to the host from the stage phase where it is wanted; the part offsets, the input ids, the lag source, the owned
+// arrays and every output lie in the call's mapped staging buffer, over the link.  There a gather costs a transaction per word,
+// so the lag of input j is computed BY INDEX at stage time -- coalesced -- by the thread that holds in_id of j, and travels to
+// its target position through LDS after the lookup (pos_of, in the LDS of q, which is idle until the owned join).  The launch
+// ends with `done | status` in the word the calling thread spins on.  kFinish == false is the kernel as it was.
 #include "la_coop.h"
 #include "la_sticky_match.h"
+
+#include <type_traits>
 
 namespace la {
 
@@ -86,6 +96,12 @@ static_assert(kEndClassify <= kEndX, "classify: the counters and the sticky ids 
 static_assert(kEndC <= kOffSticky && kEndC <= 160 * 1024, "the lists fit, and leave the sticky ids alone");
 static_assert(kOffStart >= kOffMisc + 4 * 64, "the lists leave the part offsets, the adjusted ranks and the misc words alone");
 static_assert(kOffPartOff % 8 == 0 && kOffLag % 8 == 0 && kOffKeys % 8 == 0 && kOffOwnedOff % 8 == 0, "64-bit words on 8-byte boundaries");
+// the finishing form borrows the LDS of q between the lag join's lookup and the owned join: the target position of every input
+constexpr size_t kOffPosOf = kOffQ;                                                // B  uint16 [N]  pos_of, until q is written
+static_assert(kOffPosOf + 2 * (size_t)E <= kOffQ + 4 * (size_t)E, "pos_of lies inside q");
+static_assert(kOffPosOf + 2 * (size_t)E <= kOffLag && kOffPosOf >= kOffTopic + 4 * (size_t)E, "pos_of leaves the topics and the lags alone");
+static_assert(kNoPos >= E && kNoPos <= 0xFFFF, "kNoPos is no position and fits pos_of");
+static_assert(kCoopStickyLdsBytes == 160000, "the LDS of both forms (DESIGN 4.13)");
 
 // words of the misc area
 constexpr int kSumKept = 0, kSumFresh = 1, kSumWithheld = 2, kSumDropped = 3, kSumClaimed = 4, kSumBad = 5, kTurn = 6, kTies = 7,
@@ -101,7 +117,17 @@ struct CoopStickySmallArgs {
     int32_t cap_p;              // partitions of a topic the batch's hint allows
 };
 
-__global__ __launch_bounds__(NT) void coop_sticky_small_kernel(CoopStickySmallArgs a) {
+// The finishing form (la_assign_batch_cooperative_sticky, fused: la_host.hip, assign_small_zc).  The target lies in device memory;
+// the part offsets, the input ids, the lag source, the owned arrays and EVERY output in the call's staging buffer -- coherent host
+// memory mapped into the device, read and written in place over the link -- and the launch is the call's last: it ends with
+// `done | status` in fin_flag.  Every optional output may be null, the sticky ids included.
+struct CoopStickySmallFinishArgs : CoopStickySmallArgs {
+    int32_t *target_partition, *target_rank;      // [N] in the staging buffer, or both null: the target as the caller wants it
+    uint32_t* fin_flag;                            // host word the calling thread spins on
+};
+
+template <bool kFinish>
+__global__ __launch_bounds__(NT) void coop_sticky_small_kernel(std::conditional_t<kFinish, CoopStickySmallFinishArgs, CoopStickySmallArgs> a) {
     extern __shared__ uint64_t coop_sticky_lds[];
     constexpr int kScope = __HIP_MEMORY_SCOPE_WORKGROUP;
     char* const lds = reinterpret_cast<char*>(coop_sticky_lds);
@@ -111,6 +137,7 @@ __global__ __launch_bounds__(NT) void coop_sticky_small_kernel(CoopStickySmallAr
     uint32_t* const misc = reinterpret_cast<uint32_t*>(lds + kOffMisc);
     int32_t* const e_topic = reinterpret_cast<int32_t*>(lds + kOffTopic);
     int32_t* const e_q = reinterpret_cast<int32_t*>(lds + kOffQ);
+    uint16_t* const pos_of = reinterpret_cast<uint16_t*>(lds + kOffPosOf);      // (kFinish)
     int64_t* const lag = reinterpret_cast<int64_t*>(lds + kOffLag);
     uint16_t* const placed = reinterpret_cast<uint16_t*>(lds + kOffPlaced);
     uint16_t* const loose = placed + E;
@@ -142,17 +169,34 @@ __global__ __launch_bounds__(NT) void coop_sticky_small_kernel(CoopStickySmallAr
     }
     for (int k = tid; k < N; k += NT) e_topic[k] = 0;
     if (tid < 16) misc[tid] = 0;
-    for (int i = tid; i < N; i += NT) {
-        e_pid[i] = c.out_partition[i];
-        e_rank[i] = c.out_member_rank[i];
+    if constexpr (!kFinish) {
+        for (int i = tid; i < N; i += NT) {
+            e_pid[i] = c.out_partition[i];
+            e_rank[i] = c.out_member_rank[i];
+        }
+    } else {
+        // the target on its way from device memory to LDS: where the caller wants it, it goes to the staging buffer from here,
+        // while the thread holds both words (coop_round_small_kernel<true>) -- no trip of its own
+        for (int i = tid; i < N; i += NT) {
+            const int32_t id = c.out_partition[i], rank = c.out_member_rank[i];
+            e_pid[i] = id;
+            e_rank[i] = rank;
+            if (a.target_partition) {
+                a.target_partition[i] = id;
+                a.target_rank[i] = rank;
+            }
+            pos_of[i] = (uint16_t)kNoPos;
+        }
     }
     for (int t = tid; t <= T && T > 0; t += NT) l_part_off[t] = c.part_off[t];
     constexpr int PERE = E / NT, PERO = kCoopStickyOwned / NT;
     int32_t in_id[PERE], o_topic[PERO], o_id[PERO];
+    [[maybe_unused]] int64_t in_lag[PERE];      // (kFinish) the lag of input j, read by index beside its id: one coalesced pass
 #pragma unroll
     for (int u = 0; u < PERE; ++u) {
         const int j = u * NT + tid;
         in_id[u] = j < N ? s.pid[j] : 0;
+        if constexpr (kFinish) in_lag[u] = j < N ? lag_of(s, (int64_t)j) : 0;
     }
     if (n > 0) {
         for (int r = tid; r <= M; r += NT) l_owned_off[r] = c.owned_off[r];
@@ -250,7 +294,11 @@ __global__ __launch_bounds__(NT) void coop_sticky_small_kernel(CoopStickySmallAr
                 if (seen == key) {
                     const uint32_t old = __hip_atomic_fetch_or(&payload[h], kHitMark, __ATOMIC_RELAXED, kScope);
                     if (old & kHitMark) st = kStatusSticky;         // the output id twice
-                    else if (old < (uint32_t)N) { st = 0; l = lag_of(s, (int64_t)old); }
+                    else if (old < (uint32_t)N) {
+                        st = 0;
+                        if constexpr (kFinish) pos_of[old] = (uint16_t)i;      // (a marked slot is hit once: one writer per input)
+                        else l = lag_of(s, (int64_t)old);
+                    }
                     break;
                 }
                 h = (h + 1) & mask;
@@ -264,6 +312,17 @@ __global__ __launch_bounds__(NT) void coop_sticky_small_kernel(CoopStickySmallAr
 
     // ---- owned join, in the same LDS: insert, then q at every target position ---------------------------------------------------
     for (int k = tid; k < oslots; k += NT) keys[k] = 0;
+    if constexpr (kFinish) {
+        // the lag of input j to the position that looked it up (every position holds 0 since the lookup: a miss keeps it); q is
+        // written two barriers from here
+#pragma unroll
+        for (int u = 0; u < PERE; ++u) {
+            const int j = u * NT + tid;
+            if (j >= N) continue;
+            const uint32_t p = pos_of[j];
+            if (p < (uint32_t)N) lag[p] = in_lag[u];
+        }
+    }
     __syncthreads();
     if (n > 0) {
         const uint32_t mask = (uint32_t)oslots - 1u;
@@ -441,7 +500,7 @@ __global__ __launch_bounds__(NT) void coop_sticky_small_kernel(CoopStickySmallAr
             }
             if (!sound || src >= (uint32_t)N) src = (uint32_t)d;
             const int32_t id = e_pid[src], q = e_q[src], cur = e_rank[d], topic = e_topic[d];
-            s.sticky[d] = id;
+            if (!kFinish || s.sticky) s.sticky[d] = id;
             e_sticky[d] = id;
             if (q >= 0 && q == cur) atomicAdd(&after[topic], 1u);
             if (src != (uint32_t)d) __hip_atomic_fetch_or(&tflag[topic], kTopicChanged, __ATOMIC_RELAXED, kScope);
@@ -524,7 +583,8 @@ __global__ __launch_bounds__(NT) void coop_sticky_small_kernel(CoopStickySmallAr
             s.summary[2] = (int64_t)misc[kStChanged];
             s.summary[3] = (int64_t)misc[kStPassed];
         }
-        if (misc[kSumBad]) atomicOr(a.status, misc[kSumBad]);
+        if constexpr (!kFinish)
+            if (misc[kSumBad]) atomicOr(a.status, misc[kSumBad]);
     }
     __syncthreads();                                                 // (everything but A and the sticky ids is done with: the lists take the LDS)
 
@@ -534,6 +594,20 @@ __global__ __launch_bounds__(NT) void coop_sticky_small_kernel(CoopStickySmallAr
                                              a.k.r.grouped_partition, nullptr, reinterpret_cast<uint32_t*>(lds + kOffStart),
                                              misc + kWsum, misc + kTurn, l, l + E, l + 2 * E, l + 3 * E, l + 4 * E,
                                              reinterpret_cast<uint32_t*>(l + 5 * E), reinterpret_cast<uint32_t*>(l + 6 * E));
+    if constexpr (kFinish) {
+        // The call ends here, in the order of coop_round_small_kernel<true>: every thread releases what it stored into the host's
+        // memory, the workgroup meets, ONE thread stores `done | status` where the calling thread spins.  The status is what the
+        // assignment kernels left in the lane's device word plus this round's own bits (kept in LDS: the list builder leaves the
+        // misc words below kWsum alone but for its turn counter); the device word goes back to zero HERE, so a call that ends in
+        // an error leaves nothing behind for the next one.
+        __threadfence_system();
+        __syncthreads();
+        if (tid == 0) {
+            uint32_t st = __hip_atomic_load(a.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) | misc[kSumBad];
+            if (st) __hip_atomic_store(a.status, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(a.fin_flag, 0x80000000u | st, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+    }
 }
 
 }  // namespace
@@ -550,8 +624,8 @@ hipError_t cooperative_round_sticky_launch(CoopScratch& sc, StickyScratch& stick
         a.bits_join = c.n_partitions > 0 ? ceil_log2(2 * c.n_partitions) : 1;
         a.bits_owned = c.n_owned > 0 ? ceil_log2(2 * c.n_owned) : 1;
         a.cap_p = (int32_t)(hint <= 0 || hint > kVerifyMaxPartitions ? kVerifyMaxPartitions : hint);      // as sticky_ties_launch
-        if ((e = opt_in_lds<coop_sticky_small_kernel, kCoopStickyLdsBytes>()) != hipSuccess) return e;
-        return launch_grid<coop_sticky_small_kernel>(1, NT, kCoopStickyLdsBytes, stream, a);
+        if ((e = opt_in_lds<coop_sticky_small_kernel<false>, kCoopStickyLdsBytes>()) != hipSuccess) return e;
+        return launch_grid<coop_sticky_small_kernel<false>>(1, NT, kCoopStickyLdsBytes, stream, a);
     }
     // the general form, the chain itself.  Both buffers of the shard's own first: when they cannot be had nothing has been enqueued
     const int64_t N = c.n_partitions;
@@ -572,6 +646,27 @@ hipError_t cooperative_round_sticky_launch(CoopScratch& sc, StickyScratch& stick
     CoopRoundCall r = k.r;                          // the round on the sticky order
     r.c.out_partition = s.sticky;
     return cooperative_round_launch(sc, large, r, force_table, status, stream);
+}
+
+// The finishing form: `k` within coop_sticky_is_small, the target in device memory, everything else (and fin_flag) in the mapped
+// staging buffer of a zero-copy call.  Exactly one launch, nothing else enqueued.
+hipError_t cooperative_round_sticky_finish_launch(const CoopStickyCall& k, int32_t* target_partition, int32_t* target_rank,
+                                                  uint32_t* status, uint32_t* fin_flag, hipStream_t stream) {
+    const CoopCall& c = k.r.c;
+    if (!coop_sticky_is_small(c) || !fin_flag || (target_partition == nullptr) != (target_rank == nullptr)) return hipErrorInvalidValue;
+    const int64_t hint = k.s.max_partitions_per_topic;
+    CoopStickySmallFinishArgs a{};
+    a.k = k;
+    a.status = status;
+    a.bits_join = c.n_partitions > 0 ? ceil_log2(2 * c.n_partitions) : 1;
+    a.bits_owned = c.n_owned > 0 ? ceil_log2(2 * c.n_owned) : 1;
+    a.cap_p = (int32_t)(hint <= 0 || hint > kVerifyMaxPartitions ? kVerifyMaxPartitions : hint);      // as sticky_ties_launch
+    a.target_partition = target_partition;
+    a.target_rank = target_rank;
+    a.fin_flag = fin_flag;
+    const hipError_t e = opt_in_lds<coop_sticky_small_kernel<true>, kCoopStickyLdsBytes>();
+    if (e != hipSuccess) return e;
+    return launch_grid<coop_sticky_small_kernel<true>>(1, NT, kCoopStickyLdsBytes, stream, a);
 }
 
 }  // namespace la

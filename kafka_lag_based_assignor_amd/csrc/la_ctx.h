@@ -387,6 +387,9 @@ struct StagedBatch {
     bool tail_done = false;
 };
 int enqueue_batch(la_ctx* ctx, Lane& ln, const la_device_batch* b, hipStream_t stream, StagedBatch* staged = nullptr);
+// la_device_batch + la_coop_sticky_args, checked as la_cooperative_round_sticky_device checks them (the fused host call builds its
+// round through the same door)
+int coop_sticky_call_of(la_ctx* ctx, const la_device_batch* batch, const la_coop_sticky_args* args, la::CoopStickyCall* out);
 
 // ---- la_host.hip: the host-buffer calls ------------------------------------------------------------------------------------
 struct Shape {
@@ -394,6 +397,13 @@ struct Shape {
 };
 
 constexpr int64_t kMinShardPartitions = 1 << 16;   // below this a second device costs more than it saves
+
+// What la_assign_batch_cooperative_sticky writes beside the round's outputs (la_assign_sticky_args, lagassign.h).
+struct StickyOuts {
+    int32_t* sticky_partition = nullptr;      // [N]
+    int64_t *topic_kept = nullptr, *topic_saved = nullptr;      // [T]
+    int64_t* sticky_summary = nullptr;        // [4]
+};
 
 // One host-buffer assign call (all pointers are the caller's host arrays).
 struct HostCall {
@@ -431,6 +441,9 @@ struct HostCall {
     const la::CoopRoundCall* coop = nullptr;
     bool coop_force_table = false;
     bool* coop_done = nullptr;
+    // la_assign_batch_cooperative_sticky: beside `coop`, the four outputs of the sticky order (HOST memory, each may be null).  The
+    // fused form is then the STICKY round kernel's finishing form, within the same limits; any other call leaves *coop_done alone.
+    const StickyOuts* sticky = nullptr;
 };
 
 void plan_ranges(const int64_t* po, int32_t t_begin, int32_t t_end, int parts, int32_t* bounds);

@@ -459,9 +459,11 @@ constexpr size_t kSmallHostCheck = 16384;      // consumer entries up to which t
 // One output of a staged call: where the caller wants it (null: it does not), and where it lies in the staging layout.
 struct StagedOut { void* to; size_t off, bytes; };
 // In the order of the layout.  The member lists are those of a grouped call, or of the ADJUSTED assignment of a cooperative one,
-// whose eight outputs follow them; the ungrouped results come last, so that a download can stop short of them.
+// whose eight outputs follow them, then the four of the sticky order (la_assign_batch_cooperative_sticky: carved for such a call
+// only); the ungrouped results come last, so that a download can stop short of them.
 enum { kOutTotals, kOutMemberOff, kOutListTopic, kOutListPartition, kOutKept, kOutFresh, kOutPending, kOutRelease, kOutWithheld,
-       kOutSummary, kOutPrevOwner, kOutCoopRank, kOutPid, kOutRank, kStagedOuts };
+       kOutSummary, kOutPrevOwner, kOutCoopRank, kOutSticky, kOutTopicKept, kOutTopicSaved, kOutStickySummary, kOutPid, kOutRank,
+       kStagedOuts };
 
 struct SmallLayout {
     size_t po, co, pid, end, com, beg, cr, status, total;
@@ -511,6 +513,12 @@ SmallLayout small_layout(const HostCall& c) {
         out(kOutSummary, q->c.summary, 6 * 8);
         out(kOutPrevOwner, q->c.prev_owner, n * 4);
         out(kOutCoopRank, q->c.coop_rank, n * 4);
+        if (const StickyOuts* s = c.sticky) {                 // (no slot at all for any other call: its layout is what it was)
+            out(kOutSticky, s->sticky_partition, n * 4, true);
+            out(kOutTopicKept, s->topic_kept, T * 8);
+            out(kOutTopicSaved, s->topic_saved, T * 8);
+            out(kOutStickySummary, s->sticky_summary, 4 * 8);
+        }
     } else {
         // (a call whose lists take their own round trip keeps g_off and its kin but has g_members < 0: not wanted HERE)
         out(kOutMemberOff, grouped ? c.g_off : nullptr, ((size_t)c.g_members + 1) * 8);
@@ -690,6 +698,46 @@ hipError_t small_coop_launch(const HostCall& c, Lane& ln, const SmallLayout& L, 
                                                (uint32_t*)(m + L.status), st);
 }
 
+// la_assign_batch_cooperative_sticky, fused form: the STICKY round of a zero-copy call as its last launch.  The batch is the staged
+// one -- the target at d (device memory); offsets, input ids and the lag source at m as small_fill_inputs staged them (the lags in
+// the slot of the end offsets, the sparse list scattered into a dense array, no begin at all under LA_RESET_LATEST); the hint is
+// the largest topic -- and goes through the checks of the device call; the owned arrays at m, every output to m, the completion
+// word where the calling thread spins.
+int small_coop_sticky_launch(la_ctx* ctx, const HostCall& c, Lane& ln, const SmallLayout& L, char* m, char* d, hipStream_t st) {
+    const la_device_batch b = small_batch(c, L, m, d);
+    const la::CoopCall& q = c.coop->c;
+    const bool owned = q.n_owned > 0;
+    la_coop_sticky_args a{};
+    a.struct_size = (int32_t)sizeof a;
+    la_coop_args& adj = a.round.adjust;
+    adj.n_members = q.n_members;
+    adj.n_owned = q.n_owned;
+    adj.d_owned_member_off = owned ? (const int64_t*)(m + L.oo) : nullptr;
+    adj.d_owned_topic = owned ? (const int32_t*)(m + L.otp) : nullptr;
+    adj.d_owned_partition = owned ? (const int32_t*)(m + L.opp) : nullptr;
+    adj.d_prev_owner = L.want<int32_t>(m, kOutPrevOwner);
+    adj.d_coop_member_rank = L.want<int32_t>(m, kOutCoopRank);
+    adj.d_member_kept = L.want<int64_t>(m, kOutKept);
+    adj.d_member_fresh = L.want<int64_t>(m, kOutFresh);
+    adj.d_member_pending = L.want<int64_t>(m, kOutPending);
+    adj.d_member_release = L.want<int64_t>(m, kOutRelease);
+    adj.d_topic_withheld = L.want<int64_t>(m, kOutWithheld);
+    adj.d_summary = L.want<int64_t>(m, kOutSummary);
+    a.round.member_off = L.at<int64_t>(m, kOutMemberOff);
+    a.round.grouped_topic = L.want<int32_t>(m, kOutListTopic);
+    a.round.grouped_partition = L.at<int32_t>(m, kOutListPartition);
+    a.d_sticky_partition = L.at<int32_t>(m, kOutSticky);
+    a.d_topic_kept = L.want<int64_t>(m, kOutTopicKept);
+    a.d_topic_saved = L.want<int64_t>(m, kOutTopicSaved);
+    a.d_sticky_summary = L.want<int64_t>(m, kOutStickySummary);
+    la::CoopStickyCall k{};
+    if (int rc = coop_sticky_call_of(ctx, &b, &a, &k)) return rc;
+    k.s.sticky = L.want<int32_t>(m, kOutSticky);               // (the finishing form alone: no trip over the link for ids nobody reads)
+    const hipError_t e = la::cooperative_round_sticky_finish_launch(k, L.want<int32_t>(m, kOutPid), L.want<int32_t>(m, kOutRank),
+                                                                    ln.d_status, (uint32_t*)(m + L.status), st);
+    return e != hipSuccess ? hip_fail(ctx, e, "cooperative_round_sticky: %s") : LA_OK;
+}
+
 // The tail (lists + completion word) a zero-copy call asks the dispatcher to hang on its batch b's tile launch; false: none.
 // ONE launch for the whole rebalance where the batch is one resident tile launch: its last workgroup builds the lists and
 // stores the completion word -- otherwise the grouping / finishing launches of small_zc_enqueue.  Where that pays was measured at
@@ -745,7 +793,10 @@ int small_zc_enqueue(la_ctx* ctx, const HostCall& c, Lane& ln, const SmallLayout
     if (c.g_members >= 0 && !finished)
         if (const hipError_t e = small_group_launch(c, ln, L, m, d, m, ln.d_status, st, fin_flag, &finished); e != hipSuccess)
             return hip_fail(ctx, e, "group_by_member: %s");
-    if (c.coop) {
+    if (c.coop && c.sticky) {
+        if (int rc = small_coop_sticky_launch(ctx, c, ln, L, m, d, st)) return rc;
+        finished = true;
+    } else if (c.coop) {
         if (const hipError_t e = small_coop_launch(c, ln, L, m, d, st); e != hipSuccess) return hip_fail(ctx, e, "cooperative_round: %s");
         finished = true;
     }
@@ -951,6 +1002,7 @@ void coop_take_general(la_ctx* ctx, HostCall& c) {
     c.out_pid = (int32_t*)(ctx->coop_target.data() + c.shape.k);
     c.out_rank = c.out_pid + c.shape.n;
     c.coop = nullptr;
+    c.sticky = nullptr;
     c.memory = -1;
 }
 
@@ -1094,13 +1146,14 @@ int assign_host(la_ctx* ctx, HostCall& c) {
     plan_ranges(c.part_off, 0, T, S, ctx->last_bounds);
     ctx->last_shards = S;
     const bool may_stage = S == 1 && !ctx->split_always && s.n > 0;
-    // la_assign_batch_cooperative.  FUSED: a zero-copy staged call within the round kernel's limits.  Anything else is the
-    // GENERAL form (coop_take_general).
+    // la_assign_batch_cooperative[_sticky].  FUSED: a zero-copy staged call within the (sticky) round kernel's limits.  Anything
+    // else is the GENERAL form (coop_take_general).
     if (c.coop) {
         la::CoopCall probe = c.coop->c;
         probe.n_topics = T;
         probe.n_partitions = s.n;
-        if (!may_stage || c.coop_force_table || !la::coop_round_is_small(probe)) coop_take_general(ctx, c);
+        const bool small = c.sticky ? la::coop_sticky_is_small(probe) : la::coop_round_is_small(probe);
+        if (!may_stage || c.coop_force_table || !small) coop_take_general(ctx, c);
     }
     SmallLayout L;
     int rc;

@@ -2,13 +2,17 @@
 """Time the cooperative round with sticky ties of a small rebalance three ways, on the same device-resident arrays:
 
     python tools/coop_sticky_probe.py [--sizes 100,1000,LIMIT --batch 100 --seconds 1.0] [--out profiles/coop_sticky_probe.txt]
+                                      [--host-out profiles/assign_coop_sticky_probe.txt]
 
   chain   la_cooperative_adjust_device (for d_prev_owner), la_sticky_ties_device, la_cooperative_round_device on the sticky
           order: the three calls a caller chained by hand before la_cooperative_round_sticky_device existed
   sticky  la_cooperative_round_sticky_device (within the limits of csrc/la_coop.h: one launch of one workgroup)
   forced  the same with LA_COOP_FORCE_TABLE (the general form: the chain behind one entry point)
-  host    la_assign_batch_cooperative_sticky on pageable numpy arrays beside la_assign_batch_cooperative on the same arrays, wall
-          clock per call: what the missing fused zero-copy form of the sticky call costs
+  host    la_assign_batch_cooperative_sticky on pageable numpy arrays, wall clock per call, three forms alternating: as it comes
+          (FUSED: the sticky round is the last launch of the zero-copy call), with LA_NO_FUSED_STICKY=1 in the environment (the
+          GENERAL form: a second packing, two copies, a second wait) and la_assign_batch_cooperative (fused) on the same arrays.
+          Medians and interquartile spreads in microseconds; the fused form counts as faster where the general form's median
+          exceeds its own by more than the larger of the two spreads.  Both forms are compared with the model on every output.
 
 A point is a group that has caught up, from tests/sticky_cases.py (caught_up): N entries over topics of 25 partitions (32 at the limit), 8 consumers
 per topic, 1 % of the partitions lagging, two consecutive rebalances with the lagging partitions redrawn; the owned lists are the
@@ -37,6 +41,7 @@ def main():
     ap.add_argument("--batch", type=int, default=100)
     ap.add_argument("--seconds", type=float, default=1.0)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--host-out", default=None, help="the host call's section alone (profiles/assign_coop_sticky_probe.txt)")
     args = ap.parse_args()
 
     import torch
@@ -53,13 +58,21 @@ def main():
     h = ctx._h
     lines = []
 
+    host_lines = []
+
     def say(s):
         print(s, flush=True)
         lines.append(s)
 
+    def hsay(s):                                                         # the host call's section: also a record of its own
+        say(s)
+        host_lines.append(s)
+
     say("coop_sticky_probe: batches of %d calls, at least %.1f s of timed batches per form and point, forms alternating, device %s; "
         "limits N %d, n_owned %d, M %d, T %d" % (args.batch, args.seconds, torch.cuda.get_device_name(0), N.COOP_STICKY_ENTRIES,
                                                   N.COOP_STICKY_OWNED, N.COOP_STICKY_MEMBERS, N.COOP_STICKY_TOPICS))
+    host_lines.append("coop_sticky_probe, host call: batches of %d calls on the wall clock, at least %.1f s of timed batches per form and point, "
+                      "the three forms alternating in one process, device %s" % (args.batch, args.seconds, torch.cuda.get_device_name(0)))
     ok = True
     consumers = 8
     for word in args.sizes.split(","):
@@ -188,12 +201,28 @@ def main():
         h_sticky, h_kept, h_saved, h_sum = np.empty(n, np.int32), np.empty(t, np.int64), np.empty(t, np.int64), np.empty(4, np.int64)
         a_host.sticky_partition, a_host.topic_kept, a_host.topic_saved = h_sticky.ctypes.data, h_kept.ctypes.data, h_saved.ctypes.data
         a_host.sticky_summary = h_sum.ctypes.data
-        hosts = {"la_assign_batch_cooperative": lambda: lib.la_assign_batch_cooperative(h, ctypes.byref(g_plain)),
-                 "la_assign_batch_cooperative_sticky": lambda: lib.la_assign_batch_cooperative_sticky(h, ctypes.byref(a_host))}
-        for f in hosts.values():
-            assert f() == 0, ctx._lib.la_last_error(h)
-        host_same = np.array_equal(h_sticky, exp[0]) and np.array_equal(out_host.grouped_partition, exp[-1]) and \
-            np.array_equal(out_host.out_partition, out_plain.out_partition) and np.array_equal(out_host.out_partition, res[0])
+        sticky_call = lambda: lib.la_assign_batch_cooperative_sticky(h, ctypes.byref(a_host))
+
+        def general_batch(f):                                            # the hook is read at every call: set around the batch alone
+            os.environ["LA_NO_FUSED_STICKY"] = "1"
+            try:
+                return f()
+            finally:
+                del os.environ["LA_NO_FUSED_STICKY"]
+
+        FUSED, GENERAL, PLAIN = "fused", "LA_NO_FUSED_STICKY", "la_assign_batch_cooperative (fused)"
+        hosts = {FUSED: sticky_call, GENERAL: sticky_call, PLAIN: lambda: lib.la_assign_batch_cooperative(h, ctypes.byref(g_plain))}
+        host_same, hlaunches = True, {}
+        for k, f in hosts.items():
+            for x in (h_sticky, h_kept, h_saved, h_sum) + tuple(out_host[3:]):
+                x[...] = -7
+            rc = general_batch(f) if k == GENERAL else f()
+            assert rc == 0, ctx._lib.la_last_error(h)
+            hlaunches[k] = ctx.last_launches()
+            if k != PLAIN:                                               # both forms of the sticky call: all fifteen outputs and the target
+                got = (h_sticky, h_kept, h_saved, h_sum) + tuple(out_host[3:])
+                host_same = host_same and all(np.array_equal(x, e) for x, e in zip(got, exp)) and np.array_equal(out_host.out_partition, res[0])
+        host_same = host_same and np.array_equal(out_host.out_partition, out_plain.out_partition)
         ok = ok and host_same
 
         def host_batch(f):
@@ -202,24 +231,31 @@ def main():
                 f()
             return (time.perf_counter() - t0) * 1e6 / args.batch
 
-        for f in hosts.values():
-            host_batch(f)
+        run = {k: ((lambda f=f: general_batch(lambda: host_batch(f))) if k == GENERAL else (lambda f=f: host_batch(f))) for k, f in hosts.items()}
+        for r in run.values():
+            r()
         htimes = {k: [] for k in hosts}
         hspent = {k: 0.0 for k in hosts}
         while min(hspent.values()) < args.seconds:
-            for k, f in hosts.items():
-                htimes[k].append(host_batch(f))
+            for k, r in run.items():
+                htimes[k].append(r())
                 hspent[k] += htimes[k][-1] * args.batch * 1e-6
         hmed = {k: float(np.median(v)) for k, v in htimes.items()}
-        say("    host calls, wall clock: " + "; ".join("%s %.1f us per call (min %.1f .. max %.1f, spread %.1f %%, %d batches)" % (
-            k, hmed[k], min(v), max(v), 100 * float(np.percentile(v, 75) - np.percentile(v, 25)) / hmed[k], len(v))
-            for k, v in htimes.items()) + "; sticky / plain = %.2f; results %s" % (
-            hmed["la_assign_batch_cooperative_sticky"] / hmed["la_assign_batch_cooperative"], "agree" if host_same else "DIFFER"))
+        hiqr = {k: float(np.percentile(v, 75) - np.percentile(v, 25)) for k, v in htimes.items()}
+        margin, noise = hmed[GENERAL] - hmed[FUSED], max(hiqr[FUSED], hiqr[GENERAL])
+        hsay("la_assign_batch_cooperative_sticky, host arrays, N = n_owned = %d, T = %d, M = %d, 1 %% lagging, wall clock: " % (n, t, m) +
+             "; ".join("%s %.1f us per call (min %.1f .. max %.1f, interquartile %.1f us, %d batches, %d kernel launches)" % (
+                 k, hmed[k], min(v), max(v), hiqr[k], len(v), hlaunches[k]) for k, v in htimes.items()) +
+             "; results %s" % ("agree" if host_same else "DIFFER"))
+        hsay("    LA_NO_FUSED_STICKY - fused = %.1f us against %.1f us of noise (the larger interquartile spread): the fused form is %s at "
+             "%d partitions; LA_NO_FUSED_STICKY / fused = %.2f, fused / la_assign_batch_cooperative = %.2f" % (
+                 margin, noise, "FASTER" if margin > noise else "NOT FASTER", n, hmed[GENERAL] / hmed[FUSED], hmed[FUSED] / hmed[PLAIN]))
     ctx.close()
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as fh:
-            fh.write("\n".join(lines) + "\n")
+    for path, text in ((args.out, lines), (args.host_out, host_lines)):
+        if path:
+            os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+            with open(path, "w") as fh:
+                fh.write("\n".join(text) + "\n")
     sys.exit(0 if ok else 1)
 
 
