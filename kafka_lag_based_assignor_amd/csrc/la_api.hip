@@ -1,4 +1,4 @@
-// la_api.hip -- the C ABI of include/lagassign.h over the HIP kernels.
+// la_api.hip -- the C ABI of include/lagassign.h over the HIP kernels (the cooperative and sticky entry points: la_api_coop.hip).
 //
 // There is no CPU fallback here by design: if the device or a kernel is unavailable the
 // call fails with a negative code and the caller decides what to do.
@@ -9,18 +9,6 @@
 namespace {
 
 constexpr int kMaxShards = 64;
-
-// la_hint_next_call is one-shot: "forgotten when the next host-buffer assign call returns, whatever it returns".  assign_host
-// takes the hints when it starts; every host-buffer entry point also holds one of these, so that a call that returns BEFORE
-// it gets there (a NULL result array, n_topics <= 0, a NULL lag array) spends them too and a stale bound cannot fail the
-// next, unrelated call.
-struct HintSpender {
-    la_ctx* ctx;
-    explicit HintSpender(la_ctx* c) : ctx(c) {}
-    ~HintSpender() { if (ctx) ctx->hints_set = false; }
-    HintSpender(const HintSpender&) = delete;
-    HintSpender& operator=(const HintSpender&) = delete;
-};
 
 // ---- RCCL, loaded at run time (la_allgather_results) ------------------------------------------------------------------
 // Only the five entry points the all-gather needs; prototypes as in rccl.h (ncclResult_t is an int enum, 0 = success;
@@ -1117,664 +1105,6 @@ LA_API int la_verify_assignment_device_on(la_ctx* ctx, int shard, const la_devic
                                                     sh.lanes[0].d_status, (hipStream_t)stream);
         return e != hipSuccess ? hip_fail(ctx, e, "verify_assignment: %s") : LA_OK;
     });
-}
-
-// The host offsets a flagged call reads its large topics through: they ascend inside [0, n_partitions] (as verify checks them)
-static int sticky_large_offsets_ok(la_ctx* ctx, const la_device_batch& b) {
-    if (!b.h_part_off) return fail(ctx, LA_EINVAL, "LA_FLAG_STICKY_LARGE: h_part_off is required");
-    for (int32_t t = 0; t <= b.n_topics; ++t) {
-        const int64_t p = b.h_part_off[t];
-        if (p < 0 || p > b.n_partitions || (t > 0 && p < b.h_part_off[t - 1]))
-            return fail(ctx, LA_EINVAL, "LA_FLAG_STICKY_LARGE: h_part_off must ascend inside [0, n_partitions] (topic %d)", t < b.n_topics ? t : t - 1);
-    }
-    return LA_OK;
-}
-
-// Sticky ties (la_sticky.hip).  Without LA_FLAG_STICKY_LARGE it owns no scratch: everything lives in the workgroups' LDS and the
-// caller's outputs, so the call can be captured.  With the flag the topics over the LDS limit go through tables in device memory
-// (la_sticky_large.hip) -- the shard's own buffer, not the assign scratch.  Either way the results kept for
-// la_group_last_by_member stay as they are.  On shard 0, like the cooperative calls.
-LA_API int la_sticky_ties_device(la_ctx* ctx, const la_device_batch* batch, const la_sticky_args* args, void* stream) {
-    return shard_entry<true>(ctx, 0, "exception in la_sticky_ties_device", [&](Shard& sh) -> int {
-        if (!batch) return fail(ctx, LA_EINVAL, "batch is NULL");
-        if (!args) return fail(ctx, LA_EINVAL, "args is NULL");
-        if (args->struct_size < (int32_t)sizeof(la_sticky_args))
-            return fail(ctx, LA_EINVAL, "la_sticky_args.struct_size is %d, this library takes %d and above", (int)args->struct_size, (int)sizeof(la_sticky_args));
-        const la_device_batch& b = *batch;
-        const la_sticky_args& g = *args;
-        if (g.reserved != 0) return fail(ctx, LA_EINVAL, "la_sticky_args.reserved must be 0");
-        if (b.n_topics < 0 || b.n_partitions < 0) return fail(ctx, LA_EINVAL, "negative size");
-        if (b.flags & LA_FLAG_WIRE_OUT)
-            return fail(ctx, LA_EINVAL, "LA_FLAG_WIRE_OUT: unpack the results with la_unpack_results_on before re-matching them");
-        if (b.n_topics == 0 && b.n_partitions != 0) return fail(ctx, LA_EINVAL, "partitions without topics");
-        if (b.n_topics > 0 && !b.d_part_off) return fail(ctx, LA_EINVAL, "null offsets");
-        if (b.n_partitions > 0 && (!b.d_out_partition || !b.d_out_member_rank)) return fail(ctx, LA_EINVAL, "null results");
-        if (b.n_partitions > 0 && (!b.d_partition_id || (!b.d_lag && (!b.d_end_off || !b.d_committed_off))))
-            return fail(ctx, LA_EINVAL, "null per-partition input");
-        if (!b.d_lag && b.reset_mode != LA_RESET_LATEST && !b.d_begin_off && b.n_partitions > 0)
-            return fail(ctx, LA_EINVAL, "begin_off is required unless reset_mode is LA_RESET_LATEST");
-        if (b.n_partitions > 0 && !g.d_prev_owner) return fail(ctx, LA_EINVAL, "d_prev_owner is NULL");
-        if (b.n_partitions > 0 && !g.d_sticky_partition) return fail(ctx, LA_EINVAL, "d_sticky_partition is NULL");
-        if (b.n_partitions > 0 && g.d_sticky_partition == b.d_out_partition)
-            return fail(ctx, LA_EINVAL, "d_sticky_partition must not be d_out_partition: the call does not work in place");
-        la::StickyCall c{};
-        c.n_topics = b.n_topics;
-        c.reset_latest = b.reset_mode == LA_RESET_LATEST ? 1 : 0;
-        c.n_partitions = b.n_partitions;
-        c.max_partitions_per_topic = b.max_partitions_per_topic;
-        c.part_off = b.d_part_off;
-        c.pid = b.d_partition_id;
-        c.begin = b.d_begin_off;
-        c.end = b.d_end_off;
-        c.committed = b.d_committed_off;
-        c.lag = b.d_lag;
-        c.out_pid = b.d_out_partition;
-        c.out_rank = b.d_out_member_rank;
-        c.prev_owner = g.d_prev_owner;
-        c.sticky = g.d_sticky_partition;
-        c.topic_kept = g.d_topic_kept;
-        c.topic_saved = g.d_topic_saved;
-        c.summary = g.d_summary;
-        const bool large = (b.flags & LA_FLAG_STICKY_LARGE) != 0;
-        if (large)
-            if (int rc = sticky_large_offsets_ok(ctx, b)) return rc;
-        hipError_t e = la::sticky_ties_launch(c, sh.lanes[0].d_status, (hipStream_t)stream, large ? &sh.sticky : nullptr, b.h_part_off);
-        return e != hipSuccess ? hip_fail(ctx, e, "sticky_ties: %s") : LA_OK;
-    });
-}
-
-// What la_cooperative_adjust_device and the two round calls check of a la_coop_args, and the validated call.  need_output: the
-// eight outputs are all a call has (the round calls have the lists beside them).
-static int coop_call_of(la_ctx* ctx, const la_coop_args& g, bool need_output, la::CoopCall* out) {
-    if (g.n_topics < 0 || g.n_partitions < 0 || g.n_members < 0 || g.n_owned < 0) return fail(ctx, LA_EINVAL, "negative size");
-    if (g.reserved != 0) return fail(ctx, LA_EINVAL, "la_coop_args.reserved must be 0");
-    if (g.n_members > la::kMovesMaxMembers) return fail(ctx, LA_EINVAL, "n_members must be below 2^30");
-    if (need_output && !g.d_prev_owner && !g.d_coop_member_rank && !g.d_member_kept && !g.d_member_fresh && !g.d_member_pending &&
-        !g.d_member_release && !g.d_topic_withheld && !g.d_summary)
-        return fail(ctx, LA_EINVAL, "every output is NULL");
-    if (g.n_topics == 0 && g.n_partitions != 0) return fail(ctx, LA_EINVAL, "partitions without topics");
-    if (g.n_partitions > 0 && (!g.d_part_off || !g.d_out_partition || !g.d_out_member_rank)) return fail(ctx, LA_EINVAL, "null buffer");
-    if (g.n_owned > 0 && (!g.d_owned_member_off || !g.d_owned_topic || !g.d_owned_partition))
-        return fail(ctx, LA_EINVAL, "null owned buffer");
-    la::CoopCall c{};
-    c.n_topics = g.n_topics;
-    c.n_members = g.n_members;
-    c.n_partitions = g.n_partitions;
-    c.n_owned = g.n_owned;
-    c.part_off = g.d_part_off;
-    c.out_partition = g.d_out_partition;
-    c.out_member_rank = g.d_out_member_rank;
-    c.owned_off = g.d_owned_member_off;
-    c.owned_topic = g.d_owned_topic;
-    c.owned_partition = g.d_owned_partition;
-    c.prev_owner = g.d_prev_owner;
-    c.coop_rank = g.d_coop_member_rank;
-    c.member_kept = g.d_member_kept;
-    c.member_fresh = g.d_member_fresh;
-    c.member_pending = g.d_member_pending;
-    c.member_release = g.d_member_release;
-    c.topic_withheld = g.d_topic_withheld;
-    c.summary = g.d_summary;
-    *out = c;
-    return LA_OK;
-}
-
-// The cooperative form of a rebalance (la_coop.hip), on shard 0.  The table is the shard's own buffer, not the assign scratch:
-// the results kept for la_group_last_by_member stay as they are.
-LA_API int la_cooperative_adjust_device(la_ctx* ctx, const la_coop_args* args, void* stream) {
-    return shard_entry<true>(ctx, 0, "exception in la_cooperative_adjust_device", [&](Shard& sh) -> int {
-        if (!args) return fail(ctx, LA_EINVAL, "args is NULL");
-        if (args->struct_size < (int32_t)sizeof(la_coop_args))
-            return fail(ctx, LA_EINVAL, "la_coop_args.struct_size is %d, this library takes %d and above", (int)args->struct_size, (int)sizeof(la_coop_args));
-        la::CoopCall c{};
-        if (int rc = coop_call_of(ctx, *args, true, &c)) return rc;
-        hipError_t e = la::cooperative_adjust_launch(sh.coop, c, sh.lanes[0].d_status, (hipStream_t)stream);
-        return e != hipSuccess ? hip_fail(ctx, e, "cooperative_adjust: %s") : LA_OK;
-    });
-}
-
-static_assert(LA_COOP_FORCE_TABLE == 1 && LA_COOP_STICKY_LARGE == 2, "lagassign.h");
-static_assert(LA_STICKY_GLOBAL_LAUNCHES == la::kStickyGlobalLaunches && LA_STICKY_GLOBAL_MAX_PARTITIONS == la::kStickyGlobalMaxPartitions, "lagassign.h");
-
-// a la_coop_round_args, checked: the adjust part as above, the lists' own pointers, the flags
-static int coop_round_call_of(la_ctx* ctx, const la_coop_round_args* args, la::CoopRoundCall* out) {
-    if (!args) return fail(ctx, LA_EINVAL, "args is NULL");
-    if (args->struct_size < (int32_t)sizeof(la_coop_round_args))
-        return fail(ctx, LA_EINVAL, "la_coop_round_args.struct_size is %d, this library takes %d and above", (int)args->struct_size, (int)sizeof(la_coop_round_args));
-    if (args->flags & ~LA_COOP_FORCE_TABLE) return fail(ctx, LA_EINVAL, "la_coop_round_args.flags holds a bit this library does not know");
-    la::CoopRoundCall r{};
-    if (int rc = coop_call_of(ctx, args->adjust, false, &r.c)) return rc;
-    if (!args->member_off) return fail(ctx, LA_EINVAL, "member_off is NULL");
-    if (r.c.n_partitions > 0 && !args->grouped_partition) return fail(ctx, LA_EINVAL, "grouped_partition is NULL");
-    if (r.c.n_partitions > 0x7FFFFFFF) return fail(ctx, LA_ESHAPE, "at most 2^31-1 entries are supported");
-    r.member_off = args->member_off;
-    r.grouped_topic = args->grouped_topic;
-    r.grouped_partition = args->grouped_partition;
-    *out = r;
-    return LA_OK;
-}
-
-// The cooperative round in one call (la_coop_small.hip), on shard 0: one launch of one workgroup within the limits of la_coop.h,
-// otherwise the table form and the grouping behind it.  Neither touches the assign scratch or a kept result.
-LA_API int la_cooperative_round_device(la_ctx* ctx, const la_coop_round_args* args, void* stream) {
-    return shard_entry<true>(ctx, 0, "exception in la_cooperative_round_device", [&](Shard& sh) -> int {
-        la::CoopRoundCall r{};
-        if (int rc = coop_round_call_of(ctx, args, &r)) return rc;
-        hipError_t e = la::cooperative_round_launch(sh.coop, sh.lanes[0].large, r, (args->flags & LA_COOP_FORCE_TABLE) != 0,
-                                                    sh.lanes[0].d_status, (hipStream_t)stream);
-        return e != hipSuccess ? hip_fail(ctx, e, "cooperative_round: %s") : LA_OK;
-    });
-}
-
-// [a, a + na) and [b, b + nb) share a byte (null or empty: they do not)
-static bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
-    if (!a || !b || !na || !nb) return false;
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + nb && y < x + na;
-}
-
-// la_device_batch + la_coop_sticky_args, checked: the batch as la_sticky_ties_device checks it, the round as
-// la_cooperative_round_device checks it with the target taken from the batch, the sticky outputs.
-int coop_sticky_call_of(la_ctx* ctx, const la_device_batch* batch, const la_coop_sticky_args* args, la::CoopStickyCall* out) {
-    if (!batch) return fail(ctx, LA_EINVAL, "batch is NULL");
-    if (!args) return fail(ctx, LA_EINVAL, "args is NULL");
-    if (args->struct_size < (int32_t)sizeof(la_coop_sticky_args))
-        return fail(ctx, LA_EINVAL, "la_coop_sticky_args.struct_size is %d, this library takes %d and above", (int)args->struct_size, (int)sizeof(la_coop_sticky_args));
-    if (args->flags & ~LA_COOP_FORCE_TABLE) return fail(ctx, LA_EINVAL, "la_coop_sticky_args.flags holds a bit this library does not know");
-    const la_device_batch& b = *batch;
-    if (b.n_topics < 0 || b.n_partitions < 0) return fail(ctx, LA_EINVAL, "negative size");
-    if (b.flags & LA_FLAG_WIRE_OUT)
-        return fail(ctx, LA_EINVAL, "LA_FLAG_WIRE_OUT: unpack the results with la_unpack_results_on before re-matching them");
-    if (b.n_topics == 0 && b.n_partitions != 0) return fail(ctx, LA_EINVAL, "partitions without topics");
-    if (b.n_topics > 0 && !b.d_part_off) return fail(ctx, LA_EINVAL, "null offsets");
-    if (b.n_partitions > 0 && (!b.d_out_partition || !b.d_out_member_rank)) return fail(ctx, LA_EINVAL, "null results");
-    if (b.n_partitions > 0 && (!b.d_partition_id || (!b.d_lag && (!b.d_end_off || !b.d_committed_off))))
-        return fail(ctx, LA_EINVAL, "null per-partition input");
-    if (!b.d_lag && b.reset_mode != LA_RESET_LATEST && !b.d_begin_off && b.n_partitions > 0)
-        return fail(ctx, LA_EINVAL, "begin_off is required unless reset_mode is LA_RESET_LATEST");
-    const size_t n4 = (size_t)b.n_partitions * 4, n8 = (size_t)b.n_partitions * 8;
-    if (b.n_partitions > 0 && !args->d_sticky_partition) return fail(ctx, LA_EINVAL, "d_sticky_partition is NULL");
-    for (const void* in : {(const void*)b.d_out_partition, (const void*)b.d_out_member_rank, (const void*)b.d_partition_id})
-        if (ranges_overlap(args->d_sticky_partition, n4, in, n4))
-            return fail(ctx, LA_EINVAL, "d_sticky_partition overlaps an input: the call does not work in place");
-    for (const void* in : {(const void*)b.d_lag, (const void*)b.d_begin_off, (const void*)b.d_end_off, (const void*)b.d_committed_off})
-        if (ranges_overlap(args->d_sticky_partition, n4, in, n8))
-            return fail(ctx, LA_EINVAL, "d_sticky_partition overlaps an input: the call does not work in place");
-    const la_coop_args& ra = args->round.adjust;
-    const size_t o4 = ra.n_owned > 0 ? (size_t)ra.n_owned * 4 : 0;
-    if (ranges_overlap(args->d_sticky_partition, n4, b.d_part_off, ((size_t)b.n_topics + 1) * 8) ||
-        ranges_overlap(args->d_sticky_partition, n4, ra.d_owned_member_off, ra.n_members >= 0 ? ((size_t)ra.n_members + 1) * 8 : 0) ||
-        ranges_overlap(args->d_sticky_partition, n4, ra.d_owned_topic, o4) || ranges_overlap(args->d_sticky_partition, n4, ra.d_owned_partition, o4))
-        return fail(ctx, LA_EINVAL, "d_sticky_partition overlaps an input: the call does not work in place");
-    la_coop_args adjust = args->round.adjust;       // the target is the batch's
-    adjust.n_topics = b.n_topics;
-    adjust.n_partitions = b.n_partitions;
-    adjust.d_part_off = b.d_part_off;
-    adjust.d_out_partition = b.d_out_partition;
-    adjust.d_out_member_rank = b.d_out_member_rank;
-    la::CoopStickyCall k{};
-    if (int rc = coop_call_of(ctx, adjust, false, &k.r.c)) return rc;
-    if (!args->round.member_off) return fail(ctx, LA_EINVAL, "member_off is NULL");
-    if (b.n_partitions > 0 && !args->round.grouped_partition) return fail(ctx, LA_EINVAL, "grouped_partition is NULL");
-    if (b.n_partitions > 0x7FFFFFFF) return fail(ctx, LA_ESHAPE, "at most 2^31-1 entries are supported");
-    k.r.member_off = args->round.member_off;
-    k.r.grouped_topic = args->round.grouped_topic;
-    k.r.grouped_partition = args->round.grouped_partition;
-    la::StickyCall& c = k.s;
-    c.n_topics = b.n_topics;
-    c.reset_latest = b.reset_mode == LA_RESET_LATEST ? 1 : 0;
-    c.n_partitions = b.n_partitions;
-    c.max_partitions_per_topic = b.max_partitions_per_topic;
-    c.part_off = b.d_part_off;
-    c.pid = b.d_partition_id;
-    c.begin = b.d_begin_off;
-    c.end = b.d_end_off;
-    c.committed = b.d_committed_off;
-    c.lag = b.d_lag;
-    c.out_pid = b.d_out_partition;
-    c.out_rank = b.d_out_member_rank;
-    c.sticky = args->d_sticky_partition;
-    c.topic_kept = args->d_topic_kept;
-    c.topic_saved = args->d_topic_saved;
-    c.summary = args->d_sticky_summary;
-    if (b.flags & LA_FLAG_STICKY_LARGE) {            // step 2 of the chain re-matches the large topics too
-        if (int rc = sticky_large_offsets_ok(ctx, b)) return rc;
-        k.h_part_off = b.h_part_off;
-    }
-    *out = k;
-    return LA_OK;
-}
-
-// The cooperative round with sticky ties in one call (la_coop_sticky_small.hip), on shard 0: one launch of one workgroup within
-// the limits of la_coop.h, otherwise the three launchers in turn.  Neither touches the assign scratch or a kept result.
-LA_API int la_cooperative_round_sticky_device(la_ctx* ctx, const la_device_batch* batch, const la_coop_sticky_args* args, void* stream) {
-    return shard_entry<true>(ctx, 0, "exception in la_cooperative_round_sticky_device", [&](Shard& sh) -> int {
-        la::CoopStickyCall k{};
-        if (int rc = coop_sticky_call_of(ctx, batch, args, &k)) return rc;
-        hipError_t e = la::cooperative_round_sticky_launch(sh.coop, sh.sticky, sh.lanes[0].large, k, (args->flags & LA_COOP_FORCE_TABLE) != 0,
-                                                           sh.lanes[0].d_status, (hipStream_t)stream);
-        return e != hipSuccess ? hip_fail(ctx, e, "cooperative_round_sticky: %s") : LA_OK;
-    });
-}
-
-// The cooperative staging buffers of a shard (pinned host memory and device memory) hold `total` bytes: both grown before anything
-// is enqueued, so a failure leaves nothing behind.
-static int coop_stage_reserve(la_ctx* ctx, la::CoopScratch& s, size_t total) {
-    if (total > s.stage_h_cap) {
-        if (s.stage_h) { (void)hipHostFree(s.stage_h); s.stage_h = nullptr; s.stage_h_cap = 0; }
-        const size_t want = total + total / 4 + 256;
-        const hipError_t e = hipHostMalloc(&s.stage_h, want, hipHostMallocDefault);
-        if (e != hipSuccess) { s.stage_h = nullptr; return hip_fail(ctx, e, "cooperative_round staging (host): %s"); }
-        s.stage_h_cap = want;
-    }
-    if (total > s.stage_d_cap) {
-        if (s.stage_d) { (void)hipFree(s.stage_d); s.stage_d = nullptr; s.stage_d_cap = 0; }
-        const size_t want = total + total / 4 + 256;
-        const hipError_t e = hipMalloc(&s.stage_d, want);
-        if (e != hipSuccess) { s.stage_d = nullptr; return hip_fail(ctx, e, "cooperative_round staging (device): %s"); }
-        s.stage_d_cap = want;
-    }
-    return LA_OK;
-}
-
-// la_cooperative_round_device on host buffers: the inputs packed into the shard's own staging buffer (pinned + device, both grown before anything
-// is enqueued), ONE copy in, the device call on lane 0's stream, ONE copy out, one wait.  8-byte arrays first, so every array
-// is aligned for its element.  It neither takes nor spends a pending la_hint_next_call.
-static int coop_round_host(la_ctx* ctx, Shard& sh, const la_coop_round_args* args) {
-    {
-        la::CoopRoundCall host{};
-        if (int rc = coop_round_call_of(ctx, args, &host)) return rc;
-        const la::CoopCall& h = host.c;
-        const size_t N = (size_t)h.n_partitions, n = (size_t)h.n_owned, M = (size_t)h.n_members, T = (size_t)h.n_topics;
-        const bool use_part_off = N > 0, use_owned = n > 0;
-        size_t at = 0;
-        auto take = [&](size_t bytes) { const size_t o = at; at += (bytes + 7) & ~(size_t)7; return o; };
-        // inputs
-        const size_t i_part_off = take(use_part_off ? (T + 1) * 8 : 0), i_owned_off = take(use_owned ? (M + 1) * 8 : 0);
-        const size_t i_pid = take(N * 4), i_rank = take(N * 4), i_otopic = take(n * 4), i_opid = take(n * 4);
-        const size_t in_bytes = at;
-        // outputs: the wanted ones, side by side
-        const size_t o_member_off = take((M + 1) * 8);
-        int64_t* const h_count[4] = {h.member_kept, h.member_fresh, h.member_pending, h.member_release};
-        size_t o_count[4];
-        for (int w = 0; w < 4; ++w) o_count[w] = take(h_count[w] ? M * 8 : 0);
-        const size_t o_withheld = take(h.topic_withheld ? T * 8 : 0), o_summary = take(h.summary ? 6 * 8 : 0);
-        const size_t o_prev = take(h.prev_owner ? N * 4 : 0), o_coop = take(h.coop_rank ? N * 4 : 0);
-        const size_t o_gtopic = take(host.grouped_topic ? N * 4 : 0), o_gpart = take(N * 4);
-        const size_t total = at, out_bytes = total - in_bytes;
-        // both halves of the staging buffer before anything is enqueued
-        la::CoopScratch& s = sh.coop;
-        if (int rc = coop_stage_reserve(ctx, s, total)) return rc;
-        char* const hp = static_cast<char*>(s.stage_h);
-        char* const dp = static_cast<char*>(s.stage_d);
-        if (use_part_off) memcpy(hp + i_part_off, h.part_off, (T + 1) * 8);
-        if (use_owned) memcpy(hp + i_owned_off, h.owned_off, (M + 1) * 8);
-        if (N) {
-            memcpy(hp + i_pid, h.out_partition, N * 4);
-            memcpy(hp + i_rank, h.out_member_rank, N * 4);
-        }
-        if (n) {
-            memcpy(hp + i_otopic, h.owned_topic, n * 4);
-            memcpy(hp + i_opid, h.owned_partition, n * 4);
-        }
-        la::CoopRoundCall d = host;
-        d.c.part_off = use_part_off ? (const int64_t*)(dp + i_part_off) : nullptr;
-        d.c.owned_off = use_owned ? (const int64_t*)(dp + i_owned_off) : nullptr;
-        d.c.out_partition = N ? (const int32_t*)(dp + i_pid) : nullptr;
-        d.c.out_member_rank = N ? (const int32_t*)(dp + i_rank) : nullptr;
-        d.c.owned_topic = n ? (const int32_t*)(dp + i_otopic) : nullptr;
-        d.c.owned_partition = n ? (const int32_t*)(dp + i_opid) : nullptr;
-        d.member_off = (int64_t*)(dp + o_member_off);
-        d.c.member_kept = h_count[0] ? (int64_t*)(dp + o_count[0]) : nullptr;
-        d.c.member_fresh = h_count[1] ? (int64_t*)(dp + o_count[1]) : nullptr;
-        d.c.member_pending = h_count[2] ? (int64_t*)(dp + o_count[2]) : nullptr;
-        d.c.member_release = h_count[3] ? (int64_t*)(dp + o_count[3]) : nullptr;
-        d.c.topic_withheld = h.topic_withheld ? (int64_t*)(dp + o_withheld) : nullptr;
-        d.c.summary = h.summary ? (int64_t*)(dp + o_summary) : nullptr;
-        d.c.prev_owner = h.prev_owner ? (int32_t*)(dp + o_prev) : nullptr;
-        d.c.coop_rank = h.coop_rank ? (int32_t*)(dp + o_coop) : nullptr;
-        d.grouped_topic = host.grouped_topic ? (int32_t*)(dp + o_gtopic) : nullptr;
-        d.grouped_partition = (int32_t*)(dp + o_gpart);
-        Lane& ln = sh.lanes[0];
-        hipStream_t st = ln.stream;
-        if (in_bytes) LA_HIP(ctx, hipMemcpyAsync(dp, hp, in_bytes, hipMemcpyHostToDevice, st));
-        hipError_t e = la::cooperative_round_launch(s, ln.large, d, (args->flags & LA_COOP_FORCE_TABLE) != 0, ln.d_status, st);
-        if (e != hipSuccess) {
-            (void)hipStreamSynchronize(st);
-            return hip_fail(ctx, e, "cooperative_round: %s");
-        }
-        LA_HIP(ctx, hipMemcpyAsync(hp + in_bytes, dp + in_bytes, out_bytes, hipMemcpyDeviceToHost, st));
-        if (int rc = sync_status(ctx, ln, st)) return rc;
-        memcpy(host.member_off, hp + o_member_off, (M + 1) * 8);
-        for (int w = 0; w < 4; ++w)
-            if (h_count[w] && M) memcpy(h_count[w], hp + o_count[w], M * 8);
-        if (h.topic_withheld && T) memcpy(h.topic_withheld, hp + o_withheld, T * 8);
-        if (h.summary) memcpy(h.summary, hp + o_summary, 6 * 8);
-        if (N) {
-            if (h.prev_owner) memcpy(h.prev_owner, hp + o_prev, N * 4);
-            if (h.coop_rank) memcpy(h.coop_rank, hp + o_coop, N * 4);
-            if (host.grouped_topic) memcpy(host.grouped_topic, hp + o_gtopic, N * 4);
-            memcpy(host.grouped_partition, hp + o_gpart, N * 4);
-        }
-        return LA_OK;
-    }
-}
-
-LA_API int la_cooperative_round(la_ctx* ctx, const la_coop_round_args* args) {
-    return shard_entry<true>(ctx, 0, "exception in la_cooperative_round", [&](Shard& sh) -> int { return coop_round_host(ctx, sh, args); });
-}
-
-// A cooperative rebalance from host buffers in one call: an assign call and the round on its result.  FUSED (la_host.hip,
-// assign_small_zc): the round kernel is the zero-copy call's last launch.  GENERAL: the assign call into the context's own host
-// buffers, then the body of la_cooperative_round on them; the caller's arrays are written only after both have succeeded.
-LA_API int la_assign_batch_cooperative(la_ctx* ctx, const la_assign_coop_args* g) {
-    DeviceGuard restore_device;
-    LaunchSpan span(ctx);
-    HintSpender spend_hints(ctx);
-    if (!ctx) return LA_EINVAL;
-    try {
-        if (!g) return fail(ctx, LA_EINVAL, "args is NULL");
-        if (g->struct_size < (int32_t)sizeof(la_assign_coop_args))
-            return fail(ctx, LA_EINVAL, "la_assign_coop_args.struct_size is %d, this library takes %d and above", (int)g->struct_size, (int)sizeof(la_assign_coop_args));
-        if (g->flags & ~LA_COOP_FORCE_TABLE) return fail(ctx, LA_EINVAL, "la_assign_coop_args.flags holds a bit this library does not know");
-        if (g->reserved != 0) return fail(ctx, LA_EINVAL, "la_assign_coop_args.reserved must be 0");
-        if (g->n_topics < 0 || g->n_members < 0 || g->n_owned < 0) return fail(ctx, LA_EINVAL, "negative size");
-        if (g->n_members > la::kMovesMaxMembers) return fail(ctx, LA_EINVAL, "n_members must be below 2^30");
-        if (g->n_owned > 0 && (!g->owned_member_off || !g->owned_topic || !g->owned_partition))
-            return fail(ctx, LA_EINVAL, "null owned buffer");
-        if (!g->member_off) return fail(ctx, LA_EINVAL, "member_off is NULL");
-        const int32_t T = g->n_topics;
-        if (T > 0 && g->part_off && g->part_off[T] > 0 && !g->grouped_partition) return fail(ctx, LA_EINVAL, "grouped_partition is NULL");
-        la::CoopRoundCall q{};
-        q.c.n_topics = T;
-        q.c.n_members = g->n_members;
-        q.c.n_owned = g->n_owned;
-        q.c.owned_off = g->owned_member_off;
-        q.c.owned_topic = g->owned_topic;
-        q.c.owned_partition = g->owned_partition;
-        q.c.prev_owner = g->prev_owner;
-        q.c.coop_rank = g->coop_member_rank;
-        q.c.member_kept = g->member_kept;
-        q.c.member_fresh = g->member_fresh;
-        q.c.member_pending = g->member_pending;
-        q.c.member_release = g->member_release;
-        q.c.topic_withheld = g->topic_withheld;
-        q.c.summary = g->summary;
-        q.member_off = g->member_off;
-        q.grouped_topic = g->grouped_topic;
-        q.grouped_partition = g->grouped_partition;
-        bool done = false;
-        HostCall c;
-        c.T = T; c.part_off = g->part_off; c.pid = g->partition_id; c.cons_off = g->cons_off; c.cons_rank = g->cons_rank;
-        c.out_pid = g->out_partition; c.out_rank = g->out_member_rank; c.out_total = g->out_total_lag;
-        if (g->lag) {                                            // la_assign_batch_lags
-            c.reset_mode = LA_RESET_LATEST;
-            c.lag = g->lag;
-        } else {                                                 // la_assign_batch, or la_assign_batch_sparse without a dense begin
-            c.reset_mode = g->reset_mode; c.end = g->end_off; c.committed = g->committed_off; c.begin = g->begin_off;
-            if (!g->begin_off) { c.sparse = true; c.n_none = g->n_none; c.none_index = g->none_index; c.none_begin = g->none_begin; }
-        }
-        c.coop = &q; c.coop_force_table = (g->flags & LA_COOP_FORCE_TABLE) != 0; c.coop_done = &done;
-        if (int rc = assign_host(ctx, c)) return rc;
-        if (done) return LA_OK;
-        // the general form: the target lies in ctx->coop_target (totals | ids | ranks) -- or there is none (no topics)
-        const int64_t N = T > 0 ? g->part_off[T] : 0, K = T > 0 ? g->cons_off[T] : 0;
-        int64_t* const t_total = T > 0 ? ctx->coop_target.data() : nullptr;
-        int32_t* const t_pid = T > 0 ? (int32_t*)(t_total + K) : nullptr;
-        int32_t* const t_rank = T > 0 ? t_pid + N : nullptr;
-        la_coop_round_args ra{};
-        ra.struct_size = (int32_t)sizeof ra;
-        ra.flags = g->flags;
-        ra.adjust.struct_size = (int32_t)sizeof ra.adjust;
-        ra.adjust.n_topics = T;
-        ra.adjust.n_partitions = N;
-        ra.adjust.d_part_off = g->part_off;
-        ra.adjust.d_out_partition = t_pid;
-        ra.adjust.d_out_member_rank = t_rank;
-        ra.adjust.n_members = g->n_members;
-        ra.adjust.n_owned = g->n_owned;
-        ra.adjust.d_owned_member_off = g->owned_member_off;
-        ra.adjust.d_owned_topic = g->owned_topic;
-        ra.adjust.d_owned_partition = g->owned_partition;
-        ra.adjust.d_prev_owner = g->prev_owner;
-        ra.adjust.d_coop_member_rank = g->coop_member_rank;
-        ra.adjust.d_member_kept = g->member_kept;
-        ra.adjust.d_member_fresh = g->member_fresh;
-        ra.adjust.d_member_pending = g->member_pending;
-        ra.adjust.d_member_release = g->member_release;
-        ra.adjust.d_topic_withheld = g->topic_withheld;
-        ra.adjust.d_summary = g->summary;
-        ra.member_off = g->member_off;
-        ra.grouped_topic = g->grouped_topic;
-        ra.grouped_partition = g->grouped_partition;
-        Shard& sh = ctx->shards[0];
-        LA_HIP(ctx, hipSetDevice(sh.device));
-        if (int rc = coop_round_host(ctx, sh, &ra)) return rc;
-        if (g->out_total_lag && K > 0) memcpy(g->out_total_lag, t_total, (size_t)K * 8);
-        if (g->out_partition && N > 0) {
-            memcpy(g->out_partition, t_pid, (size_t)N * 4);
-            memcpy(g->out_member_rank, t_rank, (size_t)N * 4);
-        }
-        return LA_OK;
-    } catch (...) {
-        return fail(ctx, LA_ENOMEM, "exception in la_assign_batch_cooperative");
-    }
-}
-
-// A cooperative rebalance on the STICKY order from host buffers in one call.  FUSED (la_host.hip, assign_small_zc): the sticky
-// round kernel is the zero-copy call's last launch -- one packing, no copy, one wait.  GENERAL: the assign call into buffers of
-// the context's own (as coop_take_general arranges it), then target, owned arrays, partition ids and the lag source through the
-// cooperative staging buffers -- one copy in, la_cooperative_round_sticky_device on lane 0's stream, one copy out, one wait.  The
-// caller's arrays are written only after everything has succeeded.  LA_NO_FUSED_STICKY (environment, read at every call): the
-// GENERAL form as it was before there was a fused one, for every call (A/B: tests, tools/coop_sticky_probe.py).
-LA_API int la_assign_batch_cooperative_sticky(la_ctx* ctx, const la_assign_sticky_args* args) {
-    DeviceGuard restore_device;
-    LaunchSpan span(ctx);
-    HintSpender spend_hints(ctx);
-    if (!ctx) return LA_EINVAL;
-    try {
-        if (!args) return fail(ctx, LA_EINVAL, "args is NULL");
-        if (args->struct_size < (int32_t)sizeof(la_assign_sticky_args))
-            return fail(ctx, LA_EINVAL, "la_assign_sticky_args.struct_size is %d, this library takes %d and above", (int)args->struct_size, (int)sizeof(la_assign_sticky_args));
-        if (args->reserved != 0) return fail(ctx, LA_EINVAL, "la_assign_sticky_args.reserved must be 0");
-        const la_assign_coop_args* g = &args->coop;
-        if (g->flags & ~(LA_COOP_FORCE_TABLE | LA_COOP_STICKY_LARGE)) return fail(ctx, LA_EINVAL, "la_assign_sticky_args.coop.flags holds a bit this library does not know");
-        if (g->reserved != 0) return fail(ctx, LA_EINVAL, "la_assign_coop_args.reserved must be 0");
-        if (g->n_topics < 0 || g->n_members < 0 || g->n_owned < 0) return fail(ctx, LA_EINVAL, "negative size");
-        if (g->n_members > la::kMovesMaxMembers) return fail(ctx, LA_EINVAL, "n_members must be below 2^30");
-        if (g->n_owned > 0 && (!g->owned_member_off || !g->owned_topic || !g->owned_partition))
-            return fail(ctx, LA_EINVAL, "null owned buffer");
-        if (!g->member_off) return fail(ctx, LA_EINVAL, "member_off is NULL");
-        const int32_t T = g->n_topics;
-        if (T > 0 && g->part_off && g->part_off[T] > 0 && !g->grouped_partition) return fail(ctx, LA_EINVAL, "grouped_partition is NULL");
-        if ((g->out_partition == nullptr) != (g->out_member_rank == nullptr)) return fail(ctx, LA_EINVAL, "out_partition and out_member_rank: both or neither");
-        // the assign call, into the context's own buffers (totals | ids | ranks); offsets it would refuse get no buffer and are
-        // refused by it
-        HostCall c;
-        c.T = T; c.part_off = g->part_off; c.pid = g->partition_id; c.cons_off = g->cons_off; c.cons_rank = g->cons_rank;
-        const bool sized = T > 0 && g->part_off && g->cons_off && g->part_off[T] >= 0 && g->cons_off[T] >= 0 &&
-                           g->part_off[T] <= 0x7FFFFFFF && g->cons_off[T] <= 0x7FFFFFFF;
-        if (T > 0 && !sized) return fail(ctx, LA_EINVAL, "part_off / cons_off are NULL, or end below 0 or beyond 2^31-1 entries");
-        const int64_t N = sized ? g->part_off[T] : 0, K = sized ? g->cons_off[T] : 0;
-        // the A/B hook of this entry point, read at every call (the tests and the probe compare both forms in one process)
-        const bool try_fused = getenv("LA_NO_FUSED_STICKY") == nullptr;
-        la::CoopRoundCall q{};
-        StickyOuts so;
-        bool done = false;
-        if (try_fused) {
-            // assign_host decides: FUSED ends in the sticky round's finishing form and sets `done`; otherwise it has become the plain
-            // assign call into the context's own buffers that the GENERAL form below starts from (coop_take_general)
-            q.c.n_topics = T;
-            q.c.n_members = g->n_members;
-            q.c.n_owned = g->n_owned;
-            q.c.owned_off = g->owned_member_off;
-            q.c.owned_topic = g->owned_topic;
-            q.c.owned_partition = g->owned_partition;
-            q.c.prev_owner = g->prev_owner;
-            q.c.coop_rank = g->coop_member_rank;
-            q.c.member_kept = g->member_kept;
-            q.c.member_fresh = g->member_fresh;
-            q.c.member_pending = g->member_pending;
-            q.c.member_release = g->member_release;
-            q.c.topic_withheld = g->topic_withheld;
-            q.c.summary = g->summary;
-            q.member_off = g->member_off;
-            q.grouped_topic = g->grouped_topic;
-            q.grouped_partition = g->grouped_partition;
-            so.sticky_partition = args->sticky_partition;
-            so.topic_kept = args->topic_kept;
-            so.topic_saved = args->topic_saved;
-            so.sticky_summary = args->sticky_summary;
-            c.out_pid = g->out_partition; c.out_rank = g->out_member_rank; c.out_total = g->out_total_lag;
-            c.coop = &q; c.coop_force_table = (g->flags & LA_COOP_FORCE_TABLE) != 0; c.coop_done = &done; c.sticky = &so;
-        } else if (sized) {
-            ctx->coop_target.resize((size_t)K + (size_t)N + 1);
-            c.out_total = ctx->coop_target.data();
-            c.out_pid = (int32_t*)(ctx->coop_target.data() + K);
-            c.out_rank = c.out_pid + N;
-        }
-        const bool latest = g->lag != nullptr || g->reset_mode == LA_RESET_LATEST;
-        if (g->lag) {                                            // la_assign_batch_lags
-            c.reset_mode = LA_RESET_LATEST;
-            c.lag = g->lag;
-        } else {                                                 // la_assign_batch, or la_assign_batch_sparse without a dense begin
-            c.reset_mode = g->reset_mode; c.end = g->end_off; c.committed = g->committed_off; c.begin = g->begin_off;
-            if (!g->begin_off) { c.sparse = true; c.n_none = g->n_none; c.none_index = g->none_index; c.none_begin = g->none_begin; }
-        }
-        if (int rc = assign_host(ctx, c)) return rc;
-        if (done) return LA_OK;
-        const int64_t* const t_total = sized ? ctx->coop_target.data() : nullptr;
-        const int32_t* const t_pid = sized ? (const int32_t*)(t_total + K) : nullptr;
-        const int32_t* const t_rank = sized ? t_pid + N : nullptr;
-        int64_t hint = 0;                                        // the host knows the topics: the hint is the largest of them
-        for (int32_t t = 0; t < T; ++t) hint = std::max<int64_t>(hint, g->part_off[t + 1] - g->part_off[t]);
-
-        // staging: 8-byte arrays first, so every array is aligned for its element
-        Shard& sh = ctx->shards[0];
-        LA_HIP(ctx, hipSetDevice(sh.device));
-        const size_t n = (size_t)g->n_owned, M = (size_t)g->n_members, Ts = (size_t)T, Ns = (size_t)N;
-        const bool use_begin = !g->lag && !latest;
-        size_t at = 0;
-        auto take = [&](size_t bytes) { const size_t o = at; at += (bytes + 7) & ~(size_t)7; return o; };
-        const size_t i_part_off = take(T > 0 ? (Ts + 1) * 8 : 0), i_owned_off = take(n ? (M + 1) * 8 : 0);
-        const size_t i_lag = take(g->lag ? Ns * 8 : 0), i_end = take(g->lag ? 0 : Ns * 8), i_committed = take(g->lag ? 0 : Ns * 8);
-        const size_t i_begin = take(use_begin ? Ns * 8 : 0);
-        const size_t i_pid = take(Ns * 4), i_rank = take(Ns * 4), i_input_id = take(Ns * 4), i_otopic = take(n * 4), i_opid = take(n * 4);
-        const size_t in_bytes = at;
-        const size_t o_member_off = take((M + 1) * 8);
-        size_t o_count[4];
-        for (int w = 0; w < 4; ++w) o_count[w] = take(M * 8);
-        const size_t o_withheld = take(Ts * 8), o_summary = take(6 * 8), o_kept = take(Ts * 8), o_saved = take(Ts * 8), o_ssum = take(4 * 8);
-        const size_t o_prev = take(Ns * 4), o_coop = take(Ns * 4), o_gtopic = take(Ns * 4), o_gpart = take(Ns * 4), o_sticky = take(Ns * 4);
-        const size_t total = at, out_bytes = total - in_bytes;
-        la::CoopScratch& s = sh.coop;
-        if (int rc = coop_stage_reserve(ctx, s, total)) return rc;
-        char* const hp = static_cast<char*>(s.stage_h);
-        char* const dp = static_cast<char*>(s.stage_d);
-        if (T > 0) memcpy(hp + i_part_off, g->part_off, (Ts + 1) * 8);
-        if (n) {
-            memcpy(hp + i_owned_off, g->owned_member_off, (M + 1) * 8);
-            memcpy(hp + i_otopic, g->owned_topic, n * 4);
-            memcpy(hp + i_opid, g->owned_partition, n * 4);
-        }
-        if (Ns) {
-            memcpy(hp + i_pid, t_pid, Ns * 4);
-            memcpy(hp + i_rank, t_rank, Ns * 4);
-            memcpy(hp + i_input_id, g->partition_id, Ns * 4);
-            if (g->lag) {
-                memcpy(hp + i_lag, g->lag, Ns * 8);
-            } else {
-                memcpy(hp + i_end, g->end_off, Ns * 8);
-                memcpy(hp + i_committed, g->committed_off, Ns * 8);
-                if (use_begin && g->begin_off) {
-                    memcpy(hp + i_begin, g->begin_off, Ns * 8);
-                } else if (use_begin) {                          // the sparse list over zeros: marshalling, the lag itself is lag_of's
-                    int64_t* const begin = (int64_t*)(hp + i_begin);
-                    memset(begin, 0, Ns * 8);
-                    for (int64_t i = 0; i < g->n_none; ++i)
-                        if (g->none_index[i] >= 0 && g->none_index[i] < N) begin[g->none_index[i]] = g->none_begin[i];
-                }
-            }
-        }
-        la_device_batch b{};
-        b.n_topics = T;
-        b.reset_mode = latest ? LA_RESET_LATEST : g->reset_mode;
-        b.n_partitions = N;
-        b.max_partitions_per_topic = hint;
-        if ((g->flags & LA_COOP_STICKY_LARGE) && T > 0) {
-            b.flags |= LA_FLAG_STICKY_LARGE;
-            b.h_part_off = g->part_off;
-        }
-        b.d_part_off = T > 0 ? (int64_t*)(dp + i_part_off) : nullptr;
-        b.d_partition_id = Ns ? (int32_t*)(dp + i_input_id) : nullptr;
-        b.d_lag = g->lag && Ns ? (int64_t*)(dp + i_lag) : nullptr;
-        b.d_end_off = !g->lag && Ns ? (int64_t*)(dp + i_end) : nullptr;
-        b.d_committed_off = !g->lag && Ns ? (int64_t*)(dp + i_committed) : nullptr;
-        b.d_begin_off = use_begin && Ns ? (int64_t*)(dp + i_begin) : nullptr;
-        b.d_out_partition = Ns ? (int32_t*)(dp + i_pid) : nullptr;
-        b.d_out_member_rank = Ns ? (int32_t*)(dp + i_rank) : nullptr;
-        la_coop_sticky_args a{};
-        a.struct_size = (int32_t)sizeof a;
-        a.flags = g->flags & LA_COOP_FORCE_TABLE;
-        la_coop_args& adj = a.round.adjust;
-        adj.n_members = g->n_members;
-        adj.n_owned = g->n_owned;
-        adj.d_owned_member_off = n ? (int64_t*)(dp + i_owned_off) : nullptr;
-        adj.d_owned_topic = n ? (int32_t*)(dp + i_otopic) : nullptr;
-        adj.d_owned_partition = n ? (int32_t*)(dp + i_opid) : nullptr;
-        adj.d_prev_owner = (int32_t*)(dp + o_prev);
-        adj.d_coop_member_rank = (int32_t*)(dp + o_coop);
-        adj.d_member_kept = (int64_t*)(dp + o_count[0]);
-        adj.d_member_fresh = (int64_t*)(dp + o_count[1]);
-        adj.d_member_pending = (int64_t*)(dp + o_count[2]);
-        adj.d_member_release = (int64_t*)(dp + o_count[3]);
-        adj.d_topic_withheld = (int64_t*)(dp + o_withheld);
-        adj.d_summary = (int64_t*)(dp + o_summary);
-        a.round.member_off = (int64_t*)(dp + o_member_off);
-        a.round.grouped_topic = (int32_t*)(dp + o_gtopic);
-        a.round.grouped_partition = (int32_t*)(dp + o_gpart);
-        a.d_sticky_partition = (int32_t*)(dp + o_sticky);
-        a.d_topic_kept = (int64_t*)(dp + o_kept);
-        a.d_topic_saved = (int64_t*)(dp + o_saved);
-        a.d_sticky_summary = (int64_t*)(dp + o_ssum);
-        la::CoopStickyCall k{};
-        if (int rc = coop_sticky_call_of(ctx, &b, &a, &k)) return rc;
-        Lane& ln = sh.lanes[0];
-        hipStream_t st = ln.stream;
-        if (in_bytes) LA_HIP(ctx, hipMemcpyAsync(dp, hp, in_bytes, hipMemcpyHostToDevice, st));
-        hipError_t e = la::cooperative_round_sticky_launch(s, sh.sticky, ln.large, k, (g->flags & LA_COOP_FORCE_TABLE) != 0, ln.d_status, st);
-        if (e != hipSuccess) {
-            (void)hipStreamSynchronize(st);
-            return hip_fail(ctx, e, "cooperative_round_sticky: %s");
-        }
-        LA_HIP(ctx, hipMemcpyAsync(hp + in_bytes, dp + in_bytes, out_bytes, hipMemcpyDeviceToHost, st));
-        if (int rc = sync_status(ctx, ln, st)) return rc;
-        // everything has succeeded: the caller's arrays
-        memcpy(g->member_off, hp + o_member_off, (M + 1) * 8);
-        int64_t* const h_count[4] = {g->member_kept, g->member_fresh, g->member_pending, g->member_release};
-        for (int w = 0; w < 4; ++w)
-            if (h_count[w] && M) memcpy(h_count[w], hp + o_count[w], M * 8);
-        if (g->topic_withheld && Ts) memcpy(g->topic_withheld, hp + o_withheld, Ts * 8);
-        if (g->summary) memcpy(g->summary, hp + o_summary, 6 * 8);
-        if (args->topic_kept && Ts) memcpy(args->topic_kept, hp + o_kept, Ts * 8);
-        if (args->topic_saved && Ts) memcpy(args->topic_saved, hp + o_saved, Ts * 8);
-        if (args->sticky_summary) memcpy(args->sticky_summary, hp + o_ssum, 4 * 8);
-        if (Ns) {
-            if (g->prev_owner) memcpy(g->prev_owner, hp + o_prev, Ns * 4);
-            if (g->coop_member_rank) memcpy(g->coop_member_rank, hp + o_coop, Ns * 4);
-            if (g->grouped_topic) memcpy(g->grouped_topic, hp + o_gtopic, Ns * 4);
-            memcpy(g->grouped_partition, hp + o_gpart, Ns * 4);
-            if (args->sticky_partition) memcpy(args->sticky_partition, hp + o_sticky, Ns * 4);
-            if (g->out_partition) {
-                memcpy(g->out_partition, t_pid, Ns * 4);
-                memcpy(g->out_member_rank, t_rank, Ns * 4);
-            }
-        }
-        if (g->out_total_lag && K > 0) memcpy(g->out_total_lag, t_total, (size_t)K * 8);
-        return LA_OK;
-    } catch (...) {
-        return fail(ctx, LA_ENOMEM, "exception in la_assign_batch_cooperative_sticky");
-    }
 }
 
 LA_API int la_group_by_member(la_ctx* ctx, int32_t n_topics, const int64_t* part_off, const int32_t* out_partition,

@@ -1,6 +1,6 @@
 // la_coop.h -- host-visible declarations of la_cooperative_adjust_device (la_coop.hip) and of la_cooperative_round[_device]
 // (la_coop_small.hip): the scratch, the call structs, the launchers (the status bit, kStatusCoop, stands with the others in
-// la_kernels.h).
+// la_kernels.h).  The entry points of lagassign.h over them, and the checks that make these call structs, are la_api_coop.hip.
 #pragma once
 #include "la_kernels.h"
 #include "la_group_small.h"

@@ -1,6 +1,6 @@
-// la_ctx.h -- what la_api.hip (the C ABI, the dispatcher) and la_host.hip (the host-buffer calls) share: the context and its
-// shards and lanes, error reporting, the grow-only buffers, the status word, the parked worker threads and the preamble of the
-// shard-scoped entry points.
+// la_ctx.h -- what la_api.hip (the C ABI, the dispatcher), la_api_coop.hip (the cooperative and sticky entry points) and
+// la_host.hip (the host-buffer calls) share: the context and its shards and lanes, error reporting, the grow-only buffers, the
+// status word, the parked worker threads and the preambles of the entry points.
 #pragma once
 #include "../../include/lagassign.h"
 
@@ -236,6 +236,18 @@ struct LaunchSpan {
     LaunchSpan& operator=(const LaunchSpan&) = delete;
 };
 
+// la_hint_next_call is one-shot: "forgotten when the next host-buffer assign call returns, whatever it returns".  assign_host
+// takes the hints when it starts; every host-buffer entry point also holds one of these, so that a call that returns BEFORE
+// it gets there (a NULL result array, n_topics <= 0, a NULL lag array) spends them too and a stale bound cannot fail the
+// next, unrelated call.
+struct HintSpender {
+    la_ctx* ctx;
+    explicit HintSpender(la_ctx* c) : ctx(c) {}
+    ~HintSpender() { if (ctx) ctx->hints_set = false; }
+    HintSpender(const HintSpender&) = delete;
+    HintSpender& operator=(const HintSpender&) = delete;
+};
+
 inline int fail(la_ctx* ctx, int code, const char* fmt, ...) {
     char buf[512];
     va_list ap;
@@ -387,9 +399,14 @@ struct StagedBatch {
     bool tail_done = false;
 };
 int enqueue_batch(la_ctx* ctx, Lane& ln, const la_device_batch* b, hipStream_t stream, StagedBatch* staged = nullptr);
+
+// ---- la_api_coop.hip: the cooperative and sticky entry points ------------------------------------------------------------------
 // la_device_batch + la_coop_sticky_args, checked as la_cooperative_round_sticky_device checks them (the fused host call builds its
 // round through the same door)
 int coop_sticky_call_of(la_ctx* ctx, const la_device_batch* batch, const la_coop_sticky_args* args, la::CoopStickyCall* out);
+// ... and the la_coop_round_args of it from a round whose owned arrays and outputs already lie where the device reaches them (the
+// target fields stay empty: coop_sticky_call_of takes the batch's)
+la_coop_round_args coop_round_args_of(const la::CoopRoundCall& r);
 
 // ---- la_host.hip: the host-buffer calls ------------------------------------------------------------------------------------
 struct Shape {
@@ -436,10 +453,11 @@ struct HostCall {
     int64_t max_lag = 0, max_id = 0;
     // la_assign_batch_cooperative: the owned lists and the round's outputs, all HOST memory (coop->c.part_off / out_partition /
     // out_member_rank and n_partitions are not looked at: they are this call's).  A zero-copy staged call within the limits of
-    // la_coop.h ends in the round kernel's finishing form and sets *coop_done; any other call is a plain assign call that leaves
-    // *coop_done alone -- the entry point then runs the round on its results.
+    // la_coop.h ends in the round kernel's finishing form and sets *coop_done; any other call, and every call with coop_general
+    // (LA_COOP_FORCE_TABLE, LA_NO_FUSED_STICKY), is a plain assign call that leaves *coop_done alone -- the entry point then runs
+    // the round on its results.
     const la::CoopRoundCall* coop = nullptr;
-    bool coop_force_table = false;
+    bool coop_general = false;
     bool* coop_done = nullptr;
     // la_assign_batch_cooperative_sticky: beside `coop`, the four outputs of the sticky order (HOST memory, each may be null).  The
     // fused form is then the STICKY round kernel's finishing form, within the same limits; any other call leaves *coop_done alone.

@@ -669,16 +669,10 @@ hipError_t small_group_launch(const HostCall& c, Lane& ln, const SmallLayout& L,
                                       L.at<int32_t>(lists_base, kOutListPartition), nullptr, status, st, fin_flag, finished);
 }
 
-// la_assign_batch_cooperative, fused form: the round of a zero-copy call as its last launch.  The target at d (device memory),
-// the part offsets and the owned arrays at m (the device's view of the staging buffer), every output to m, the completion word
-// where the calling thread spins.
-hipError_t small_coop_launch(const HostCall& c, Lane& ln, const SmallLayout& L, char* m, const char* d, hipStream_t st) {
+// The round of a fused cooperative call, both forms: the owned arrays at m (the device's view of the staging buffer) and every
+// output to m.  The target is the caller's to add.
+la::CoopRoundCall small_coop_round(const HostCall& c, const SmallLayout& L, char* m) {
     la::CoopRoundCall r = *c.coop;
-    r.c.n_topics = c.T;
-    r.c.n_partitions = c.shape.n;
-    r.c.part_off = (const int64_t*)(m + L.po);
-    r.c.out_partition = L.at<const int32_t>(d, kOutPid);
-    r.c.out_member_rank = L.at<const int32_t>(d, kOutRank);
     const bool owned = r.c.n_owned > 0;
     r.c.owned_off = owned ? (const int64_t*)(m + L.oo) : nullptr;
     r.c.owned_topic = owned ? (const int32_t*)(m + L.otp) : nullptr;
@@ -694,6 +688,18 @@ hipError_t small_coop_launch(const HostCall& c, Lane& ln, const SmallLayout& L, 
     r.member_off = L.at<int64_t>(m, kOutMemberOff);
     r.grouped_topic = L.want<int32_t>(m, kOutListTopic);
     r.grouped_partition = L.at<int32_t>(m, kOutListPartition);
+    return r;
+}
+
+// la_assign_batch_cooperative, fused form: the round of a zero-copy call as its last launch.  The target at d (device memory),
+// the part offsets at m, the completion word where the calling thread spins.
+hipError_t small_coop_launch(const HostCall& c, Lane& ln, const SmallLayout& L, char* m, const char* d, hipStream_t st) {
+    la::CoopRoundCall r = small_coop_round(c, L, m);
+    r.c.n_topics = c.T;
+    r.c.n_partitions = c.shape.n;
+    r.c.part_off = (const int64_t*)(m + L.po);
+    r.c.out_partition = L.at<const int32_t>(d, kOutPid);
+    r.c.out_member_rank = L.at<const int32_t>(d, kOutRank);
     return la::cooperative_round_finish_launch(r, L.want<int32_t>(m, kOutPid), L.want<int32_t>(m, kOutRank), ln.d_status,
                                                (uint32_t*)(m + L.status), st);
 }
@@ -705,27 +711,9 @@ hipError_t small_coop_launch(const HostCall& c, Lane& ln, const SmallLayout& L, 
 // word where the calling thread spins.
 int small_coop_sticky_launch(la_ctx* ctx, const HostCall& c, Lane& ln, const SmallLayout& L, char* m, char* d, hipStream_t st) {
     const la_device_batch b = small_batch(c, L, m, d);
-    const la::CoopCall& q = c.coop->c;
-    const bool owned = q.n_owned > 0;
     la_coop_sticky_args a{};
     a.struct_size = (int32_t)sizeof a;
-    la_coop_args& adj = a.round.adjust;
-    adj.n_members = q.n_members;
-    adj.n_owned = q.n_owned;
-    adj.d_owned_member_off = owned ? (const int64_t*)(m + L.oo) : nullptr;
-    adj.d_owned_topic = owned ? (const int32_t*)(m + L.otp) : nullptr;
-    adj.d_owned_partition = owned ? (const int32_t*)(m + L.opp) : nullptr;
-    adj.d_prev_owner = L.want<int32_t>(m, kOutPrevOwner);
-    adj.d_coop_member_rank = L.want<int32_t>(m, kOutCoopRank);
-    adj.d_member_kept = L.want<int64_t>(m, kOutKept);
-    adj.d_member_fresh = L.want<int64_t>(m, kOutFresh);
-    adj.d_member_pending = L.want<int64_t>(m, kOutPending);
-    adj.d_member_release = L.want<int64_t>(m, kOutRelease);
-    adj.d_topic_withheld = L.want<int64_t>(m, kOutWithheld);
-    adj.d_summary = L.want<int64_t>(m, kOutSummary);
-    a.round.member_off = L.at<int64_t>(m, kOutMemberOff);
-    a.round.grouped_topic = L.want<int32_t>(m, kOutListTopic);
-    a.round.grouped_partition = L.at<int32_t>(m, kOutListPartition);
+    a.round = coop_round_args_of(small_coop_round(c, L, m));
     a.d_sticky_partition = L.at<int32_t>(m, kOutSticky);
     a.d_topic_kept = L.want<int64_t>(m, kOutTopicKept);
     a.d_topic_saved = L.want<int64_t>(m, kOutTopicSaved);
@@ -1147,13 +1135,14 @@ int assign_host(la_ctx* ctx, HostCall& c) {
     ctx->last_shards = S;
     const bool may_stage = S == 1 && !ctx->split_always && s.n > 0;
     // la_assign_batch_cooperative[_sticky].  FUSED: a zero-copy staged call within the (sticky) round kernel's limits.  Anything
-    // else is the GENERAL form (coop_take_general).
+    // else, and whatever the entry point asks for with coop_general (LA_COOP_FORCE_TABLE, the sticky call's LA_NO_FUSED_STICKY),
+    // is the GENERAL form (coop_take_general).
     if (c.coop) {
         la::CoopCall probe = c.coop->c;
         probe.n_topics = T;
         probe.n_partitions = s.n;
         const bool small = c.sticky ? la::coop_sticky_is_small(probe) : la::coop_round_is_small(probe);
-        if (!may_stage || c.coop_force_table || !small) coop_take_general(ctx, c);
+        if (!may_stage || c.coop_general || !small) coop_take_general(ctx, c);
     }
     SmallLayout L;
     int rc;

@@ -384,6 +384,47 @@ def test_errors_leave_the_outputs_untouched_and_nothing_behind(ctx, torch_dev, m
     assert ctx.last_launches() == unhinted
 
 
+@pytest.mark.parametrize("form", ["as it comes", "LA_NO_FUSED_STICKY"])
+def test_entry_refuses_bad_arguments(ctx, torch_dev, monkeypatch, form):
+    """The table of la_assign_batch_cooperative's test of this name (test_assign_coop_gpu.py), on a struct that is valid but for
+    the one field: two topics of 5 and 6 partitions, 2 members, lags mode."""
+    if form == "LA_NO_FUSED_STICKY":
+        monkeypatch.setenv("LA_NO_FUSED_STICKY", "1")
+    lib = N.load()
+    h = caught_up(38, [5, 6], 2)
+    bufs = buffers(h)
+
+    def args():
+        a = N.AssignStickyArgs()
+        a.struct_size = ctypes.sizeof(N.AssignStickyArgs)
+        ctx._fill_assign_coop(a.coop, h.part_off, h.pid, h.cons_off, h.cons_rank, h.m, *h.owned, h.lag, None, None, None, 0, None, None,
+                              False, N.AssignCoop(**{k: bufs[k] for k in N.AssignCoop._fields}))
+        for name in STICKY:
+            setattr(a, name, bufs[name].ctypes.data)
+        return a
+
+    def no_owned_arrays(a):
+        a.coop.n_owned, a.coop.owned_member_off, a.coop.owned_topic, a.coop.owned_partition = 3, None, None, None
+
+    for name, change in (("struct_size", lambda a: setattr(a, "struct_size", a.struct_size - 8)),
+                         ("an unknown flag bit", lambda a: setattr(a.coop, "flags", 4)),
+                         ("reserved", lambda a: setattr(a, "reserved", 1)), ("coop.reserved", lambda a: setattr(a.coop, "reserved", 1)),
+                         ("n_members", lambda a: setattr(a.coop, "n_members", -1)), ("n_owned without owned arrays", no_owned_arrays),
+                         ("member_off", lambda a: setattr(a.coop, "member_off", None)),
+                         ("grouped_partition", lambda a: setattr(a.coop, "grouped_partition", None)),
+                         ("out_partition without out_member_rank", lambda a: setattr(a.coop, "out_member_rank", None))):
+        a = args()
+        change(a)
+        assert lib.la_assign_batch_cooperative_sticky(ctx._h, ctypes.byref(a)) == N.LA_EINVAL, name
+        for out, b in bufs.items():
+            assert (b == SENTINEL).all(), "%s was written by a call that was refused (%s)" % (out, name)
+    assert lib.la_assign_batch_cooperative_sticky(ctx._h, None) == N.LA_EINVAL
+    assert lib.la_assign_batch_cooperative_sticky(None, ctypes.byref(args())) == N.LA_EINVAL
+    a = args()
+    assert lib.la_assign_batch_cooperative_sticky(ctx._h, ctypes.byref(a)) == N.LA_OK
+    same(bufs, h.expect("lag"), form)
+
+
 # ---- 8: buffer contract ---------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("mode", ["lag", "dense", "sparse"])
 def test_guarded_views_at_shift_one(ctx, torch_dev, monkeypatch, mode):
