@@ -1116,6 +1116,72 @@ typedef struct la_assign_sticky_args {
 } la_assign_sticky_args;
 int la_assign_batch_cooperative_sticky(la_ctx *ctx, const la_assign_sticky_args *args);
 
+/* The PINNED assignment: the follow-up of a cooperative rebalance that moves nothing that is owned (nothing in the reference
+ * computes it).  The cooperative round withholds what changes owner and asks for a follow-up rebalance; that follow-up only
+ * settles if it hands the withheld partitions out WITHOUT moving the owned ones, and the reference's greedy over fresh lags
+ * does not: a lagging group's offsets move between two rebalances and most of the target moves with them.  Here a partition
+ * that a subscriber of its topic owns stays with that owner and only the others are dealt out, by the reference's own rule,
+ * from bins that start with what every consumer already holds.
+ *   batch   the struct an assign call takes: topics, partition ids, the lag source (d_lag, or begin / end / committed with
+ *           reset_mode, the lag computed exactly as the assign call computes it), d_cons_off / d_cons_rank, and the three result
+ *           arrays.  algo, the hints, h_part_off / h_cons_off and every flag are ignored, except LA_FLAG_WIRE_OUT: LA_EINVAL.
+ *   args    the owned lists, as la_coop_args has them, with the same rules: member r claims the entries
+ *           [d_owned_member_off[r], d_owned_member_off[r+1]), entries before off[0] and from off[M] on are not looked at,
+ *           topic -1 is stale; n_owned == 0: nobody owns anything and the three pointers may be NULL.
+ * For topic t with consumer ranks R = cons_rank[c0:c1] (strictly ascending) and input partitions j of lag_j and id_j, q_j the
+ * member whose owned slice holds (t, id_j), or -1:
+ *   1  j is PINNED iff q_j is one of R, k_j its index there.  A partition whose claimant does not consume the topic is FOREIGN:
+ *      it is dealt out like an unowned one (and the round that follows withholds it, as it should).
+ *   2  every consumer k starts with count_k = its pinned partitions and total_k = the wrapping int64 sum of their lags: all
+ *      pinned partitions are in the bins before anything is dealt.
+ *   3  the positions are the reference's order, lag descending (signed), id ascending: d_out_partition is what
+ *      la_assign_batch_device writes for the same inputs, bit for bit.
+ *   4  walking the positions in ascending order, a pinned partition gets q_j; any other goes to the k with the least
+ *      (count_k, total_k, R[k]), compared as Long.compare does; then count_k += 1, total_k += lag (wrapping).
+ *   5  a topic without consumers: every rank is -1.  d_out_total_lag[c0 + k] is the final total_k.
+ * With nothing owned the result IS the assign call's, bit for bit.  An input id that appears twice in a topic matches twice
+ * (no error).  The three results have the layout of an assign result: la_group_by_member_device, the cooperative calls,
+ * la_member_loads_device and la_assignment_moves_device take them as they are.  d_out_total_lag may be NULL.
+ *   d_topic_free[T]   the partitions of the topic that are not pinned (what rule 4 dealt out; in a topic without consumers
+ *                     all of them)
+ *   d_summary[4]      pinned, free, foreign (part of free), stale: owned entries inside [off[0], off[M]) that matched no
+ *                     partition, those with topic -1 included
+ * Both are OVERWRITTEN and may be NULL.  T == 0, N == 0 and n_owned == 0 are valid.  n_members < 2^30.
+ * Reported by la_sync as LA_EINVAL: a cons_rank segment that does not ascend strictly (the assign call's status bit); an owned
+ * topic outside [-1, T) or the same (topic, id) claimed twice (the cooperative calls' bit).  As LA_ESHAPE: owned offsets that
+ * do not ascend inside [0, n_owned] (positions come from the walk over the owned arrays alone), part or consumer offsets of a
+ * topic that descend or leave [0, N] / [0, K] -- such a topic is skipped -- and a topic of more than LA_PINNED_MAX_PARTITIONS
+ * partitions or LA_PINNED_MAX_CONSUMERS consumers: nothing is written for it, neither its results nor its totals, it counts
+ * nowhere, and the other topics are done as usual.
+ * One workgroup per topic holds the topic in its LDS.  The join is the (topic, id) table of la_cooperative_adjust_device, the
+ * shard's own buffer: never the assign scratch (kept results stay valid), LA_ENOMEM with nothing enqueued when it cannot be
+ * had, and this call is ordered with the shard's other cooperative calls.  At most two kernel launches behind the memsets
+ * (la_last_launches): insert the owned entries, do the topics.  The call may allocate: it must not be captured.  Buffer
+ * contract as everywhere in this header.  The call runs on shard 0.
+ * struct_size: sizeof(la_pinned_args) of the caller's header; less than this library's is LA_EINVAL.  reserved, reserved2: 0. */
+#define LA_PINNED_MAX_PARTITIONS 4096
+#define LA_PINNED_MAX_CONSUMERS  2048
+typedef struct la_pinned_args {
+    int32_t struct_size, reserved;           /* sizeof(la_pinned_args) of the caller's header; 0 */
+    int32_t n_members, reserved2;            /* M; 0 */
+    int64_t n_owned;                         /* capacity of d_owned_topic / d_owned_partition */
+    const int64_t *d_owned_member_off;       /* [M+1] */
+    const int32_t *d_owned_topic, *d_owned_partition;   /* [n_owned] */
+    int64_t *d_topic_free;                   /* [T] or NULL */
+    int64_t *d_summary;                      /* [4] or NULL: pinned, free, foreign (part of free), stale */
+} la_pinned_args;
+int la_assign_pinned_device(la_ctx *ctx, const la_device_batch *batch, const la_pinned_args *args, void *stream);
+
+/* LA_COOP_PINNED, in la_assign_coop_args.flags of la_assign_batch_cooperative only (every other entry answers LA_EINVAL to the
+ * bit): the TARGET of the call is the pinned assignment above instead of the assign call's.  Every output keeps its meaning;
+ * out_partition, out_member_rank and out_total_lag describe the pinned target.  The inputs and the owned arrays travel as ONE
+ * H2D copy through the cooperative staging buffers of shard 0 (the sparse begin is scattered over zeros while packing), the
+ * pinned assignment and then the round run on device memory on la_stream, the outputs come back as ONE D2H copy, one wait.  There
+ * is no fused form.  A topic over LA_PINNED_MAX_PARTITIONS / LA_PINNED_MAX_CONSUMERS is LA_ESHAPE at the call, with nothing
+ * enqueued: the caller falls back to the call without the flag.  On any error the caller's outputs are left as they were.  The
+ * call makes NO promise about la_group_last_by_member afterwards. */
+#define LA_COOP_PINNED 4
+
 #ifdef __cplusplus
 }
 #endif

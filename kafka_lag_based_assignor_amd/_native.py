@@ -76,6 +76,13 @@ LA_FLAG_STICKY_LARGE = 16384
 LA_COOP_STICKY_LARGE = 2
 STICKY_GLOBAL_LAUNCHES = 43
 STICKY_GLOBAL_MAX_PARTITIONS = (1 << 30) - 2
+# la_assign_pinned_device: one workgroup holds a topic in its LDS, up to these sizes (kPinnedMax* of csrc/la_coop.h); a larger
+# topic is LA_ESHAPE -- from sync() for the device call, at the call for assign_batch_cooperative(pinned=True).  At most
+# PINNED_MAX_LAUNCHES kernels: insert the owned entries, do the topics
+LA_PINNED_MAX_PARTITIONS = PINNED_MAX_PARTITIONS = 4096
+LA_PINNED_MAX_CONSUMERS = PINNED_MAX_CONSUMERS = 2048
+PINNED_MAX_LAUNCHES = 2
+LA_COOP_PINNED = 4
 
 EXPORTED_SYMBOLS = (
     "la_create", "la_destroy", "la_last_error", "la_version", "la_compute_lag",
@@ -96,6 +103,7 @@ EXPORTED_SYMBOLS = (
     "la_assign_batch_cooperative",
     "la_sticky_ties_device",
     "la_cooperative_round_sticky_device", "la_assign_batch_cooperative_sticky",
+    "la_assign_pinned_device",
 )
 
 _i64p = ctypes.POINTER(ctypes.c_int64)
@@ -204,6 +212,16 @@ class CoopStickyArgs(ctypes.Structure):
         ("struct_size", ctypes.c_int32), ("flags", ctypes.c_int32), ("round", CoopRoundArgs),
         ("d_sticky_partition", ctypes.c_void_p), ("d_topic_kept", ctypes.c_void_p), ("d_topic_saved", ctypes.c_void_p),
         ("d_sticky_summary", ctypes.c_void_p),
+    ]
+
+
+class PinnedArgs(ctypes.Structure):
+    """struct la_pinned_args (device addresses as ints, None / 0 = NULL; struct_size is filled in by assign_pinned_device)"""
+    _fields_ = [
+        ("struct_size", ctypes.c_int32), ("reserved", ctypes.c_int32), ("n_members", ctypes.c_int32), ("reserved2", ctypes.c_int32),
+        ("n_owned", ctypes.c_int64),
+        ("d_owned_member_off", ctypes.c_void_p), ("d_owned_topic", ctypes.c_void_p), ("d_owned_partition", ctypes.c_void_p),
+        ("d_topic_free", ctypes.c_void_p), ("d_summary", ctypes.c_void_p),
     ]
 
 
@@ -448,6 +466,9 @@ def load() -> ctypes.CDLL:
         L.la_sticky_ties_device_on.restype = ctypes.c_int
         L.la_sticky_ties_device_on.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(DeviceBatch), ctypes.POINTER(StickyArgs),
                                                ctypes.c_void_p]
+    if hasattr(L, "la_assign_pinned_device"):
+        L.la_assign_pinned_device.restype = ctypes.c_int
+        L.la_assign_pinned_device.argtypes = [ctypes.c_void_p, ctypes.POINTER(DeviceBatch), ctypes.POINTER(PinnedArgs), ctypes.c_void_p]
     _lib = L
     return L
 
@@ -978,6 +999,23 @@ class Context:
             args.struct_size = ctypes.sizeof(CoopStickyArgs)
         self._check(fn(self._h, ctypes.byref(batch) if batch is not None else None, ctypes.byref(args), ctypes.c_void_p(stream)))
 
+    def assign_pinned_device(self, batch: DeviceBatch, args: PinnedArgs, stream: int = 0) -> None:
+        """la_assign_pinned_device (shard 0 of the context): the PINNED assignment of `batch` (the struct an assign call takes)
+        against every member's owned list (args.d_owned_member_off int64[M+1], d_owned_topic / d_owned_partition
+        int32[n_owned]) -- a partition that a consumer of its topic owns stays with it, every consumer's bin starts from what it
+        holds, only the other partitions are dealt out by the reference's rule.  Writes batch.d_out_partition /
+        d_out_member_rank / d_out_total_lag in the layout of an assign result, args.d_topic_free (int64[T]) and args.d_summary
+        (int64[4]: pinned, free, foreign, stale), the last three optional.  Enqueued on `stream`, at most PINNED_MAX_LAUNCHES
+        kernels; sync() reports an unsorted cons_rank segment, an owned topic out of range and a (topic, id) claimed twice
+        (LA_EINVAL), offsets that do not ascend inside their arrays and a topic over PINNED_MAX_PARTITIONS /
+        PINNED_MAX_CONSUMERS (LA_ESHAPE; such a topic is left untouched).  sharding.assign_pinned_numpy is the same on the host."""
+        fn = getattr(self._lib, "la_assign_pinned_device", None)
+        if fn is None:
+            raise LagAssignError(LA_EINVAL, "this liblagassign.so has no la_assign_pinned_device")
+        if not args.struct_size:
+            args.struct_size = ctypes.sizeof(PinnedArgs)
+        self._check(fn(self._h, ctypes.byref(batch) if batch is not None else None, ctypes.byref(args), ctypes.c_void_p(stream)))
+
     def cooperative_round(self, part_off, out_partition, out_member_rank, n_members: int, owned_off, owned_topic, owned_partition,
                           force_table: bool = False) -> CoopRound:
         """la_cooperative_round: the cooperative round on host arrays (numpy in, a CoopRound of numpy arrays out) -- the target
@@ -1023,19 +1061,26 @@ class Context:
     def assign_batch_cooperative(self, part_off, partition_id, cons_off, cons_rank, n_members: int, owned_off, owned_topic,
                                  owned_partition, *, lag=None, begin=None, end=None, committed=None, reset_mode: int = 0,
                                  none_index=None, none_begin=None, force_table: bool = False,
-                                 out: Optional[AssignCoop] = None) -> AssignCoop:
+                                 out: Optional[AssignCoop] = None, pinned: bool = False) -> AssignCoop:
         """la_assign_batch_cooperative: a COOPERATIVE rebalance in one call -- the assign call (`lag`: assign_batch_lags; `begin`:
         assign_batch; neither: assign_batch_sparse with none_index / none_begin) and cooperative_round on its result against
         every member's owned list (owned_off int64[M+1], owned_topic / owned_partition; all three None when nobody owns
         anything).  Returns an AssignCoop; `out` = caller-owned buffers in that shape, None entries are not computed.  A small
         call is zero-copy with the round as its last launch; the target stays on the device for group_last_by_member().
-        sharding.assign_cooperative_numpy is the same on the host."""
+        sharding.assign_cooperative_numpy is the same on the host.
+        pinned: LA_COOP_PINNED -- the target is the PINNED assignment (assign_pinned_device: what a subscriber owns stays with
+        it, only the rest is dealt out), the follow-up form that settles; one copy each way through the cooperative staging
+        buffers, no fused form, a topic over PINNED_MAX_PARTITIONS / PINNED_MAX_CONSUMERS raises LA_ESHAPE at the call.
+        sharding.assign_cooperative_numpy with assign = the first three results of sharding.assign_pinned_numpy is the same on
+        the host."""
         fn = getattr(self._lib, "la_assign_batch_cooperative", None)
         if fn is None:
             raise LagAssignError(LA_EINVAL, "this liblagassign.so has no la_assign_batch_cooperative")
         g = AssignCoopArgs()
         out = self._fill_assign_coop(g, part_off, partition_id, cons_off, cons_rank, n_members, owned_off, owned_topic, owned_partition,
                                      lag, begin, end, committed, reset_mode, none_index, none_begin, force_table, out)
+        if pinned:
+            g.flags |= LA_COOP_PINNED
         self._check(fn(self._h, ctypes.byref(g)))
         return out
 

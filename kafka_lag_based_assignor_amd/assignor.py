@@ -49,8 +49,15 @@ class LagBasedPartitionAssignor:
         """Main.java:97-130.  Raises ValueError (IllegalArgumentException) without group.id.  ``lag.assignor.sticky.ties``
         (a boolean, default false): assign_cooperative() keeps partitions of equal lag with their previous owner.
         ``lag.assignor.sticky.ties.large`` (a boolean, default false, no effect unless the former is on): topics of more than
-        4096 partitions are re-matched too instead of keeping the reference's order."""
+        4096 partitions are re-matched too instead of keeping the reference's order.
+        ``lag.assignor.cooperative.followup``: ``full`` (the default) or ``pinned`` -- with ``pinned`` an assign_cooperative()
+        that follows one which reported ``followup``, for the same members and topic lists, deals out only the partitions
+        nobody owns (the pinned assignment), so that the follow-up settles; any other value raises ValueError."""
         self._impl.configure({str(k): str(v) for k, v in configs.items()})
+
+    def cooperative_followup(self) -> str:
+        """``lag.assignor.cooperative.followup`` as configure() read it: "full" or "pinned"."""
+        return "pinned" if self._impl.cooperative_followup_pinned() else "full"
 
     def sticky_ties(self) -> bool:
         """``lag.assignor.sticky.ties`` as configure() read it."""
@@ -98,7 +105,9 @@ class LagBasedPartitionAssignor:
         """What the last assign_cooperative() on this thread did: ``per_member`` memberId -> (kept, fresh, pending, release),
         ``topic_withheld`` topic -> count, the totals ``kept`` / ``fresh`` / ``withheld`` / ``dropped`` / ``stale`` and
         ``followup`` (another rebalance is needed), ``sticky_kept_before`` / ``sticky_kept_after`` /
-        ``sticky_topics_passed_through`` (0 unless ``lag.assignor.sticky.ties`` is on).  last_topic_totals / last_member_loads / last_native_call describe the
+        ``sticky_topics_passed_through`` (0 unless ``lag.assignor.sticky.ties`` is on), ``pinned`` (the call was a pinned
+        follow-up, ``lag.assignor.cooperative.followup``) with ``pinned_free`` (partitions it dealt out) and ``pinned_foreign``
+        (those of them still claimed by a member that does not consume their topic).  last_topic_totals / last_member_loads / last_native_call describe the
         TARGET of that call, as after assign()."""
         d = dict(_host().LagBasedPartitionAssignor.last_cooperative_round())
         d["per_member"] = {m: tuple(int(x) for x in v) for m, v in d["per_member"].items()}

@@ -160,7 +160,7 @@ void hint_bounds(la_ctx* ctx, const Flat& f) {
 Assignment run_native(const Plan& plan, const std::vector<const TopicData*>& data, bool offsets_mode,
                       int32_t reset_mode, std::map<std::string, std::map<std::string, int64_t>>* totals_out,
                       const std::function<void(const std::string&)>* debug = nullptr, const OwnedArrays* owned = nullptr,
-                      bool sticky = false, bool sticky_large = false) {
+                      bool sticky = false, bool sticky_large = false, bool pinned = false) {
     Flat f;
     for (size_t t = 0; t < plan.topics.size(); ++t) {
         const TopicData* d = data[t];
@@ -237,23 +237,51 @@ Assignment run_native(const Plan& plan, const std::vector<const TopicData*>& dat
         a.topic_withheld = withheld.data();
         a.summary = summary.data();
         std::vector<int64_t> sticky_summary(4, 0);
-        if (sticky) {                                            // lag.assignor.sticky.ties: the lists are those of the sticky order
+        if (pinned) {
+            // lag.assignor.cooperative.followup = pinned, and this IS a follow-up: what is owned stays, only the rest is dealt
+            // out (LA_COOP_PINNED; the sticky entry does not take the flag, and there is nothing left for it to re-match).  A
+            // topic over the limits, should one get here, sends the call through the full form below.
+            a.flags |= LA_COOP_PINNED;
+            const int rc = la_assign_batch_cooperative(ctx, &a);
+            if (rc == LA_ESHAPE) {
+                pinned = false;
+                a.flags &= ~LA_COOP_PINNED;
+                hint_bounds(ctx, f);
+            } else {
+                check(ctx, rc);
+            }
+        }
+        if (!pinned && sticky) {                                 // lag.assignor.sticky.ties: the lists are those of the sticky order
             la_assign_sticky_args sa{};
             sa.struct_size = (int32_t)sizeof sa;
             sa.coop = a;
             if (sticky_large) sa.coop.flags |= LA_COOP_STICKY_LARGE;      // lag.assignor.sticky.ties.large: topics of any size
             sa.sticky_summary = sticky_summary.data();
             check(ctx, la_assign_batch_cooperative_sticky(ctx, &sa));
-        } else {
+        } else if (!pinned) {
             check(ctx, la_assign_batch_cooperative(ctx, &a));
         }
         t_last_native.pipeline = la_last_pipeline(ctx);
         t_last_native.launches = la_last_launches(ctx);
-        if (debug && *debug) {                                   // (only then: the target's eager lists, still on the device)
+        if (debug && *debug) {                                   // (only then: the target's eager lists)
             eager_off.assign(M + 1, 0);
             eager_topic.resize(n);
             eager_pid.resize(n);
-            if (n > 0) check(ctx, la_group_last_by_member(ctx, n_members, eager_off.data(), eager_topic.data(), eager_pid.data()));
+            if (pinned) {
+                // the pinned call keeps nothing on the device: the same stable grouping by rank, from the target it returned
+                std::vector<int64_t> at(M + 2, 0);               // [0]: nobody's, [r + 1]: member r's
+                for (size_t i = 0; i < n; ++i) ++at[(size_t)(target_rank[i] + 1) + 1];
+                for (size_t r = 1; r < M + 2; ++r) at[r] += at[r - 1];
+                for (size_t r = 0; r <= M; ++r) eager_off[r] = at[r + 1];
+                for (size_t t = 0; t < T; ++t)
+                    for (int64_t i = f.part_off[t]; i < f.part_off[t + 1]; ++i) {
+                        const int64_t j = at[(size_t)(target_rank[(size_t)i] + 1)]++;
+                        eager_topic[(size_t)j] = (int32_t)t;
+                        eager_pid[(size_t)j] = target_pid[(size_t)i];
+                    }
+            } else if (n > 0) {                                  // still on the device
+                check(ctx, la_group_last_by_member(ctx, n_members, eager_off.data(), eager_topic.data(), eager_pid.data()));
+            }
         }
         for (size_t r = 0; r < M; ++r)
             t_last_coop.per_member[plan.members[plan.member_of_rank[r]]] = {counts[r], counts[M + r], counts[2 * M + r], counts[3 * M + r]};
@@ -262,6 +290,10 @@ Assignment run_native(const Plan& plan, const std::vector<const TopicData*>& dat
         t_last_coop.dropped = summary[3]; t_last_coop.stale = summary[4]; t_last_coop.followup = summary[5] != 0;
         t_last_coop.sticky_kept_before = sticky_summary[0]; t_last_coop.sticky_kept_after = sticky_summary[1];
         t_last_coop.sticky_topics_passed_through = sticky_summary[3];
+        // a pinned target keeps exactly its pinned partitions, and its foreign ones are what the round withholds or drops
+        t_last_coop.pinned = pinned;
+        t_last_coop.pinned_free = pinned ? (int64_t)n - summary[0] : 0;
+        t_last_coop.pinned_foreign = pinned ? summary[2] + summary[3] : 0;
     } else if (!plan.topics.empty()) {
         std::lock_guard<std::mutex> lock(g_ctx_mutex);       // one lock over both calls: the second reads the first's results
         la_ctx* ctx = shared_ctx_locked();
@@ -407,6 +439,19 @@ void LagBasedPartitionAssignor::configure(const std::map<std::string, std::strin
         for (char& ch : v) ch = (char)std::tolower((unsigned char)ch);
         sticky_ties_large_ = v == "true";
     }
+    // lag.assignor.cooperative.followup: "full" (the default: every rebalance computes the reference's assignment over fresh
+    // lags) or "pinned" -- a follow-up rebalance deals out only what nobody owns (LA_COOP_PINNED), so that it settles
+    auto followup = consumer_group_props_.find("lag.assignor.cooperative.followup");
+    followup_pinned_ = false;
+    if (followup != consumer_group_props_.end()) {
+        std::string v = followup->second;
+        for (char& ch : v) ch = (char)std::tolower((unsigned char)ch);
+        if (v != "full" && v != "pinned")
+            throw std::invalid_argument("lag.assignor.cooperative.followup must be full or pinned, not " + followup->second);
+        followup_pinned_ = v == "pinned";
+    }
+    last_followup_ = false;
+    last_subscription_.clear();
 }
 
 int64_t LagBasedPartitionAssignor::computePartitionLag(const std::optional<OffsetAndMetadata>& partitionMetadata,
@@ -568,7 +613,20 @@ Assignment LagBasedPartitionAssignor::assignImpl(const Cluster& metadata, const 
         std::vector<std::vector<TopicPartition>> per_member;
         for (const std::string& m : plan.members) per_member.push_back(*of.at(m));
         const OwnedArrays arrays = cooperativeOwnedArrays(plan.members, plan.topics, per_member);
-        return run_native(plan, data, true, reset, &last_totals_, &debug, &arrays, sticky_ties_, sticky_ties_ && sticky_ties_large_);
+        // lag.assignor.cooperative.followup = pinned: this rebalance is the follow-up of the last one when that one asked for
+        // it and the group is the same -- member ids and every member's topic list -- and the pinned form takes every topic
+        std::map<std::string, std::vector<std::string>> subscription;
+        for (const auto& kv : hashed) subscription[kv.first] = kv.second;
+        bool pinned = followup_pinned_ && last_followup_ && subscription == last_subscription_;
+        for (size_t t = 0; pinned && t < plan.topics.size(); ++t)
+            pinned = (!data[t] || data[t]->partition.size() <= (size_t)LA_PINNED_MAX_PARTITIONS) &&
+                     plan.topic_ranks[t].size() <= (size_t)LA_PINNED_MAX_CONSUMERS;
+        last_followup_ = false;                                      // (a call that throws leaves no follow-up behind)
+        Assignment assignment = run_native(plan, data, true, reset, &last_totals_, &debug, &arrays, sticky_ties_,
+                                           sticky_ties_ && sticky_ties_large_, pinned);
+        last_followup_ = t_last_coop.followup;
+        last_subscription_ = std::move(subscription);
+        return assignment;
     }
     return run_native(plan, data, true, reset, &last_totals_, &debug);           // wrap: :152-156
 }

@@ -117,6 +117,10 @@ class LagBasedPartitionAssignor {
         // lag.assignor.sticky.ties: kept before / after the re-matching of equal-lag partitions (0 / 0 with the key off) and the
         // topics that kept the reference's order although the key is on
         int64_t sticky_kept_before = 0, sticky_kept_after = 0, sticky_topics_passed_through = 0;
+        // lag.assignor.cooperative.followup = pinned: whether this call was a pinned follow-up (LA_COOP_PINNED) and, if so, how
+        // many partitions it dealt out and how many of those a member that does not consume their topic still claims
+        bool pinned = false;
+        int64_t pinned_free = 0, pinned_foreign = 0;
     };
     static CooperativeRound lastCooperativeRound();
 
@@ -135,6 +139,12 @@ class LagBasedPartitionAssignor {
     bool stickyTies() const { return sticky_ties_; }
     // lag.assignor.sticky.ties.large as configure() read it (default false; it has no effect unless stickyTies())
     bool stickyTiesLarge() const { return sticky_ties_large_; }
+    // lag.assignor.cooperative.followup as configure() read it: false = "full" (the default), true = "pinned".  With pinned,
+    // assignCooperative deals out only the unowned partitions (la_assign_batch_cooperative with LA_COOP_PINNED) when the
+    // previous assignCooperative on this instance reported a follow-up, the member ids and every member's topic list are
+    // unchanged since then and no topic exceeds LA_PINNED_MAX_PARTITIONS / LA_PINNED_MAX_CONSUMERS; in every other case, and
+    // after an LA_ESHAPE, it is the full form, sticky or not as configured.
+    bool cooperativeFollowupPinned() const { return followup_pinned_; }
 
     // The accessors below describe the TARGET (the eager assignment) after assignCooperative, exactly as after assign().
     // Per-topic consumer totals of the last instance-level assign (the debug summary's
@@ -188,6 +198,9 @@ class LagBasedPartitionAssignor {
     std::map<std::string, std::string> metadata_consumer_props_;
     bool sticky_ties_ = false;                                           // lag.assignor.sticky.ties
     bool sticky_ties_large_ = false;                                     // lag.assignor.sticky.ties.large
+    bool followup_pinned_ = false;                                       // lag.assignor.cooperative.followup = pinned
+    bool last_followup_ = false;                                         // the last assignCooperative asked for a follow-up ...
+    std::map<std::string, std::vector<std::string>> last_subscription_;  // ... of this group: memberId -> its topic list
     std::map<std::string, std::map<std::string, int64_t>> last_totals_;
     bool last_order_exact_ = true;
 };

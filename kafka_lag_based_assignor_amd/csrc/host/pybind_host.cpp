@@ -112,6 +112,7 @@ PYBIND11_MODULE(_host, m) {
         .def("configure", &LagBasedPartitionAssignor::configure)
         .def("sticky_ties", &LagBasedPartitionAssignor::stickyTies)
         .def("sticky_ties_large", &LagBasedPartitionAssignor::stickyTiesLarge)
+        .def("cooperative_followup_pinned", &LagBasedPartitionAssignor::cooperativeFollowupPinned)
         .def("name", &LagBasedPartitionAssignor::name)
         .def("metadata_consumer_props", &LagBasedPartitionAssignor::metadataConsumerProps)
         .def("last_topic_totals", &LagBasedPartitionAssignor::lastTopicTotals)
@@ -164,6 +165,9 @@ PYBIND11_MODULE(_host, m) {
             d["sticky_kept_before"] = c.sticky_kept_before;
             d["sticky_kept_after"] = c.sticky_kept_after;
             d["sticky_topics_passed_through"] = c.sticky_topics_passed_through;
+            d["pinned"] = c.pinned;
+            d["pinned_free"] = c.pinned_free;
+            d["pinned_foreign"] = c.pinned_foreign;
             return d;
         })
         .def_static("assign_static",

@@ -1,10 +1,11 @@
 // la_api_coop.hip -- the cooperative and sticky entry points of include/lagassign.h: la_sticky_ties_device, la_cooperative_adjust_device,
-// the two round calls on device memory, la_cooperative_round on host buffers, and the two host calls that run an assign call
-// and the round on its result.  Every struct of lagassign.h is checked and turned into its la_coop.h / la_kernels.h call in ONE
+// the two round calls on device memory, la_assign_pinned_device, la_cooperative_round on host buffers, and the two host calls
+// that run an assign call (or, with LA_COOP_PINNED, the pinned assignment) and the round on its result.  Every struct of lagassign.h is checked and turned into its la_coop.h / la_kernels.h call in ONE
 // function here; the host forms stage their arrays through the shard's cooperative staging buffers by ONE helper (CoopStage).
 #include "la_ctx.h"
 
-static_assert(LA_COOP_FORCE_TABLE == 1 && LA_COOP_STICKY_LARGE == 2, "lagassign.h");
+static_assert(LA_COOP_FORCE_TABLE == 1 && LA_COOP_STICKY_LARGE == 2 && LA_COOP_PINNED == 4, "lagassign.h");
+static_assert(LA_PINNED_MAX_PARTITIONS == la::kPinnedMaxPartitions && LA_PINNED_MAX_CONSUMERS == la::kPinnedMaxConsumers, "lagassign.h");
 static_assert(LA_STICKY_GLOBAL_LAUNCHES == la::kStickyGlobalLaunches && LA_STICKY_GLOBAL_MAX_PARTITIONS == la::kStickyGlobalMaxPartitions, "lagassign.h");
 
 namespace {
@@ -260,16 +261,78 @@ LA_API int la_cooperative_round_sticky_device(la_ctx* ctx, const la_device_batch
     });
 }
 
+// la_device_batch + la_pinned_args, checked: the batch as the sticky call checks it, with the consumers an assign call has and
+// the results as outputs; the owned lists as coop_call_of checks them.
+int pinned_call_of(la_ctx* ctx, const la_device_batch* batch, const la_pinned_args* args, la::PinnedCall* out) {
+    if (!batch) return fail(ctx, LA_EINVAL, "batch is NULL");
+    if (!args) return fail(ctx, LA_EINVAL, "args is NULL");
+    if (args->struct_size < (int32_t)sizeof(la_pinned_args))
+        return fail(ctx, LA_EINVAL, "la_pinned_args.struct_size is %d, this library takes %d and above", (int)args->struct_size, (int)sizeof(la_pinned_args));
+    const la_device_batch& b = *batch;
+    const la_pinned_args& g = *args;
+    if (g.reserved != 0 || g.reserved2 != 0) return fail(ctx, LA_EINVAL, "la_pinned_args.reserved and reserved2 must be 0");
+    if (b.n_topics < 0 || b.n_partitions < 0 || b.n_consumers < 0 || g.n_members < 0 || g.n_owned < 0) return fail(ctx, LA_EINVAL, "negative size");
+    if (g.n_members > la::kMovesMaxMembers) return fail(ctx, LA_EINVAL, "n_members must be below 2^30");
+    if (b.flags & LA_FLAG_WIRE_OUT) return fail(ctx, LA_EINVAL, "LA_FLAG_WIRE_OUT: the pinned assignment writes plain results");
+    if (b.n_topics == 0 && (b.n_partitions != 0 || b.n_consumers != 0)) return fail(ctx, LA_EINVAL, "partitions or consumers without topics");
+    if (b.n_topics > 0 && (!b.d_part_off || !b.d_cons_off)) return fail(ctx, LA_EINVAL, "null offsets");
+    if (b.n_consumers > 0 && !b.d_cons_rank) return fail(ctx, LA_EINVAL, "null consumer ranks");
+    if (b.n_partitions > 0 && (!b.d_out_partition || !b.d_out_member_rank)) return fail(ctx, LA_EINVAL, "null results");
+    if (b.n_partitions > 0 && (!b.d_partition_id || (!b.d_lag && (!b.d_end_off || !b.d_committed_off))))
+        return fail(ctx, LA_EINVAL, "null per-partition input");
+    if (!b.d_lag && b.reset_mode != LA_RESET_LATEST && !b.d_begin_off && b.n_partitions > 0)
+        return fail(ctx, LA_EINVAL, "begin_off is required unless reset_mode is LA_RESET_LATEST");
+    if (g.n_owned > 0 && (!g.d_owned_member_off || !g.d_owned_topic || !g.d_owned_partition))
+        return fail(ctx, LA_EINVAL, "null owned buffer");
+    la::PinnedCall c{};
+    c.n_topics = b.n_topics;
+    c.n_members = g.n_members;
+    c.reset_latest = b.reset_mode == LA_RESET_LATEST ? 1 : 0;
+    c.n_partitions = b.n_partitions;
+    c.n_consumers = b.n_consumers;
+    c.n_owned = g.n_owned;
+    c.part_off = b.d_part_off;
+    c.cons_off = b.d_cons_off;
+    c.pid = b.d_partition_id;
+    c.cons_rank = b.d_cons_rank;
+    c.begin = b.d_begin_off;
+    c.end = b.d_end_off;
+    c.committed = b.d_committed_off;
+    c.lag = b.d_lag;
+    c.owned_off = g.d_owned_member_off;
+    c.owned_topic = g.d_owned_topic;
+    c.owned_partition = g.d_owned_partition;
+    c.out_pid = b.d_out_partition;
+    c.out_rank = b.d_out_member_rank;
+    c.out_total = b.d_out_total_lag;
+    c.topic_free = g.d_topic_free;
+    c.summary = g.d_summary;
+    *out = c;
+    return LA_OK;
+}
+
+// The pinned assignment (la_pinned.hip), on shard 0: the insert launch of the cooperative table, then one workgroup per topic.
+// The table is the shard's own buffer, not the assign scratch: the results kept for la_group_last_by_member stay as they are.
+LA_API int la_assign_pinned_device(la_ctx* ctx, const la_device_batch* batch, const la_pinned_args* args, void* stream) {
+    return shard_entry<true>(ctx, 0, "exception in la_assign_pinned_device", [&](Shard& sh) -> int {
+        la::PinnedCall c{};
+        if (int rc = pinned_call_of(ctx, batch, args, &c)) return rc;
+        hipError_t e = la::pinned_launch(sh.coop, c, sh.lanes[0].d_status, (hipStream_t)stream);
+        return e != hipSuccess ? hip_fail(ctx, e, "assign_pinned: %s") : LA_OK;
+    });
+}
+
 namespace {
 
 // ---- host arrays through the cooperative staging buffers of a shard: one copy in, the device call, one copy out, one wait ----------
 // In the order of the layout: the inputs, then the outputs; 8-byte arrays first on either side, so that every array is aligned
 // for its element.  A call plans the slots it has (the others stay empty and take no room), then: coop_stage_begin, the device
 // call over at(), coop_stage_upload, its launch, coop_stage_finish.
-enum { kInPartOff, kInOwnedOff, kInLag, kInEnd, kInCommitted, kInBegin, kInTargetPid, kInTargetRank, kInInputId, kInOwnedTopic,
-       kInOwnedPartition, kCoopStageIns,
+enum { kInPartOff, kInOwnedOff, kInConsOff, kInLag, kInEnd, kInCommitted, kInBegin, kInTargetPid, kInTargetRank, kInInputId, kInOwnedTopic,
+       kInOwnedPartition, kInConsRank, kCoopStageIns,
        kOutMemberOff = kCoopStageIns, kOutKept, kOutFresh, kOutPending, kOutRelease, kOutWithheld, kOutSummary, kOutTopicKept,
-       kOutTopicSaved, kOutStickySummary, kOutPrevOwner, kOutCoopRank, kOutListTopic, kOutListPartition, kOutSticky, kCoopStageSlots };
+       kOutTopicSaved, kOutStickySummary, kOutTargetTotal, kOutPrevOwner, kOutCoopRank, kOutListTopic, kOutListPartition, kOutSticky,
+       kOutTargetPid, kOutTargetRank, kCoopStageSlots };
 
 struct CoopStage {
     // An input: where it is copied from (null: the call fills host() itself after coop_stage_begin).  An output: where the caller
@@ -450,6 +513,100 @@ int assign_coop_call_of(la_ctx* ctx, const la_assign_coop_args* g, int32_t known
     return LA_OK;
 }
 
+// la_assign_batch_cooperative with LA_COOP_PINNED: the target is the pinned assignment.  The rebalance's inputs and the owned
+// arrays through the cooperative staging buffers of shard 0 -- one copy in; la_assign_pinned_device and then the round on the
+// device copy of its result, both on lane 0's stream; the target and the round's outputs in one copy out; one wait.  A topic
+// over the limits is LA_ESHAPE before anything is enqueued.  The caller's arrays are written only after everything succeeded.
+int assign_coop_pinned(la_ctx* ctx, const la_assign_coop_args* g) {
+    la::CoopRoundCall q{};
+    HostCall unused;
+    if (int rc = assign_coop_call_of(ctx, g, LA_COOP_FORCE_TABLE | LA_COOP_PINNED, "la_assign_coop_args.flags", unused, q)) return rc;
+    if ((g->out_partition == nullptr) != (g->out_member_rank == nullptr)) return fail(ctx, LA_EINVAL, "out_partition and out_member_rank: both or neither");
+    const int32_t T = g->n_topics;
+    if (T > 0 && (!g->part_off || !g->cons_off)) return fail(ctx, LA_EINVAL, "part_off / cons_off are NULL");
+    if (T > 0 && (g->part_off[0] != 0 || g->cons_off[0] != 0)) return fail(ctx, LA_EINVAL, "part_off / cons_off must start at 0");
+    for (int32_t t = 0; t < T; ++t) {
+        const int64_t p = g->part_off[t + 1] - g->part_off[t], c = g->cons_off[t + 1] - g->cons_off[t];
+        if (p < 0 || c < 0 || g->part_off[t + 1] > 0x7FFFFFFF || g->cons_off[t + 1] > 0x7FFFFFFF)
+            return fail(ctx, LA_EINVAL, "part_off / cons_off must ascend, up to 2^31-1 entries (topic %d)", t);
+        if (p > LA_PINNED_MAX_PARTITIONS || c > LA_PINNED_MAX_CONSUMERS)
+            return fail(ctx, LA_ESHAPE, "LA_COOP_PINNED: topic %d has %lld partitions and %lld consumers, the pinned assignment takes %d and %d",
+                        t, (long long)p, (long long)c, LA_PINNED_MAX_PARTITIONS, LA_PINNED_MAX_CONSUMERS);
+    }
+    const int64_t N = T > 0 ? g->part_off[T] : 0, K = T > 0 ? g->cons_off[T] : 0;
+    const bool latest = g->lag != nullptr || g->reset_mode == LA_RESET_LATEST;
+    const bool use_begin = !g->lag && !latest;
+    if (N > 0 && (!g->partition_id || (!g->lag && (!g->end_off || !g->committed_off)))) return fail(ctx, LA_EINVAL, "null per-partition input");
+    if (use_begin && !g->begin_off && g->n_none > 0 && (!g->none_index || !g->none_begin)) return fail(ctx, LA_EINVAL, "null sparse begin list");
+    if (use_begin && !g->begin_off && g->n_none < 0) return fail(ctx, LA_EINVAL, "negative size");
+    if (K > 0 && !g->cons_rank) return fail(ctx, LA_EINVAL, "null consumer ranks");
+    q.c.n_partitions = N;
+    if (int rc = coop_lists_of(ctx, g->member_off, g->grouped_topic, g->grouped_partition, &q)) return rc;
+
+    Shard& sh = ctx->shards[0];
+    LA_HIP(ctx, hipSetDevice(sh.device));
+    const size_t Ts = (size_t)T, Ns = (size_t)N, Ks = (size_t)K;
+    CoopStage sg{};
+    sg.in(kInPartOff, g->part_off, T > 0 ? (Ts + 1) * 8 : 0);
+    sg.in(kInConsOff, g->cons_off, T > 0 ? (Ts + 1) * 8 : 0);
+    sg.in(kInLag, g->lag, g->lag ? Ns * 8 : 0);
+    sg.in(kInEnd, g->end_off, g->lag ? 0 : Ns * 8);
+    sg.in(kInCommitted, g->committed_off, g->lag ? 0 : Ns * 8);
+    sg.in(kInBegin, g->begin_off, use_begin ? Ns * 8 : 0);       // (without a dense begin: filled from the sparse list below)
+    sg.in(kInInputId, g->partition_id, Ns * 4);
+    sg.in(kInConsRank, g->cons_rank, Ks * 4);
+    coop_stage_plan_round(sg, q, false);
+    sg.out(kOutTargetTotal, g->out_total_lag, Ks * 8, true);
+    sg.out(kOutTargetPid, g->out_partition, Ns * 4, true);
+    sg.out(kOutTargetRank, g->out_member_rank, Ns * 4, true);
+    if (int rc = coop_stage_begin(ctx, sh.coop, sg)) return rc;
+    if (use_begin && !g->begin_off && Ns) {                      // the sparse list over zeros: marshalling, the lag itself is lag_of's
+        int64_t* const begin = sg.host<int64_t>(kInBegin);
+        memset(begin, 0, Ns * 8);
+        for (int64_t i = 0; i < g->n_none; ++i)
+            if (g->none_index[i] >= 0 && g->none_index[i] < N) begin[g->none_index[i]] = g->none_begin[i];
+    }
+    la_device_batch b{};
+    b.n_topics = T;
+    b.reset_mode = latest ? LA_RESET_LATEST : g->reset_mode;
+    b.n_partitions = N;
+    b.n_consumers = K;
+    b.d_part_off = sg.at<int64_t>(kInPartOff);
+    b.d_cons_off = sg.at<int64_t>(kInConsOff);
+    b.d_partition_id = sg.at<int32_t>(kInInputId);
+    b.d_cons_rank = sg.at<int32_t>(kInConsRank);
+    b.d_lag = sg.at<int64_t>(kInLag);
+    b.d_end_off = sg.at<int64_t>(kInEnd);
+    b.d_committed_off = sg.at<int64_t>(kInCommitted);
+    b.d_begin_off = sg.at<int64_t>(kInBegin);
+    b.d_out_partition = sg.at<int32_t>(kOutTargetPid);
+    b.d_out_member_rank = sg.at<int32_t>(kOutTargetRank);
+    b.d_out_total_lag = sg.at<int64_t>(kOutTargetTotal);
+    la::CoopRoundCall d = coop_stage_round(sg, q);
+    d.c.part_off = b.d_part_off;
+    d.c.out_partition = b.d_out_partition;
+    d.c.out_member_rank = b.d_out_member_rank;
+    la_pinned_args pa{};
+    pa.struct_size = (int32_t)sizeof pa;
+    pa.n_members = g->n_members;
+    pa.n_owned = g->n_owned;
+    pa.d_owned_member_off = d.c.owned_off;
+    pa.d_owned_topic = d.c.owned_topic;
+    pa.d_owned_partition = d.c.owned_partition;
+    la::PinnedCall pc{};
+    if (int rc = pinned_call_of(ctx, &b, &pa, &pc)) return rc;
+    Lane& ln = sh.lanes[0];
+    hipStream_t st = ln.stream;
+    if (int rc = coop_stage_upload(ctx, sg, st)) return rc;
+    hipError_t e = la::pinned_launch(sh.coop, pc, ln.d_status, st);
+    if (e == hipSuccess) e = la::cooperative_round_launch(sh.coop, ln.large, d, (g->flags & LA_COOP_FORCE_TABLE) != 0, ln.d_status, st);
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(st);
+        return hip_fail(ctx, e, "assign_batch_cooperative (pinned): %s");
+    }
+    return coop_stage_finish(ctx, sg, ln, st);
+}
+
 }  // namespace
 
 LA_API int la_cooperative_round(la_ctx* ctx, const la_coop_round_args* args) {
@@ -472,6 +629,7 @@ LA_API int la_assign_batch_cooperative(la_ctx* ctx, const la_assign_coop_args* g
         if (!g) return fail(ctx, LA_EINVAL, "args is NULL");
         if (g->struct_size < (int32_t)sizeof(la_assign_coop_args))
             return fail(ctx, LA_EINVAL, "la_assign_coop_args.struct_size is %d, this library takes %d and above", (int)g->struct_size, (int)sizeof(la_assign_coop_args));
+        if (g->flags & LA_COOP_PINNED) return assign_coop_pinned(ctx, g);
         la::CoopRoundCall q{};
         HostCall c;
         if (int rc = assign_coop_call_of(ctx, g, LA_COOP_FORCE_TABLE, "la_assign_coop_args.flags", c, q)) return rc;

@@ -1,5 +1,5 @@
-// la_coop.h -- host-visible declarations of la_cooperative_adjust_device (la_coop.hip) and of la_cooperative_round[_device]
-// (la_coop_small.hip): the scratch, the call structs, the launchers (the status bit, kStatusCoop, stands with the others in
+// la_coop.h -- host-visible declarations of la_cooperative_adjust_device (la_coop.hip), of la_cooperative_round[_device]
+// (la_coop_small.hip) and of la_assign_pinned_device (la_pinned.hip): the scratch, the call structs, the launchers (the status bit, kStatusCoop, stands with the others in
 // la_kernels.h).  The entry points of lagassign.h over them, and the checks that make these call structs, are la_api_coop.hip.
 #pragma once
 #include "la_kernels.h"
@@ -33,6 +33,29 @@ __device__ __forceinline__ int64_t last_not_above(const int64_t* off, int64_t lo
     return lo;
 }
 
+// The table as a kernel sees it: keys null = nobody owns anything.  la_coop.hip fills it; la_pinned.hip reads it too.
+struct CoopTable {
+    uint64_t* keys;
+    uint32_t* owners;
+    int32_t bits;               // 1 << bits slots
+};
+
+// the member that claimed (topic, id), or -1; *st |= kStatusInternal when the walk ran out (never expected: at most half full)
+__device__ __forceinline__ int32_t coop_table_lookup(const CoopTable& t, int32_t topic, int32_t id, uint32_t* st) {
+    if (!t.keys) return -1;
+    const uint64_t mask = (1ull << t.bits) - 1;
+    const uint64_t key = coop_key(topic, id);
+    uint64_t h = coop_first_slot(key, t.bits);
+    for (uint64_t w = 0; w <= mask; ++w) {
+        const uint64_t seen = t.keys[h];
+        if (seen == 0) return -1;
+        if (seen == key) return (int32_t)t.owners[h];
+        h = (h + 1) & mask;
+    }
+    *st |= kStatusInternal;
+    return -1;
+}
+
 struct CoopScratch {            // of one shard, grown lazily: never the assign scratch (results kept on the device stay valid)
     void* table = nullptr;      // keys, then payloads
     size_t table_cap = 0;
@@ -62,6 +85,41 @@ struct CoopCall {               // la_coop_args (lagassign.h), validated
 // be had.  Sets kStatusCoop / kStatusShape / kStatusInternal.
 hipError_t cooperative_adjust_launch(CoopScratch& s, const CoopCall& c, uint32_t* status, hipStream_t stream);
 void coop_scratch_release(CoopScratch& s);
+
+// The two halves of the table's making, for a caller that joins against it with a kernel of its own (la_pinned.hip).  reserve:
+// the shard's table grown for n_owned entries, nothing enqueued (n_owned == 0: the empty table, keys null); hipErrorOutOfMemory when
+// it cannot be had.  insert: the keys zeroed on `stream`, then the insert launch over c's owned arrays (n_topics, n_members,
+// n_owned and the three owned pointers are all it reads of `c`); the number of claims, topic -1 entries included, is ADDED to
+// *claimed (null: not wanted).  Nothing is enqueued with n_owned == 0.  Sets kStatusCoop / kStatusShape / kStatusInternal.
+hipError_t coop_table_reserve(CoopScratch& s, int64_t n_owned, CoopTable* out);
+hipError_t coop_table_insert_launch(const CoopTable& t, const CoopCall& c, int64_t* claimed, uint32_t* status, hipStream_t stream);
+
+// ---- the pinned assignment: owned partitions stay, only the others are dealt out (la_pinned.hip) ---------------------------------
+// One workgroup of kPinnedThreads per topic holds the topic in its LDS: up to kPinnedMaxPartitions partitions and
+// kPinnedMaxConsumers consumers (the budget is proved by the static_asserts of la_pinned.hip).
+constexpr int kPinnedMaxPartitions = 4096;
+constexpr int kPinnedMaxConsumers = 2048;
+constexpr int kPinnedThreads = 1024;
+constexpr int kPinnedLaunches = 2;          // insert | topics: what la_last_launches reports at most (lagassign.h)
+
+struct PinnedCall {             // la_device_batch + la_pinned_args (lagassign.h), validated
+    int32_t n_topics, n_members, reset_latest;
+    int64_t n_partitions, n_consumers, n_owned;
+    const int64_t *part_off, *cons_off;
+    const int32_t *pid, *cons_rank;
+    const int64_t *begin, *end, *committed, *lag;      // as StickyCall
+    const int64_t* owned_off;
+    const int32_t *owned_topic, *owned_partition;
+    int32_t *out_pid, *out_rank;
+    int64_t* out_total;         // [K] or null
+    int64_t* topic_free;        // [T] or null
+    int64_t* summary;           // [4] or null
+};
+
+// Zeroes topic_free, summary and the table's keys on `stream`, then at most kPinnedLaunches launches (insert: skipped without
+// owned entries; topics: skipped without topics).  hipErrorOutOfMemory, with nothing enqueued, when the table cannot be had.
+// Sets kStatusUnsorted / kStatusCoop / kStatusShape / kStatusInternal.
+hipError_t pinned_launch(CoopScratch& s, const PinnedCall& c, uint32_t* status, hipStream_t stream);
 
 // ---- the round in one call: the adjusted assignment AND every member's list of it (la_coop_small.hip) ---------------------------
 // A call within ALL four limits is ONE launch of ONE workgroup that holds the (topic, id) table, the counters and the lists in

@@ -43,6 +43,7 @@ struct CoopArgs {
     uint32_t* owners;
     int32_t bits;               // the table has 1 << bits slots
     int32_t tables, stride;     // bins: copies (a power of two) and their stride in counters (odd)
+    int64_t* claimed;           // insert: where the count of claims goes (the adjust call: summary + 4); null: nowhere
     int64_t n_chunks;           // workgroup steps of the launch
 };
 
@@ -97,24 +98,13 @@ __global__ __launch_bounds__(kMovesThreads) void coop_insert_kernel(CoopArgs a) 
         }
     }
     claimed = wave_sum_u64(claimed);
-    if ((tid & (kWave - 1)) == 0 && claimed && a.c.summary) global_add(a.c.summary + 4, claimed);
+    if ((tid & (kWave - 1)) == 0 && claimed && a.claimed) global_add(a.claimed, claimed);
     if (bad) atomicOr(a.status, bad);
 }
 
 // the member that claimed (topic, id), or -1; *st |= kStatusInternal when the walk ran out
 __device__ __forceinline__ int32_t coop_lookup(const CoopArgs& a, int32_t topic, int32_t id, uint32_t* st) {
-    if (!a.keys) return -1;
-    const uint64_t mask = (1ull << a.bits) - 1;
-    const uint64_t key = coop_key(topic, id);
-    uint64_t h = coop_first_slot(key, a.bits);
-    for (uint64_t w = 0; w <= mask; ++w) {
-        const uint64_t seen = a.keys[h];
-        if (seen == 0) return -1;
-        if (seen == key) return (int32_t)a.owners[h];
-        h = (h + 1) & mask;
-    }
-    *st |= kStatusInternal;
-    return -1;
+    return coop_table_lookup(CoopTable{a.keys, a.owners, a.bits}, topic, id, st);
 }
 
 // the workgroup's bins into the outputs: one 64-bit global atomic per non-zero bin (behind a barrier)
@@ -238,36 +228,58 @@ void coop_scratch_release(CoopScratch& s) {
     s = CoopScratch{};
 }
 
-hipError_t cooperative_adjust_launch(CoopScratch& s, const CoopCall& c, uint32_t* status, hipStream_t stream) {
+hipError_t coop_table_reserve(CoopScratch& s, int64_t n_owned, CoopTable* out) {
+    *out = CoopTable{};
+    if (n_owned <= 0) return hipSuccess;
+    if (n_owned > kCoopMaxOwned) return hipErrorOutOfMemory;
+    out->bits = ceil_log2(2 * n_owned);
+    const size_t slots = (size_t)1 << out->bits;
+    const hipError_t e = grow_device(&s.table, &s.table_cap, slots * 12);
+    if (e != hipSuccess) return e;
+    out->keys = static_cast<uint64_t*>(s.table);
+    out->owners = reinterpret_cast<uint32_t*>(out->keys + slots);
+    return hipSuccess;
+}
+
+hipError_t coop_table_insert_launch(const CoopTable& t, const CoopCall& c, int64_t* claimed, uint32_t* status, hipStream_t stream) {
+    const int64_t M = c.n_members, n = c.n_owned;
+    if (n <= 0) return hipSuccess;
     hipError_t e;
-    const int64_t T = c.n_topics, N = c.n_partitions, M = c.n_members, n = c.n_owned;
     CoopArgs a{};
     a.c = c;
     a.status = status;
     a.tables = a.stride = 1;
-    if (n > 0) {
-        // the table first: when it cannot be had nothing has been enqueued
-        if (n > kCoopMaxOwned) return hipErrorOutOfMemory;
-        a.bits = ceil_log2(2 * n);
-        const size_t slots = (size_t)1 << a.bits;
-        if ((e = grow_device(&s.table, &s.table_cap, slots * 12)) != hipSuccess) return e;
-        a.keys = static_cast<uint64_t*>(s.table);
-        a.owners = reinterpret_cast<uint32_t*>(a.keys + slots);
-    }
+    a.keys = t.keys;
+    a.owners = t.owners;
+    a.bits = t.bits;
+    a.claimed = claimed;
+    if ((e = hipMemsetAsync(a.keys, 0, (size_t)8 << a.bits, stream)) != hipSuccess) return e;
+    a.n_chunks = (n + kMovesChunk - 1) / kMovesChunk;
+    // (the grid also shares the check of the M + 1 offsets: a few owned entries of very many members get workgroups for it)
+    const int64_t want = std::max<int64_t>(a.n_chunks, M / kMovesThreads + 1);
+    return M <= kMovesLdsMaxMembers ? launch_resident<coop_insert_kernel<true>>(want, kMovesThreads, (size_t)(M + 1) * 8, stream, a)
+                                    : launch_resident<coop_insert_kernel<false>>(want, kMovesThreads, 0, stream, a);
+}
+
+hipError_t cooperative_adjust_launch(CoopScratch& s, const CoopCall& c, uint32_t* status, hipStream_t stream) {
+    hipError_t e;
+    const int64_t T = c.n_topics, N = c.n_partitions, M = c.n_members;
+    CoopArgs a{};
+    a.c = c;
+    a.status = status;
+    a.tables = a.stride = 1;
+    // the table first: when it cannot be had nothing has been enqueued
+    CoopTable table{};
+    if ((e = coop_table_reserve(s, c.n_owned, &table)) != hipSuccess) return e;
+    a.keys = table.keys;
+    a.owners = table.owners;
+    a.bits = table.bits;
     for (int64_t* p : {c.member_kept, c.member_fresh, c.member_pending, c.member_release})
         if (p && M && (e = hipMemsetAsync(p, 0, (size_t)M * 8, stream)) != hipSuccess) return e;
     if (c.topic_withheld && T && (e = hipMemsetAsync(c.topic_withheld, 0, (size_t)T * 8, stream)) != hipSuccess) return e;
     if (c.summary && (e = hipMemsetAsync(c.summary, 0, 6 * 8, stream)) != hipSuccess) return e;
 
-    if (n > 0) {
-        if ((e = hipMemsetAsync(a.keys, 0, (size_t)8 << a.bits, stream)) != hipSuccess) return e;
-        a.n_chunks = (n + kMovesChunk - 1) / kMovesChunk;
-        // (the grid also shares the check of the M + 1 offsets: a few owned entries of very many members get workgroups for it)
-        const int64_t want = std::max<int64_t>(a.n_chunks, M / kMovesThreads + 1);
-        e = M <= kMovesLdsMaxMembers ? launch_resident<coop_insert_kernel<true>>(want, kMovesThreads, (size_t)(M + 1) * 8, stream, a)
-                                     : launch_resident<coop_insert_kernel<false>>(want, kMovesThreads, 0, stream, a);
-        if (e != hipSuccess) return e;
-    }
+    if ((e = coop_table_insert_launch(table, c, c.summary ? c.summary + 4 : nullptr, status, stream)) != hipSuccess) return e;
     if (T > 0 && N > 0) {
         a.n_chunks = (N + kMovesChunk - 1) / kMovesChunk;
         const int64_t want = std::max<int64_t>(a.n_chunks, T / kMovesThreads + 1);      // (as above, for the T + 1 part offsets)

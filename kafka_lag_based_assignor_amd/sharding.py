@@ -653,6 +653,112 @@ def assign_cooperative_sticky_numpy(part_off, partition_id, lag, cons_off, cons_
         max_partitions=max_partitions)
 
 
+PINNED_MAX_PARTITIONS = 4096      # LA_PINNED_MAX_PARTITIONS
+PINNED_MAX_CONSUMERS = 2048       # LA_PINNED_MAX_CONSUMERS
+
+
+def assign_pinned_numpy(part_off, partition_id, lag, cons_off, cons_rank, n_members: int, owned_off, owned_topic, owned_partition,
+                        *, strict: bool = True):
+    """la_assign_pinned_device restated on the host, rule by rule -> (out_partition int32[N], out_member_rank int32[N],
+    totals int64[K], topic_free int64[T], summary int64[4]).  For every topic: a partition whose claimant (the member whose
+    owned slice holds (topic, id); owned lists as cooperative_adjust_numpy reads them) is one of the topic's consumers is PINNED
+    and stays with it; every consumer's bin starts from its pinned partitions (count, wrapping int64 sum of lags); the
+    positions are the reference's order (lag descending, signed; id ascending); walking them in that order every other
+    partition -- unowned, or FOREIGN: claimed by a member that does not consume the topic -- goes to the consumer with the
+    least (count, total, rank), which then counts it.  A topic without consumers gets rank -1 everywhere and none of its
+    partitions is pinned.  topic_free[t]: the partitions of t that are not pinned; summary = pinned, free, foreign (part of
+    free), stale (owned entries looked at that matched no partition, topic -1 included).  With nothing owned the result is the
+    reference's assignment.  ValueError for what the device reports: offsets that do not ascend inside their arrays, a
+    cons_rank segment that does not ascend strictly, an owned topic outside [-1, T), a (topic, id) claimed twice, and a topic of
+    more than PINNED_MAX_PARTITIONS partitions or PINNED_MAX_CONSUMERS consumers -- with strict=False such a topic is skipped
+    as the device skips it (its entries of the three results stay 0, it counts nowhere).  The yardstick of
+    tests/test_pinned_gpu.py."""
+    import heapq
+
+    m = int(n_members)
+    po = np.asarray(part_off, dtype=np.int64).ravel()
+    co = np.asarray(cons_off, dtype=np.int64).ravel()
+    pid = np.asarray(partition_id, dtype=np.int64).ravel()
+    lags = np.asarray(lag, dtype=np.int64).ravel()
+    ranks = np.asarray(cons_rank, dtype=np.int64).ravel()
+    o_topic = np.asarray(owned_topic if owned_topic is not None else [], dtype=np.int64).ravel()
+    o_pid = np.asarray(owned_partition if owned_partition is not None else [], dtype=np.int64).ravel()
+    n, k_all, n_owned = pid.size, ranks.size, o_topic.size
+    if m < 0 or po.size < 1 or co.size != po.size or lags.size != n or o_pid.size != n_owned:
+        raise ValueError("n_members < 0, no part_off, or arrays that differ in length")
+    t_all = po.size - 1
+    if po[0] != 0 or po[-1] != n or (np.diff(po) < 0).any():
+        raise ValueError("part_off does not ascend from 0 to the number of partitions")
+    if co[0] != 0 or co[-1] != k_all or (np.diff(co) < 0).any():
+        raise ValueError("cons_off does not ascend from 0 to the number of consumers")
+    if owned_off is None:
+        if n_owned:
+            raise ValueError("owned entries without owned_off")
+        off = np.zeros(m + 1, dtype=np.int64)
+    else:
+        off = np.asarray(owned_off, dtype=np.int64).ravel()
+    if off.size != m + 1 or off.min() < 0 or off.max() > n_owned or (np.diff(off) < 0).any():
+        raise ValueError("owned_off must hold n_members + 1 offsets ascending inside [0, n_owned]")
+    owner, looked_at = {}, 0
+    for r in range(m):
+        for j in range(int(off[r]), int(off[r + 1])):
+            looked_at += 1
+            key = (int(o_topic[j]), int(o_pid[j]))
+            if key[0] == -1:
+                continue
+            if key[0] < -1 or key[0] >= t_all:
+                raise ValueError("an owned topic lies outside [-1, n_topics)")
+            if key in owner:
+                raise ValueError("a (topic, partition id) is claimed twice")
+            owner[key] = r
+    wrap = lambda x: ((x + (1 << 63)) & ((1 << 64) - 1)) - (1 << 63)
+    out_pid, out_rank = np.zeros(n, np.int32), np.zeros(n, np.int32)
+    totals, topic_free = np.zeros(k_all, np.int64), np.zeros(t_all, np.int64)
+    pinned = free = foreign = hits = 0
+    for t in range(t_all):
+        p0, p1, c0, c1 = int(po[t]), int(po[t + 1]), int(co[t]), int(co[t + 1])
+        r_t = ranks[c0:c1].tolist()
+        if any(b <= a for a, b in zip(r_t, r_t[1:])):
+            raise ValueError("a cons_rank segment does not ascend strictly")
+        if p1 - p0 > PINNED_MAX_PARTITIONS or c1 - c0 > PINNED_MAX_CONSUMERS:
+            if strict:
+                raise ValueError("topic %d exceeds the limits of the pinned assignment" % t)
+            continue
+        index_of = {r: k for k, r in enumerate(r_t)}
+        ids, lg = pid[p0:p1], lags[p0:p1]
+        order = np.lexsort((ids, ~lg))                               # lag descending (signed), id ascending
+        ids, lg = ids[order].tolist(), lg[order].tolist()
+        q = [owner.get((t, i), -1) for i in ids]                     # rule 1
+        k_of = [index_of.get(x, -1) if x >= 0 else -1 for x in q]
+        count, total = [0] * len(r_t), [0] * len(r_t)
+        for k, l in zip(k_of, lg):                                   # rule 2
+            if k >= 0:
+                count[k] += 1
+                total[k] = wrap(total[k] + l)
+        heap = [(count[k], total[k], r_t[k], k) for k in range(len(r_t))]
+        heapq.heapify(heap)
+        for pos, (k, l) in enumerate(zip(k_of, lg)):                 # rules 3 and 4
+            hits += q[pos] >= 0
+            if k >= 0:
+                pinned += 1
+                out_rank[p0 + pos] = q[pos]
+                continue
+            free += 1
+            foreign += q[pos] >= 0
+            topic_free[t] += 1
+            if not r_t:                                              # rule 5
+                out_rank[p0 + pos] = -1
+                continue
+            cnt, tot, r, k = heapq.heappop(heap)
+            out_rank[p0 + pos] = r
+            total[k] = wrap(tot + l)
+            heapq.heappush(heap, (cnt + 1, total[k], r, k))
+        out_pid[p0:p1] = np.asarray(ids, np.int64).astype(np.int32)
+        totals[c0:c1] = total
+    summary = np.array([pinned, free, foreign, looked_at - hits], dtype=np.int64)
+    return out_pid, out_rank, totals, topic_free, summary
+
+
 def reduce_member_loads(partitions, lag, unassigned, group=None):
     """Partial roll-ups of the ranks' shards -> the group-wide roll-up on every rank: ONE all_reduce(SUM) over a single int64
     tensor of 2 * M + 1 entries (shards are disjoint topic ranges, so the sum of the partial roll-ups IS the roll-up; int64
