@@ -172,6 +172,9 @@ extern "C" {
                                    * of more than 4096 partitions are found from h_part_off (then required) and re-matched through tables in device *
                                    * memory instead of being passed through -- see la_sticky_ties_device.  It reads host memory and may allocate:    *
                                    * not capturable                                                                                              */
+#define LA_FLAG_PINNED_LARGE 32768 /* la_assign_pinned_device only (every other entry ignores it): topics of more than 4096 partitions are found   *
+                                   * from h_part_off / h_cons_off (then required) and assigned through device memory instead of being skipped     *
+                                   * with LA_ESHAPE -- see that call.  It reads host memory and may allocate: not capturable                       */
 #define LA_FLAG_SERIAL_LARGE 512 /* large path: the batch's large topics one after another (round 3's form) instead of side by   *
                                  * side in shared launches (test hook / A-B)                                            */
 
@@ -279,6 +282,8 @@ const char *la_last_error(const la_ctx *ctx);
  *                la_cooperative_round_sticky_device (the cooperative round on the sticky order in one call);
  *                la_assign_batch_cooperative_sticky (a cooperative rebalance on the sticky order from host buffers);
  *                LA_FLAG_STICKY_LARGE, LA_COOP_STICKY_LARGE (sticky ties for topics of any size);
+ *                LA_FLAG_PINNED_LARGE, LA_COOP_PINNED_LARGE, LA_PINNED_LARGE_MAX_PARTITIONS, LA_PINNED_LARGE_LAUNCHES (the
+ *                pinned assignment for topics of any size);
  *                a shim detects them by symbol lookup (dlsym / getattr) instead of by version */
 #define LA_VERSION 500
 int la_version(void);
@@ -1124,7 +1129,8 @@ int la_assign_batch_cooperative_sticky(la_ctx *ctx, const la_assign_sticky_args 
  * from bins that start with what every consumer already holds.
  *   batch   the struct an assign call takes: topics, partition ids, the lag source (d_lag, or begin / end / committed with
  *           reset_mode, the lag computed exactly as the assign call computes it), d_cons_off / d_cons_rank, and the three result
- *           arrays.  algo, the hints, h_part_off / h_cons_off and every flag are ignored, except LA_FLAG_WIRE_OUT: LA_EINVAL.
+ *           arrays.  algo, the hints, h_part_off / h_cons_off and every flag are ignored, except LA_FLAG_WIRE_OUT: LA_EINVAL,
+ *           and LA_FLAG_PINNED_LARGE with the two host arrays (below).
  *   args    the owned lists, as la_coop_args has them, with the same rules: member r claims the entries
  *           [d_owned_member_off[r], d_owned_member_off[r+1]), entries before off[0] and from off[M] on are not looked at,
  *           topic -1 is stale; n_owned == 0: nobody owns anything and the three pointers may be NULL.
@@ -1158,9 +1164,37 @@ int la_assign_batch_cooperative_sticky(la_ctx *ctx, const la_assign_sticky_args 
  * had, and this call is ordered with the shard's other cooperative calls.  At most two kernel launches behind the memsets
  * (la_last_launches): insert the owned entries, do the topics.  The call may allocate: it must not be captured.  Buffer
  * contract as everywhere in this header.  The call runs on shard 0.
- * struct_size: sizeof(la_pinned_args) of the caller's header; less than this library's is LA_EINVAL.  reserved, reserved2: 0. */
+ * struct_size: sizeof(la_pinned_args) of the caller's header; less than this library's is LA_EINVAL.  reserved, reserved2: 0.
+ *
+ * LA_FLAG_PINNED_LARGE (batch->flags): topics of ANY size.  Without the flag nothing above changes: no host array is read,
+ * nothing is allocated, a topic over LA_PINNED_MAX_PARTITIONS is LA_ESHAPE and skipped.  With it batch->h_part_off and
+ * batch->h_cons_off are required and must ascend inside [0, N] / [0, K] (LA_EINVAL at the call otherwise, nothing enqueued).  A
+ * topic within 4096 partitions is done exactly as without the flag: same kernel, same results.  A topic of more than 4096 and at
+ * most LA_PINNED_LARGE_MAX_PARTITIONS (2^30 - 2) partitions and at most LA_PINNED_MAX_CONSUMERS consumers is a LARGE topic: it
+ * is assigned by the large form (la_pinned_large.hip) and every output is rules 1-5 bit for bit -- results, totals,
+ * d_topic_free[t] and the topic's share of d_summary.  All large topics of a call run side by side.  A topic of more than
+ * LA_PINNED_MAX_CONSUMERS consumers stays LA_ESHAPE and skipped, whatever its partitions.
+ * Large topics are read through the HOST's offsets alone.  la_sync returns LA_ESHAPE, and the call's outputs are unspecified
+ * but stay inside the arrays, when d_part_off[t], d_part_off[t+1], d_cons_off[t] or d_cons_off[t+1] differs from the host's for
+ * a large topic, or when a topic is large by the device's offsets but not by the host's.  The errors above keep their codes in
+ * a large topic (unsorted ranks, a double claim, an owned topic out of range: LA_EINVAL); an input id that appears twice in a
+ * large topic matches twice.
+ * Launches (la_last_launches): at most 2 + LA_PINNED_LARGE_LAUNCHES, whatever the number of large topics -- keys and plan of
+ * the library's radix sort, its 12 digit passes once per tile class the large topics fall into (at most three: below 2^17,
+ * below 3 x 2^20 partitions, above), classify, chunk scan, compact, levels; the count is the same for one large topic as for
+ * several of one tile class.  A flagged call without a large topic enqueues exactly what the unflagged call does and touches
+ * no new scratch.
+ * Working memory is a buffer of the shard's own, never the assign scratch (kept results stay valid), grown before anything is
+ * enqueued (LA_ENOMEM leaves nothing enqueued): per large-topic partition 24 B of sort buffers (two keys of 8, two payloads
+ * of 4), 0.5 B of the sort's look-back granules, 1 B of flags and 4 B of the free list => about 30 B, + 4 B per chunk of 1024
+ * positions, 12 B per consumer of a large topic and about 26 KiB of sort control per large topic.  A call whose large topics
+ * hold more than LA_PINNED_LARGE_MAX_PARTITIONS partitions together is LA_ENOMEM with nothing enqueued.  With large topics the
+ * call reads host memory and may allocate: it must not be captured, and flagged calls of one shard must be ordered among
+ * themselves. */
 #define LA_PINNED_MAX_PARTITIONS 4096
 #define LA_PINNED_MAX_CONSUMERS  2048
+#define LA_PINNED_LARGE_MAX_PARTITIONS ((1 << 30) - 2)
+#define LA_PINNED_LARGE_LAUNCHES 42
 typedef struct la_pinned_args {
     int32_t struct_size, reserved;           /* sizeof(la_pinned_args) of the caller's header; 0 */
     int32_t n_members, reserved2;            /* M; 0 */
@@ -1181,6 +1215,11 @@ int la_assign_pinned_device(la_ctx *ctx, const la_device_batch *batch, const la_
  * enqueued: the caller falls back to the call without the flag.  On any error the caller's outputs are left as they were.  The
  * call makes NO promise about la_group_last_by_member afterwards. */
 #define LA_COOP_PINNED 4
+/* LA_COOP_PINNED_LARGE, valid only together with LA_COOP_PINNED on la_assign_batch_cooperative (alone, or on any other entry:
+ * LA_EINVAL): the pinned assignment runs with LA_FLAG_PINNED_LARGE and the caller's part_off / cons_off as the host offsets.
+ * The call then refuses only a topic of more than LA_PINNED_MAX_CONSUMERS consumers or LA_PINNED_LARGE_MAX_PARTITIONS
+ * partitions (LA_ESHAPE, nothing enqueued). */
+#define LA_COOP_PINNED_LARGE 8
 
 #ifdef __cplusplus
 }

@@ -83,6 +83,13 @@ LA_PINNED_MAX_PARTITIONS = PINNED_MAX_PARTITIONS = 4096
 LA_PINNED_MAX_CONSUMERS = PINNED_MAX_CONSUMERS = 2048
 PINNED_MAX_LAUNCHES = 2
 LA_COOP_PINNED = 4
+# LA_FLAG_PINNED_LARGE in the batch's flags (h_part_off / h_cons_off then required): topics of more than PINNED_MAX_PARTITIONS and
+# up to PINNED_LARGE_MAX_PARTITIONS partitions go through the large form (csrc/la_pinned_large.hip) in at most
+# PINNED_LARGE_LAUNCHES more kernels; LA_COOP_PINNED_LARGE is the same for assign_batch_cooperative(pinned=True, pinned_large=True)
+LA_FLAG_PINNED_LARGE = 32768
+LA_COOP_PINNED_LARGE = 8
+LA_PINNED_LARGE_MAX_PARTITIONS = PINNED_LARGE_MAX_PARTITIONS = (1 << 30) - 2
+LA_PINNED_LARGE_LAUNCHES = PINNED_LARGE_LAUNCHES = 42
 
 EXPORTED_SYMBOLS = (
     "la_create", "la_destroy", "la_last_error", "la_version", "la_compute_lag",
@@ -1061,7 +1068,7 @@ class Context:
     def assign_batch_cooperative(self, part_off, partition_id, cons_off, cons_rank, n_members: int, owned_off, owned_topic,
                                  owned_partition, *, lag=None, begin=None, end=None, committed=None, reset_mode: int = 0,
                                  none_index=None, none_begin=None, force_table: bool = False,
-                                 out: Optional[AssignCoop] = None, pinned: bool = False) -> AssignCoop:
+                                 out: Optional[AssignCoop] = None, pinned: bool = False, pinned_large: bool = False) -> AssignCoop:
         """la_assign_batch_cooperative: a COOPERATIVE rebalance in one call -- the assign call (`lag`: assign_batch_lags; `begin`:
         assign_batch; neither: assign_batch_sparse with none_index / none_begin) and cooperative_round on its result against
         every member's owned list (owned_off int64[M+1], owned_topic / owned_partition; all three None when nobody owns
@@ -1072,7 +1079,10 @@ class Context:
         it, only the rest is dealt out), the follow-up form that settles; one copy each way through the cooperative staging
         buffers, no fused form, a topic over PINNED_MAX_PARTITIONS / PINNED_MAX_CONSUMERS raises LA_ESHAPE at the call.
         sharding.assign_cooperative_numpy with assign = the first three results of sharding.assign_pinned_numpy is the same on
-        the host."""
+        the host.
+        pinned_large: LA_COOP_PINNED_LARGE, only with pinned (LA_EINVAL otherwise) -- topics of up to PINNED_LARGE_MAX_PARTITIONS
+        partitions are taken (assign_pinned_device with LA_FLAG_PINNED_LARGE); the host form is assign_pinned_numpy with
+        max_partitions=sharding.PINNED_ANY_SIZE."""
         fn = getattr(self._lib, "la_assign_batch_cooperative", None)
         if fn is None:
             raise LagAssignError(LA_EINVAL, "this liblagassign.so has no la_assign_batch_cooperative")
@@ -1081,6 +1091,8 @@ class Context:
                                      lag, begin, end, committed, reset_mode, none_index, none_begin, force_table, out)
         if pinned:
             g.flags |= LA_COOP_PINNED
+        if pinned_large:
+            g.flags |= LA_COOP_PINNED_LARGE
         self._check(fn(self._h, ctypes.byref(g)))
         return out
 

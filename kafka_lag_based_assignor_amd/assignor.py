@@ -52,12 +52,19 @@ class LagBasedPartitionAssignor:
         4096 partitions are re-matched too instead of keeping the reference's order.
         ``lag.assignor.cooperative.followup``: ``full`` (the default) or ``pinned`` -- with ``pinned`` an assign_cooperative()
         that follows one which reported ``followup``, for the same members and topic lists, deals out only the partitions
-        nobody owns (the pinned assignment), so that the follow-up settles; any other value raises ValueError."""
+        nobody owns (the pinned assignment), so that the follow-up settles; any other value raises ValueError.
+        ``lag.assignor.cooperative.followup.large``: ``false`` (the default) or ``true``, any other value raises ValueError; no
+        effect unless the former is ``pinned`` -- the pinned follow-up then takes topics of more than 4096 partitions too
+        instead of falling back to the full form."""
         self._impl.configure({str(k): str(v) for k, v in configs.items()})
 
     def cooperative_followup(self) -> str:
         """``lag.assignor.cooperative.followup`` as configure() read it: "full" or "pinned"."""
         return "pinned" if self._impl.cooperative_followup_pinned() else "full"
+
+    def cooperative_followup_large(self) -> bool:
+        """``lag.assignor.cooperative.followup.large`` as configure() read it."""
+        return bool(self._impl.cooperative_followup_pinned_large())
 
     def sticky_ties(self) -> bool:
         """``lag.assignor.sticky.ties`` as configure() read it."""

@@ -24,7 +24,7 @@ HOST = os.path.join(HERE, "_host" + (sysconfig.get_config_var("EXT_SUFFIX") or "
 SOURCES = ["la_api.hip", "la_api_coop.hip", "la_host.hip", "la_lag.hip", "la_wave_tile.hip", "la_wave_tile_l8.hip", "la_wave_tile_l16.hip",
            "la_wave_tile_l32.hip", "la_wave_tile_l64.hip", "la_radix.hip", "la_large.hip", "la_group.hip", "la_block.hip", "la_wire.hip",
            "la_loads.hip", "la_moves.hip", "la_moves_layouts.hip", "la_verify.hip", "la_coop.hip", "la_coop_small.hip",
-           "la_sticky.hip", "la_sticky_large.hip", "la_coop_sticky_small.hip", "la_pinned.hip"]
+           "la_sticky.hip", "la_sticky_large.hip", "la_coop_sticky_small.hip", "la_pinned.hip", "la_pinned_large.hip"]
 HOST_SOURCES = ["host/lag_based_partition_assignor.cpp", "host/pybind_host.cpp"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden",
          "-Wall", "-Wextra", "-Wno-unused-parameter"] + os.environ.get("LA_EXTRA_HIPCC_FLAGS", "").split()

@@ -160,7 +160,7 @@ void hint_bounds(la_ctx* ctx, const Flat& f) {
 Assignment run_native(const Plan& plan, const std::vector<const TopicData*>& data, bool offsets_mode,
                       int32_t reset_mode, std::map<std::string, std::map<std::string, int64_t>>* totals_out,
                       const std::function<void(const std::string&)>* debug = nullptr, const OwnedArrays* owned = nullptr,
-                      bool sticky = false, bool sticky_large = false, bool pinned = false) {
+                      bool sticky = false, bool sticky_large = false, bool pinned = false, bool pinned_large = false) {
     Flat f;
     for (size_t t = 0; t < plan.topics.size(); ++t) {
         const TopicData* d = data[t];
@@ -241,11 +241,11 @@ Assignment run_native(const Plan& plan, const std::vector<const TopicData*>& dat
             // lag.assignor.cooperative.followup = pinned, and this IS a follow-up: what is owned stays, only the rest is dealt
             // out (LA_COOP_PINNED; the sticky entry does not take the flag, and there is nothing left for it to re-match).  A
             // topic over the limits, should one get here, sends the call through the full form below.
-            a.flags |= LA_COOP_PINNED;
+            a.flags |= LA_COOP_PINNED | (pinned_large ? LA_COOP_PINNED_LARGE : 0);      // (.followup.large: topics of any size)
             const int rc = la_assign_batch_cooperative(ctx, &a);
             if (rc == LA_ESHAPE) {
                 pinned = false;
-                a.flags &= ~LA_COOP_PINNED;
+                a.flags &= ~(LA_COOP_PINNED | LA_COOP_PINNED_LARGE);
                 hint_bounds(ctx, f);
             } else {
                 check(ctx, rc);
@@ -450,6 +450,18 @@ void LagBasedPartitionAssignor::configure(const std::map<std::string, std::strin
             throw std::invalid_argument("lag.assignor.cooperative.followup must be full or pinned, not " + followup->second);
         followup_pinned_ = v == "pinned";
     }
+    // lag.assignor.cooperative.followup.large: false (the default) or true -- the pinned follow-up takes topics of up to
+    // LA_PINNED_LARGE_MAX_PARTITIONS partitions (LA_COOP_PINNED_LARGE) instead of falling back to the full form from 4097 on;
+    // no effect unless the key above is "pinned"
+    auto followup_large = consumer_group_props_.find("lag.assignor.cooperative.followup.large");
+    followup_pinned_large_ = false;
+    if (followup_large != consumer_group_props_.end()) {
+        std::string v = followup_large->second;
+        for (char& ch : v) ch = (char)std::tolower((unsigned char)ch);
+        if (v != "false" && v != "true")
+            throw std::invalid_argument("lag.assignor.cooperative.followup.large must be false or true, not " + followup_large->second);
+        followup_pinned_large_ = v == "true";
+    }
     last_followup_ = false;
     last_subscription_.clear();
 }
@@ -619,11 +631,12 @@ Assignment LagBasedPartitionAssignor::assignImpl(const Cluster& metadata, const 
         for (const auto& kv : hashed) subscription[kv.first] = kv.second;
         bool pinned = followup_pinned_ && last_followup_ && subscription == last_subscription_;
         for (size_t t = 0; pinned && t < plan.topics.size(); ++t)
-            pinned = (!data[t] || data[t]->partition.size() <= (size_t)LA_PINNED_MAX_PARTITIONS) &&
+            pinned = (!data[t] || data[t]->partition.size() <= (followup_pinned_large_ ? (size_t)LA_PINNED_LARGE_MAX_PARTITIONS
+                                                                                        : (size_t)LA_PINNED_MAX_PARTITIONS)) &&
                      plan.topic_ranks[t].size() <= (size_t)LA_PINNED_MAX_CONSUMERS;
         last_followup_ = false;                                      // (a call that throws leaves no follow-up behind)
         Assignment assignment = run_native(plan, data, true, reset, &last_totals_, &debug, &arrays, sticky_ties_,
-                                           sticky_ties_ && sticky_ties_large_, pinned);
+                                           sticky_ties_ && sticky_ties_large_, pinned, pinned && followup_pinned_large_);
         last_followup_ = t_last_coop.followup;
         last_subscription_ = std::move(subscription);
         return assignment;

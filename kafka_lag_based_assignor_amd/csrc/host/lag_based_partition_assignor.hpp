@@ -145,6 +145,9 @@ class LagBasedPartitionAssignor {
     // unchanged since then and no topic exceeds LA_PINNED_MAX_PARTITIONS / LA_PINNED_MAX_CONSUMERS; in every other case, and
     // after an LA_ESHAPE, it is the full form, sticky or not as configured.
     bool cooperativeFollowupPinned() const { return followup_pinned_; }
+    // lag.assignor.cooperative.followup.large as configure() read it (default false; it has no effect unless the key above is
+    // "pinned"): the partition limit of the pinned follow-up is LA_PINNED_LARGE_MAX_PARTITIONS (LA_COOP_PINNED_LARGE)
+    bool cooperativeFollowupPinnedLarge() const { return followup_pinned_large_; }
 
     // The accessors below describe the TARGET (the eager assignment) after assignCooperative, exactly as after assign().
     // Per-topic consumer totals of the last instance-level assign (the debug summary's
@@ -199,6 +202,7 @@ class LagBasedPartitionAssignor {
     bool sticky_ties_ = false;                                           // lag.assignor.sticky.ties
     bool sticky_ties_large_ = false;                                     // lag.assignor.sticky.ties.large
     bool followup_pinned_ = false;                                       // lag.assignor.cooperative.followup = pinned
+    bool followup_pinned_large_ = false;                                 // lag.assignor.cooperative.followup.large
     bool last_followup_ = false;                                         // the last assignCooperative asked for a follow-up ...
     std::map<std::string, std::vector<std::string>> last_subscription_;  // ... of this group: memberId -> its topic list
     std::map<std::string, std::map<std::string, int64_t>> last_totals_;

@@ -113,6 +113,7 @@ PYBIND11_MODULE(_host, m) {
         .def("sticky_ties", &LagBasedPartitionAssignor::stickyTies)
         .def("sticky_ties_large", &LagBasedPartitionAssignor::stickyTiesLarge)
         .def("cooperative_followup_pinned", &LagBasedPartitionAssignor::cooperativeFollowupPinned)
+        .def("cooperative_followup_pinned_large", &LagBasedPartitionAssignor::cooperativeFollowupPinnedLarge)
         .def("name", &LagBasedPartitionAssignor::name)
         .def("metadata_consumer_props", &LagBasedPartitionAssignor::metadataConsumerProps)
         .def("last_topic_totals", &LagBasedPartitionAssignor::lastTopicTotals)

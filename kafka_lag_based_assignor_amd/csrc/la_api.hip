@@ -591,6 +591,7 @@ LA_API void la_destroy(la_ctx* ctx) {
         la::verify_scratch_release(sh.verify);
         la::sticky_scratch_release(sh.sticky);
         la::coop_scratch_release(sh.coop);
+        la::pinned_large_scratch_release(sh.pinned_large);
         if (sh.ready) (void)hipEventDestroy(sh.ready);
         for (hipEvent_t e : sh.chunk_ev) (void)hipEventDestroy(e);
         for (hipStream_t st : sh.copy_in)

@@ -4,7 +4,8 @@
 // function here; the host forms stage their arrays through the shard's cooperative staging buffers by ONE helper (CoopStage).
 #include "la_ctx.h"
 
-static_assert(LA_COOP_FORCE_TABLE == 1 && LA_COOP_STICKY_LARGE == 2 && LA_COOP_PINNED == 4, "lagassign.h");
+static_assert(LA_COOP_FORCE_TABLE == 1 && LA_COOP_STICKY_LARGE == 2 && LA_COOP_PINNED == 4 && LA_COOP_PINNED_LARGE == 8, "lagassign.h");
+static_assert(LA_PINNED_LARGE_MAX_PARTITIONS == la::kPinnedLargeMaxPartitions && LA_PINNED_LARGE_LAUNCHES == la::kPinnedLargeLaunches, "lagassign.h");
 static_assert(LA_PINNED_MAX_PARTITIONS == la::kPinnedMaxPartitions && LA_PINNED_MAX_CONSUMERS == la::kPinnedMaxConsumers, "lagassign.h");
 static_assert(LA_STICKY_GLOBAL_LAUNCHES == la::kStickyGlobalLaunches && LA_STICKY_GLOBAL_MAX_PARTITIONS == la::kStickyGlobalMaxPartitions, "lagassign.h");
 
@@ -17,6 +18,19 @@ int sticky_large_offsets_ok(la_ctx* ctx, const la_device_batch& b) {
         const int64_t p = b.h_part_off[t];
         if (p < 0 || p > b.n_partitions || (t > 0 && p < b.h_part_off[t - 1]))
             return fail(ctx, LA_EINVAL, "LA_FLAG_STICKY_LARGE: h_part_off must ascend inside [0, n_partitions] (topic %d)", t < b.n_topics ? t : t - 1);
+    }
+    return LA_OK;
+}
+
+// The host offsets a flagged pinned call reads its large topics through: both ascend inside [0, n_partitions] / [0, n_consumers]
+int pinned_large_offsets_ok(la_ctx* ctx, const la_device_batch& b) {
+    if (!b.h_part_off || !b.h_cons_off) return fail(ctx, LA_EINVAL, "LA_FLAG_PINNED_LARGE: h_part_off and h_cons_off are required");
+    for (int32_t t = 0; t <= b.n_topics; ++t) {
+        const int64_t p = b.h_part_off[t], c = b.h_cons_off[t];
+        if (p < 0 || p > b.n_partitions || (t > 0 && p < b.h_part_off[t - 1]))
+            return fail(ctx, LA_EINVAL, "LA_FLAG_PINNED_LARGE: h_part_off must ascend inside [0, n_partitions] (topic %d)", t < b.n_topics ? t : t - 1);
+        if (c < 0 || c > b.n_consumers || (t > 0 && c < b.h_cons_off[t - 1]))
+            return fail(ctx, LA_EINVAL, "LA_FLAG_PINNED_LARGE: h_cons_off must ascend inside [0, n_consumers] (topic %d)", t < b.n_topics ? t : t - 1);
     }
     return LA_OK;
 }
@@ -307,17 +321,27 @@ int pinned_call_of(la_ctx* ctx, const la_device_batch* batch, const la_pinned_ar
     c.out_total = b.d_out_total_lag;
     c.topic_free = g.d_topic_free;
     c.summary = g.d_summary;
+    if ((b.flags & LA_FLAG_PINNED_LARGE) && b.n_topics > 0)      // the large topics are found from the host's offsets
+        if (int rc = pinned_large_offsets_ok(ctx, b)) return rc;
     *out = c;
     return LA_OK;
 }
 
+// the large form's scratch and host offsets of a checked call, or none: what pinned_launch takes behind the call
+la::PinnedLargeScratch* pinned_large_of(Shard& sh, const la_device_batch& b) {
+    return (b.flags & LA_FLAG_PINNED_LARGE) && b.n_topics > 0 ? &sh.pinned_large : nullptr;
+}
+
 // The pinned assignment (la_pinned.hip), on shard 0: the insert launch of the cooperative table, then one workgroup per topic.
+// With LA_FLAG_PINNED_LARGE the topics over the LDS limit go through the large form (la_pinned_large.hip) in between, in a buffer
+// of the shard's own.
 // The table is the shard's own buffer, not the assign scratch: the results kept for la_group_last_by_member stay as they are.
 LA_API int la_assign_pinned_device(la_ctx* ctx, const la_device_batch* batch, const la_pinned_args* args, void* stream) {
     return shard_entry<true>(ctx, 0, "exception in la_assign_pinned_device", [&](Shard& sh) -> int {
         la::PinnedCall c{};
         if (int rc = pinned_call_of(ctx, batch, args, &c)) return rc;
-        hipError_t e = la::pinned_launch(sh.coop, c, sh.lanes[0].d_status, (hipStream_t)stream);
+        hipError_t e = la::pinned_launch(sh.coop, c, sh.lanes[0].d_status, (hipStream_t)stream, pinned_large_of(sh, *batch),
+                                         batch->h_part_off, batch->h_cons_off);
         return e != hipSuccess ? hip_fail(ctx, e, "assign_pinned: %s") : LA_OK;
     });
 }
@@ -516,11 +540,13 @@ int assign_coop_call_of(la_ctx* ctx, const la_assign_coop_args* g, int32_t known
 // la_assign_batch_cooperative with LA_COOP_PINNED: the target is the pinned assignment.  The rebalance's inputs and the owned
 // arrays through the cooperative staging buffers of shard 0 -- one copy in; la_assign_pinned_device and then the round on the
 // device copy of its result, both on lane 0's stream; the target and the round's outputs in one copy out; one wait.  A topic
-// over the limits is LA_ESHAPE before anything is enqueued.  The caller's arrays are written only after everything succeeded.
+// over the limits (with LA_COOP_PINNED_LARGE: over the large form's) is LA_ESHAPE before anything is enqueued.  The caller's arrays are written only after everything succeeded.
 int assign_coop_pinned(la_ctx* ctx, const la_assign_coop_args* g) {
     la::CoopRoundCall q{};
     HostCall unused;
-    if (int rc = assign_coop_call_of(ctx, g, LA_COOP_FORCE_TABLE | LA_COOP_PINNED, "la_assign_coop_args.flags", unused, q)) return rc;
+    if (int rc = assign_coop_call_of(ctx, g, LA_COOP_FORCE_TABLE | LA_COOP_PINNED | LA_COOP_PINNED_LARGE, "la_assign_coop_args.flags", unused, q)) return rc;
+    const bool any_size = (g->flags & LA_COOP_PINNED_LARGE) != 0;
+    const int64_t max_p = any_size ? (int64_t)LA_PINNED_LARGE_MAX_PARTITIONS : (int64_t)LA_PINNED_MAX_PARTITIONS;
     if ((g->out_partition == nullptr) != (g->out_member_rank == nullptr)) return fail(ctx, LA_EINVAL, "out_partition and out_member_rank: both or neither");
     const int32_t T = g->n_topics;
     if (T > 0 && (!g->part_off || !g->cons_off)) return fail(ctx, LA_EINVAL, "part_off / cons_off are NULL");
@@ -529,9 +555,9 @@ int assign_coop_pinned(la_ctx* ctx, const la_assign_coop_args* g) {
         const int64_t p = g->part_off[t + 1] - g->part_off[t], c = g->cons_off[t + 1] - g->cons_off[t];
         if (p < 0 || c < 0 || g->part_off[t + 1] > 0x7FFFFFFF || g->cons_off[t + 1] > 0x7FFFFFFF)
             return fail(ctx, LA_EINVAL, "part_off / cons_off must ascend, up to 2^31-1 entries (topic %d)", t);
-        if (p > LA_PINNED_MAX_PARTITIONS || c > LA_PINNED_MAX_CONSUMERS)
-            return fail(ctx, LA_ESHAPE, "LA_COOP_PINNED: topic %d has %lld partitions and %lld consumers, the pinned assignment takes %d and %d",
-                        t, (long long)p, (long long)c, LA_PINNED_MAX_PARTITIONS, LA_PINNED_MAX_CONSUMERS);
+        if (p > max_p || c > LA_PINNED_MAX_CONSUMERS)
+            return fail(ctx, LA_ESHAPE, "LA_COOP_PINNED: topic %d has %lld partitions and %lld consumers, the pinned assignment takes %lld and %d",
+                        t, (long long)p, (long long)c, (long long)max_p, LA_PINNED_MAX_CONSUMERS);
     }
     const int64_t N = T > 0 ? g->part_off[T] : 0, K = T > 0 ? g->cons_off[T] : 0;
     const bool latest = g->lag != nullptr || g->reset_mode == LA_RESET_LATEST;
@@ -582,6 +608,11 @@ int assign_coop_pinned(la_ctx* ctx, const la_assign_coop_args* g) {
     b.d_out_partition = sg.at<int32_t>(kOutTargetPid);
     b.d_out_member_rank = sg.at<int32_t>(kOutTargetRank);
     b.d_out_total_lag = sg.at<int64_t>(kOutTargetTotal);
+    if (any_size) {                                              // the caller's offsets are the host's
+        b.flags = LA_FLAG_PINNED_LARGE;
+        b.h_part_off = g->part_off;
+        b.h_cons_off = g->cons_off;
+    }
     la::CoopRoundCall d = coop_stage_round(sg, q);
     d.c.part_off = b.d_part_off;
     d.c.out_partition = b.d_out_partition;
@@ -598,7 +629,7 @@ int assign_coop_pinned(la_ctx* ctx, const la_assign_coop_args* g) {
     Lane& ln = sh.lanes[0];
     hipStream_t st = ln.stream;
     if (int rc = coop_stage_upload(ctx, sg, st)) return rc;
-    hipError_t e = la::pinned_launch(sh.coop, pc, ln.d_status, st);
+    hipError_t e = la::pinned_launch(sh.coop, pc, ln.d_status, st, pinned_large_of(sh, b), b.h_part_off, b.h_cons_off);
     if (e == hipSuccess) e = la::cooperative_round_launch(sh.coop, ln.large, d, (g->flags & LA_COOP_FORCE_TABLE) != 0, ln.d_status, st);
     if (e != hipSuccess) {
         (void)hipStreamSynchronize(st);

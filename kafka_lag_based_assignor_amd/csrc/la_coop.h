@@ -1,5 +1,5 @@
 // la_coop.h -- host-visible declarations of la_cooperative_adjust_device (la_coop.hip), of la_cooperative_round[_device]
-// (la_coop_small.hip) and of la_assign_pinned_device (la_pinned.hip): the scratch, the call structs, the launchers (the status bit, kStatusCoop, stands with the others in
+// (la_coop_small.hip) and of la_assign_pinned_device (la_pinned.hip, la_pinned_large.hip): the scratch, the call structs, the launchers (the status bit, kStatusCoop, stands with the others in
 // la_kernels.h).  The entry points of lagassign.h over them, and the checks that make these call structs, are la_api_coop.hip.
 #pragma once
 #include "la_kernels.h"
@@ -116,10 +116,64 @@ struct PinnedCall {             // la_device_batch + la_pinned_args (lagassign.h
     int64_t* summary;           // [4] or null
 };
 
+// ---- the pinned assignment of topics beyond the LDS limit (la_pinned_large.hip, LA_FLAG_PINNED_LARGE) ---------------------------
+// The large form: all topics of a call with more than kPinnedMaxPartitions partitions (and at most kPinnedMaxConsumers consumers)
+// side by side.  The order is the radix sort's of la_radix.h, a LargeItem per topic; the phases of the LDS kernel behind it are
+// launches over regions in device memory, the levels one workgroup per topic with the bins in LDS.
+constexpr int64_t kPinnedLargeMaxPartitions = (1 << 30) - 2;      // of one topic, and of a call's large topics together
+// keys | plan | 12 digit passes for each of the sort's three tile classes | classify | chunk scan | compact | levels
+constexpr int kPinnedLargeLaunches = 2 + 3 * 12 + 4;
+constexpr int64_t kPinnedLargeStep = 1024;      // positions of a workgroup step = the chunk of the device-wide scan
+
+struct PinnedBig {              // one large topic; every offset and size is the HOST's, inside [0, N] / [0, K]
+    int64_t p0, np, c0, nc;     // its segments of the batch
+    int64_t q0;                 // its first position in the concatenated list of all large topics' positions
+    int64_t step0;              // its first workgroup step, numbered through the topics
+    int64_t k0;                 // its first bin in the concatenated list of all large topics' consumers
+    uint64_t o_ctl, o_k0, o_k1, o_v0, o_v1;      // its sort: control block and buffers, bytes from the working memory's base
+    int32_t topic, pad;
+};
+
+struct PinnedLargeWork {        // the large form's device memory, as the kernels see it (every pointer a kernel argument)
+    char* base;                 // the working memory: the sorts live at offsets from it
+    const PinnedBig* big;       // ascending in topic; null: the call has no large topic
+    int32_t n_big;
+    int64_t n_pos, n_steps;
+    uint8_t* flag;              // [L] 1: the position is free
+    uint32_t* fpos;             // [L] the free positions (inside their topic), ascending, topic after topic
+    uint32_t* cfree;            // [n_steps] free positions of every chunk; the scan makes it exclusive
+    unsigned long long* tot;    // [1] all free positions
+    unsigned long long* ctr;    // [4 n_big] pinned | foreign | unused | unused, of every large topic
+    unsigned long long* btotal; // [consumers of the large topics] the bins' seeds
+    uint32_t* bcount;
+};
+
+struct PinnedLargeScratch {     // of one shard, grown lazily: never the assign scratch (results kept on the device stay valid)
+    void* work = nullptr;       // the sorts' buffers, per-position arrays and bins, one allocation carved into regions
+    size_t work_cap = 0;
+    StagedList list;            // the topic list and the sort's items
+    // what pinned_large_reserve found for the call it was made for (host arithmetic only)
+    int64_t n_big = 0, n_pos = 0, n_steps = 0, n_bins = 0;
+};
+
+// Lists the large topics from the host's offsets (validated by the caller: ascending inside [0, N] / [0, K]) into s.list and
+// grows s.work for them.  Enqueues nothing; s.n_big == 0 afterwards: the batch holds no such topic and nothing was touched.
+// hipErrorOutOfMemory when the memory cannot be had or the large topics hold more than kPinnedLargeMaxPartitions together.
+hipError_t pinned_large_reserve(PinnedLargeScratch& s, const PinnedCall& c, const int64_t* h_part_off, const int64_t* h_cons_off);
+// The large form behind a reserve for the same call and behind the table's insert launch: at most kPinnedLargeLaunches launches.
+// *out: the list the LDS kernel skips.  Sets kStatusUnsorted / kStatusShape / kStatusOrder / kStatusInternal.
+hipError_t pinned_large_enqueue(PinnedLargeScratch& s, const PinnedCall& c, const CoopTable& table, uint32_t* status,
+                                hipStream_t stream, PinnedLargeWork* out);
+void pinned_large_scratch_release(PinnedLargeScratch& s);
+
 // Zeroes topic_free, summary and the table's keys on `stream`, then at most kPinnedLaunches launches (insert: skipped without
 // owned entries; topics: skipped without topics).  hipErrorOutOfMemory, with nothing enqueued, when the table cannot be had.
 // Sets kStatusUnsorted / kStatusCoop / kStatusShape / kStatusInternal.
-hipError_t pinned_launch(CoopScratch& s, const PinnedCall& c, uint32_t* status, hipStream_t stream);
+// With `large` (LA_FLAG_PINNED_LARGE; h_part_off / h_cons_off validated by the caller) the topics over the partition limit are
+// assigned by the large form between the two launches: at most kPinnedLargeLaunches more, its memory grown before anything is
+// enqueued.  Without a large topic the flagged call enqueues what the unflagged one does and touches no scratch.
+hipError_t pinned_launch(CoopScratch& s, const PinnedCall& c, uint32_t* status, hipStream_t stream, PinnedLargeScratch* large = nullptr,
+                         const int64_t* h_part_off = nullptr, const int64_t* h_cons_off = nullptr);
 
 // ---- the round in one call: the adjusted assignment AND every member's list of it (la_coop_small.hip) ---------------------------
 // A call within ALL four limits is ONE launch of ONE workgroup that holds the (topic, id) table, the counters and the lists in

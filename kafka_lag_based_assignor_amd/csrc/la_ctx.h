@@ -100,6 +100,7 @@ struct Shard {
     la::VerifyScratch verify;            // la_verify_assignment_device with LA_FLAG_VERIFY_LARGE: the global form's tables and topic list
     la::StickyScratch sticky;            // la_sticky_ties_device with LA_FLAG_STICKY_LARGE: the global form's tables, sort buffers and topic list
     la::CoopScratch coop;                // la_cooperative_adjust_device: the (topic, id) table of the owned lists
+    la::PinnedLargeScratch pinned_large; // la_assign_pinned_device with LA_FLAG_PINNED_LARGE: the large form's sort buffers, lists and bins
     HostBuf zc_h;                        // zero-copy small calls: coherent, device-mapped staging the kernels read and write in place
     // pinned caller arrays (la_host_alloc): one host thread, three streams -- every H2D of the call in order on copy_in,
     // the kernels on lane 0's stream, every D2H on copy_out, chained per chunk by events (run_shard_async)

@@ -22,7 +22,10 @@
 // or a rank; every walk is bounded (a level hands out at least one partition); no thread waits for another except at a barrier.
 // The sort is the direction-free bitonic network in plain HIP: the lower index of every pair keeps the smaller record, so the
 // positions from n on, which no pair touches, stand for +infinity and any n sorts without padding.
-#include "la_coop.h"
+//
+// With LA_FLAG_PINNED_LARGE the topics over the partition limit are la_pinned_large.hip's: pinned_launch lists them from the host's
+// offsets, runs the large form between the insert launch and the kernel here, and the kernel skips a listed topic silently.
+#include "la_pinned_sort.h"
 
 namespace la {
 
@@ -43,38 +46,9 @@ struct PinnedArgs {
     PinnedCall c;
     CoopTable table;
     uint32_t* status;
+    const PinnedBig* big;       // the topics of the large form, ascending in topic (n_big == 0: none, null)
+    int32_t n_big;
 };
-
-// ascending by (key, tb) over the first n entries of LDS arrays (pay rides along); every thread of the workgroup calls it with the
-// same n, behind a barrier; ends behind one
-template <bool PAYLOAD>
-__device__ __forceinline__ void pinned_sort(uint64_t* key, uint32_t* tb, int32_t* pay, int n, int tid) {
-    int np2 = 1;
-    while (np2 < n) np2 <<= 1;
-    for (int k = 2; k <= np2; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            const bool mirror = j == (k >> 1);
-            for (int t = tid; t < (np2 >> 1); t += kPinnedThreads) {
-                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));      // bit j clear
-                const int l = mirror ? (i ^ (k - 1)) : (i | j);           // i < l
-                if (l < n) {
-                    const uint64_t ki = key[i], kl = key[l];
-                    const uint32_t ti = tb[i], tl = tb[l];
-                    if (kl < ki || (kl == ki && tl < ti)) {
-                        key[i] = kl; key[l] = ki;
-                        tb[i] = tl; tb[l] = ti;
-                        if (PAYLOAD) {
-                            const int32_t pi = pay[i];
-                            pay[i] = pay[l];
-                            pay[l] = pi;
-                        }
-                    }
-                }
-            }
-            __syncthreads();
-        }
-    }
-}
 
 __global__ __launch_bounds__(kPinnedThreads) void pinned_kernel(PinnedArgs a) {
     extern __shared__ uint64_t pinned_lds[];
@@ -97,6 +71,15 @@ __global__ __launch_bounds__(kPinnedThreads) void pinned_kernel(PinnedArgs a) {
     uint64_t n_pinned = 0, n_free = 0, n_foreign = 0;
     for (int64_t t = blockIdx.x; t < T; t += gridDim.x) {
         // (everything up to the first barrier is the same in every thread: the offsets are loaded from one address)
+        if (a.n_big > 0) {                                               // the large form's topic: not this kernel's, no error
+            int lo = 0, hi = a.n_big;
+            while (hi - lo > 1) {
+                const int mid = lo + ((hi - lo) >> 1);
+                if ((int64_t)a.big[mid].topic <= t) lo = mid;
+                else hi = mid;
+            }
+            if ((int64_t)a.big[lo].topic == t) continue;
+        }
         const int64_t p0 = c.part_off[t], p1 = c.part_off[t + 1], c0 = c.cons_off[t], c1 = c.cons_off[t + 1];
         if (p0 < 0 || p1 < p0 || p1 > N || c0 < 0 || c1 < c0 || c1 > K) { bad |= kStatusShape; continue; }
         if (p1 - p0 > kPinnedMaxPartitions || c1 - c0 > kPinnedMaxConsumers) { bad |= kStatusShape; continue; }
@@ -228,12 +211,14 @@ __global__ __launch_bounds__(kPinnedThreads) void pinned_kernel(PinnedArgs a) {
 
 }  // namespace
 
-hipError_t pinned_launch(CoopScratch& s, const PinnedCall& c, uint32_t* status, hipStream_t stream) {
+hipError_t pinned_launch(CoopScratch& s, const PinnedCall& c, uint32_t* status, hipStream_t stream, PinnedLargeScratch* large,
+                         const int64_t* h_part_off, const int64_t* h_cons_off) {
     hipError_t e;
     const int64_t T = c.n_topics;
-    // the table first: when it cannot be had nothing has been enqueued
+    // the table and the large form's memory first: when either cannot be had nothing has been enqueued
     PinnedArgs a{};
     if ((e = coop_table_reserve(s, c.n_owned, &a.table)) != hipSuccess) return e;
+    if (large && (e = pinned_large_reserve(*large, c, h_part_off, h_cons_off)) != hipSuccess) return e;
     a.c = c;
     a.status = status;
     if (c.topic_free && T && (e = hipMemsetAsync(c.topic_free, 0, (size_t)T * 8, stream)) != hipSuccess) return e;
@@ -246,6 +231,12 @@ hipError_t pinned_launch(CoopScratch& s, const PinnedCall& c, uint32_t* status, 
     owned.owned_topic = c.owned_topic;
     owned.owned_partition = c.owned_partition;
     if ((e = coop_table_insert_launch(a.table, owned, c.summary ? c.summary + 3 : nullptr, status, stream)) != hipSuccess) return e;
+    if (large && large->n_big > 0) {
+        PinnedLargeWork g{};
+        if ((e = pinned_large_enqueue(*large, c, a.table, status, stream, &g)) != hipSuccess) return e;
+        a.big = g.big;
+        a.n_big = g.n_big;
+    }
     return launch_resident_lds<pinned_kernel, kPinnedLds>(T, kPinnedThreads, kPinnedLds, stream, a);
 }
 

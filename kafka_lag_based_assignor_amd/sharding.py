@@ -655,10 +655,11 @@ def assign_cooperative_sticky_numpy(part_off, partition_id, lag, cons_off, cons_
 
 PINNED_MAX_PARTITIONS = 4096      # LA_PINNED_MAX_PARTITIONS
 PINNED_MAX_CONSUMERS = 2048       # LA_PINNED_MAX_CONSUMERS
+PINNED_ANY_SIZE = (1 << 30) - 2   # LA_PINNED_LARGE_MAX_PARTITIONS: max_partitions of a call with LA_FLAG_PINNED_LARGE
 
 
 def assign_pinned_numpy(part_off, partition_id, lag, cons_off, cons_rank, n_members: int, owned_off, owned_topic, owned_partition,
-                        *, strict: bool = True):
+                        *, strict: bool = True, max_partitions: int = PINNED_MAX_PARTITIONS):
     """la_assign_pinned_device restated on the host, rule by rule -> (out_partition int32[N], out_member_rank int32[N],
     totals int64[K], topic_free int64[T], summary int64[4]).  For every topic: a partition whose claimant (the member whose
     owned slice holds (topic, id); owned lists as cooperative_adjust_numpy reads them) is one of the topic's consumers is PINNED
@@ -671,8 +672,9 @@ def assign_pinned_numpy(part_off, partition_id, lag, cons_off, cons_rank, n_memb
     reference's assignment.  ValueError for what the device reports: offsets that do not ascend inside their arrays, a
     cons_rank segment that does not ascend strictly, an owned topic outside [-1, T), a (topic, id) claimed twice, and a topic of
     more than PINNED_MAX_PARTITIONS partitions or PINNED_MAX_CONSUMERS consumers -- with strict=False such a topic is skipped
-    as the device skips it (its entries of the three results stay 0, it counts nowhere).  The yardstick of
-    tests/test_pinned_gpu.py."""
+    as the device skips it (its entries of the three results stay 0, it counts nowhere).  max_partitions: the partition limit;
+    PINNED_ANY_SIZE stands for a call with LA_FLAG_PINNED_LARGE (the consumer limit stays).  The yardstick of
+    tests/test_pinned_gpu.py and tests/test_pinned_large_gpu.py."""
     import heapq
 
     m = int(n_members)
@@ -720,7 +722,7 @@ def assign_pinned_numpy(part_off, partition_id, lag, cons_off, cons_rank, n_memb
         r_t = ranks[c0:c1].tolist()
         if any(b <= a for a, b in zip(r_t, r_t[1:])):
             raise ValueError("a cons_rank segment does not ascend strictly")
-        if p1 - p0 > PINNED_MAX_PARTITIONS or c1 - c0 > PINNED_MAX_CONSUMERS:
+        if p1 - p0 > max_partitions or c1 - c0 > PINNED_MAX_CONSUMERS:
             if strict:
                 raise ValueError("topic %d exceeds the limits of the pinned assignment" % t)
             continue
