@@ -115,14 +115,19 @@ def case(name):
     return w, S.target(w)
 
 
+def skewed_prev(w, res, seed=3):
+    """prev_owner: the topic's lowest rank owned 60 % of everything, the others what they have now: |W| > |S| and |S| > |W|."""
+    rng = np.random.default_rng(seed)
+    first = np.repeat([int(w.cons_rank[int(w.cons_off[t])]) if w.cons_off[t + 1] > w.cons_off[t] else -1 for t in range(w.n_topics)],
+                      np.diff(w.part_off)).astype(np.int32)
+    return np.where(rng.random(w.n_partitions) < 0.6, first, res[1]).astype(np.int32)
+
+
 @functools.lru_cache(maxsize=None)
 def prev_of(name, kind="mixed", seed=3):
     w, res = case(name)
-    if kind == "skewed":        # the topic's lowest rank owned 60 % of everything, the others what they have now: |W| > |S| and |S| > |W|
-        rng = np.random.default_rng(seed)
-        first = np.repeat([int(w.cons_rank[int(w.cons_off[t])]) if w.cons_off[t + 1] > w.cons_off[t] else -1 for t in range(w.n_topics)],
-                          np.diff(w.part_off)).astype(np.int32)
-        return np.where(rng.random(w.n_partitions) < 0.6, first, res[1]).astype(np.int32)
+    if kind == "skewed":
+        return skewed_prev(w, res, seed)
     return S.draw_prev_owner(w, res, seed, kind)
 
 

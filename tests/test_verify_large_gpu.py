@@ -329,7 +329,7 @@ def test_results_kept_for_group_last_by_member_survive_the_flagged_call(torch_de
 def test_buffer_contract_with_two_large_topics(ctx, torch_dev, pattern):
     stream = _stream(torch_dev[0])
     shifts = shifts_for(pattern, INPUTS + RESULTS + OUTPUTS)
-    w = L.batch([(37, 3), (5000, 37), (1, 1), (300, 4097), (0, 2), (1025, 9)], 55)
+    w = L.two_large_batch()
     exp = V.oracle_result(w)
     hw = offset_cases.make_case(((100, 16), (4099, 5), (7, 0)), "full-range", "50%")
     h_exp = oracle.assign_flat(hw.part_off, hw.partition_id, offset_cases.java_lags(hw.begin, hw.end, hw.committed, False), hw.cons_off,

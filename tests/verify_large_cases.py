@@ -44,6 +44,11 @@ def catalogue_batch(shape):
     return batch([(64, 8), shape, (40, 0), (30, 5)], 5)
 
 
+def two_large_batch():
+    """Two large topics, one by its partitions and one by its consumers, between small ones, an empty one among them."""
+    return batch([(37, 3), (5000, 37), (1, 1), (300, 4097), (0, 2), (1025, 9)], 55)
+
+
 def yardstick(w, res, **kw):
     """sharding.verify_assignment_numpy without a size limit: what the flagged call computes."""
     return V.yardstick(w, res, max_partitions=NO_LIMIT, max_consumers=NO_LIMIT, **kw)
